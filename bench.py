@@ -284,6 +284,37 @@ def load_traffic(precision):
     return None, stale
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, outputs, lengths, seed=0):
+    """`--dump-outputs DIR`: writes what a caller of the timed path received from its last step -- every output
+    (name -> [T, N, C] log-probabilities) as DIR/<name>.npy in float32 and the frame lengths [N] as DIR/lengths.npy in
+    float64.  Above DUMP_BUDGET_BYTES in all, a fixed sample of utterances (seeded: the same from run to run) is written
+    instead, its indices in DIR/sample_utterances.npy.  Returns what was written, for the result line."""
+    import numpy as np
+
+    if "lengths" in outputs or "sample_utterances" in outputs:
+        raise ValueError(f"an output name collides with the files of --dump-outputs: {sorted(outputs)}")
+    n = len(lengths)
+    per_utterance = sum(v[:, 0].numel() for v in outputs.values()) * 4 + 8
+    keep = None
+    if per_utterance * n > DUMP_BUDGET_BYTES:
+        k = max(1, DUMP_BUDGET_BYTES // per_utterance)
+        keep = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+        outputs = {name: v[:, keep] for name, v in outputs.items()}
+        lengths = lengths[keep]
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: v.contiguous().numpy().astype(np.float32, copy=False) for name, v in outputs.items()}
+    arrays["lengths"] = lengths.numpy().astype(np.float64)
+    if keep is not None:
+        arrays["sample_utterances"] = keep.numpy().astype(np.float64)
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
+    return {"dir": directory, "files": sorted(name + ".npy" for name in arrays),
+            "bytes": sum(a.nbytes for a in arrays.values()), "utterances": len(lengths), "sampled": keep is not None}
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -348,7 +379,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true",
                     help="enqueue every pass launch by launch (AMX_FLAG_NO_GRAPH) instead of replaying its HIP graph: the same kernels; "
                          "used under rocprofv3 counter collection (tools/profile_bench.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (log-probabilities per output, frame "
+                         "lengths) as DIR/<name>.npy, at most 64 MB in all: for comparing two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     preset = CONFIG_PRESETS[args.config]
     if args.utterances is None:
         args.utterances = preset[0]
@@ -394,11 +430,13 @@ def main():
 
     graph_stats = {}
     pass_stats = {}
+    last_outputs = {}
 
-    def measure(precision, steps, warmup, batch, timing_pass=True):
+    def measure(precision, steps, warmup, batch, timing_pass=True, keep_outputs=False):
         """K timed steps (no per-kernel events: recording ~370 events costs 0.3-1.2 ms per step) bracketed by barrier +
         synchronize, max over ranks; then a second pass of K steps with HIP events around every launch for the per-kernel
-        numbers.  `batch` is this rank's device-resident shard."""
+        numbers.  `batch` is this rank's device-resident shard.  `keep_outputs`: the predictions of the last timed step (on
+        rank 0: the gathered global batch) are copied to the host into `last_outputs[precision]`."""
         est = Estimator(spec, state, device, precision)
         # equal shards are established on the host below (shard_bounds of equal-length utterances): no per-step agreement
         runner = parallel.DataParallelRunner(lambda b: est.predict(b, tfi, True, _no_graph=args.no_graph), device, dst=0,
@@ -421,10 +459,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
-        last = None
+        last = step()  # one GPU: the last step's predictions (the earlier ones are released as before)
         if runner is not None:
+            last = None  # (the previous step's gather, which step() returned: released before the drain, as before)
             last = runner.drain()  # the last gather completes (and is assembled on rank 0) inside the timed region
         torch.cuda.synchronize()
         if use_dist:
@@ -433,6 +472,9 @@ def main():
         elapsed = time.perf_counter() - t0
         if last is not None:
             last.check_ranks()  # (outside the timed region: a rank that reported a range error with its shard fails the run here)
+        if keep_outputs and last is not None:
+            # copied to the host here, outside the timed region
+            last_outputs[precision] = ({k: v.float().cpu() for k, v in last.outputs.items()}, last.lengths.cpu())
         t_tensor = torch.tensor([elapsed], dtype=torch.float64, device=device)
         if use_dist:
             dist.all_reduce(t_tensor, op=dist.ReduceOp.MAX)
@@ -568,7 +610,7 @@ def main():
         n_local = n_global
         local = Batch(audio.to(device), lengths, global_batch.language_ids)
 
-    elapsed, timing = measure(args.precision, args.steps, args.warmup, local)
+    elapsed, timing = measure(args.precision, args.steps, args.warmup, local, keep_outputs=args.dump_outputs is not None)
     w, roofline = summarize(args.precision, args.steps, timing, n_local)
     frames_global = w["frames_per_utt"] * n_global
     result = None
@@ -616,6 +658,8 @@ def main():
             # products around them: `kernels.rownorm` is then the fold's row statistics + the first / final norm), packed rows, graph
             "pass": pass_stats.get(args.precision),
         }
+        if args.dump_outputs is not None:
+            result["dump_outputs"] = dump_outputs(args.dump_outputs, *last_outputs[args.precision])
     # N > 1: the weak-scaling leg (config 2 on every GPU), reported beside the strong-scaling headline
     if world > 1 and not args.no_weak:
         w_audio, w_lengths = synthetic.make_audio(n_global, length, seed=1234 + rank)
