@@ -1,6 +1,7 @@
 // C ABI of liballophant_amx (see include/allophant_amx.h): model construction from a reference state_dict, inventory
 // composition, and the forward pass orchestration (kernel sequence on one HIP stream).
 #include "../../include/allophant_amx.h"
+#include "../../include/allophant_amx_allophones.h"
 #include "amx_common.h"
 
 #include <algorithm>
@@ -212,6 +213,13 @@ struct amx_handle_s {
     // OUTPUT_i classifiers, the final hidden state and the logits hold sum(frames) rows, utterance n at last_rowoff[n]
     bool last_packed_rows = false;
     std::vector<int> last_rowoff, last_frames;
+    // allophone layer (amx_set_allophones): per (language, q) column the unmasked entries (p, W[l, p, q]) of the reference's
+    // matrices and the accumulator start (finfo.min if the column has a masked entry, else -inf); one device allocation
+    int al_lang = 0, al_P1 = 0, al_Q1 = 0;
+    void* al_buf = nullptr;
+    size_t al_bytes = 0;
+    int *al_col_ptr = nullptr, *al_ent_p = nullptr;
+    float *al_ent_w = nullptr, *al_init = nullptr;
 };
 
 namespace {
@@ -908,6 +916,7 @@ extern "C" int amx_destroy(amx_handle h) {
     }
     for (auto& sp : h->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
+    if (h->al_buf) (void)hipFree(h->al_buf);
     delete h;
     return AMX_OK;
 }
@@ -2390,6 +2399,103 @@ extern "C" int amx_greedy_ctc_emissions(int device, const float* emissions, int6
     launch_greedy_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, tokens, timesteps, counts,
                                 scores, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "greedy CTC kernel launch failed");
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// allophone layer
+// =================================================================================================================
+extern "C" int amx_set_allophones(amx_handle h, int n_lang, int P1, int Q1, const float* matrices, const uint8_t* mask) {
+    if (!h) return AMX_EINVAL;
+    if (!h->cfg.allophone_layer) return fail(h, AMX_EINVAL, "Can't map phones to allophones with a model without an allophone layer");
+    if (!matrices || !mask) return fail(h, AMX_EINVAL, "null allophone matrices or mask");
+    const amx_class_desc* phoneme = nullptr;
+    int ci_phoneme = -1;
+    for (int ci = 0; ci < (int)h->classes.size(); ++ci)
+        if (!strcmp(h->classes[ci].name, "phoneme")) { phoneme = &h->classes[ci]; ci_phoneme = ci; }
+    if (!phoneme) return fail(h, AMX_EINVAL, "model has no phoneme classifier");
+    if (n_lang < 1) return fail(h, AMX_EINVAL, "the allophone layer needs at least one language");
+    if (Q1 != phoneme->size + 1) return fail(h, AMX_EINVAL, "allophone matrices have " + std::to_string(Q1) +
+                                              " phoneme columns, the model's phoneme classifier " + std::to_string(phoneme->size + 1));
+    // the phone block of a composition model is as wide as its inventory, checked per call by the binding
+    if (ci_phoneme != h->composed_class && P1 != phoneme->out_features)
+        return fail(h, AMX_EINVAL, "allophone matrices have " + std::to_string(P1) + " phone rows, the model's phone output " +
+                                       std::to_string(phoneme->out_features));
+    if (P1 < 1 || P1 > AL_MAX_P1) return fail(h, AMX_EINVAL, "allophone matrices need 1 to " + std::to_string(AL_MAX_P1) + " phone rows");
+    // compress: column-major walk of every language's matrix, unmasked entries only
+    const int64_t cols = (int64_t)n_lang * Q1;
+    std::vector<int> col_ptr(cols + 1), ent_p;
+    std::vector<float> ent_w, init(cols);
+    col_ptr[0] = 0;
+    for (int l = 0; l < n_lang; ++l) {
+        const int64_t base = (int64_t)l * P1 * Q1;
+        for (int q = 0; q < Q1; ++q) {
+            bool masked_any = false;
+            for (int p = 0; p < P1; ++p) {
+                const int64_t i = base + (int64_t)p * Q1 + q;
+                if (mask[i]) {
+                    masked_any = true;
+                } else {
+                    ent_p.push_back(p);
+                    ent_w.push_back(matrices[i]);
+                }
+            }
+            if (ent_p.size() > (size_t)INT32_MAX) return fail(h, AMX_EINVAL, "allophone matrices too large");
+            col_ptr[(int64_t)l * Q1 + q + 1] = (int)ent_p.size();
+            init[(int64_t)l * Q1 + q] = masked_any ? -3.40282347e+38f : -INFINITY;
+        }
+    }
+    const size_t n_ent = ent_p.size();
+    const size_t b_ptr = (cols + 1) * sizeof(int), b_init = cols * sizeof(float), b_ent = n_ent * sizeof(int);
+    const size_t bytes = b_ptr + b_init + 2 * b_ent;
+    HIPCHK(h, hipSetDevice(h->device));
+    // a map still in flight may read the previous structure
+    HIPCHK(h, hipDeviceSynchronize());
+    if (h->al_buf) {
+        HIPCHK(h, hipFree(h->al_buf));
+        h->weight_bytes -= (int64_t)h->al_bytes;
+        h->al_buf = nullptr;
+        h->al_lang = 0;
+    }
+    void* buf = nullptr;
+    if (hipMalloc(&buf, bytes ? bytes : 16) != hipSuccess) return fail(h, AMX_ENOMEM, "allophone structure allocation failed");
+    char* b = (char*)buf;
+    h->al_col_ptr = (int*)b;
+    h->al_init = (float*)(b + b_ptr);
+    h->al_ent_p = (int*)(b + b_ptr + b_init);
+    h->al_ent_w = (float*)(b + b_ptr + b_init + b_ent);
+    int rc = AMX_OK;
+    if (hipMemcpy(h->al_col_ptr, col_ptr.data(), b_ptr, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->al_init, init.data(), b_init, hipMemcpyHostToDevice) != hipSuccess ||
+        (n_ent && hipMemcpy(h->al_ent_p, ent_p.data(), b_ent, hipMemcpyHostToDevice) != hipSuccess) ||
+        (n_ent && hipMemcpy(h->al_ent_w, ent_w.data(), b_ent, hipMemcpyHostToDevice) != hipSuccess))
+        rc = fail(h, AMX_EHIP, "allophone structure upload failed");
+    if (rc) {
+        (void)hipFree(buf);
+        return rc;
+    }
+    h->al_buf = buf;
+    h->al_bytes = bytes;
+    h->weight_bytes += (int64_t)bytes;
+    h->al_lang = n_lang;
+    h->al_P1 = P1;
+    h->al_Q1 = Q1;
+    return AMX_OK;
+}
+
+extern "C" int amx_map_allophones(amx_handle h, const float* phone, int64_t stride_t, int64_t stride_n, const int32_t* language_ids,
+                                  int N, int64_t T, float* out, void* stream) {
+    if (!h) return AMX_EINVAL;
+    if (!h->al_buf) return fail(h, AMX_ESTATE, "amx_map_allophones needs amx_set_allophones first");
+    if (N < 0 || T < 0) return fail(h, AMX_EINVAL, "negative batch geometry");
+    if (N > 65535) return fail(h, AMX_EINVAL, "at most 65535 utterances per call");
+    if (T > ((int64_t)1 << 31)) return fail(h, AMX_EINVAL, "too many frames");
+    if (N == 0 || T == 0) return AMX_OK;
+    if (!phone || !language_ids || !out) return fail(h, AMX_EINVAL, "null buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_allophone_map(phone, stride_t, stride_n, language_ids, h->al_lang, N, T, h->al_P1, h->al_Q1, h->al_col_ptr, h->al_ent_p,
+                         h->al_ent_w, h->al_init, out, (hipStream_t)stream);
+    HIPCHK(h, hipGetLastError());
     return AMX_OK;
 }
 

@@ -476,6 +476,15 @@ void launch_greedy_ctc(const OutDesc* descs_dev, int n_out, const float* out, co
 void launch_greedy_ctc_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T,
                                  int C, int blank, int64_t* tokens, int64_t* timesteps, int* counts, float* scores, hipStream_t s);
 
+// allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
+// strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]
+// of ent_p / ent_w and the accumulator start col_init[l * Q1 + q]; language_ids int32 [N] in [0, n_lang)
+constexpr int AL_MAX_P1 = 16384;  // one staged phone row fills 64 KB of LDS
+int allophone_frames(int P1);
+void launch_allophone_map(const float* phone, int64_t stride_t, int64_t stride_n, const int* language_ids, int n_lang, int N,
+                          int64_t T, int P1, int Q1, const int* col_ptr, const int* ent_p, const float* ent_w,
+                          const float* col_init, float* out, hipStream_t s);
+
 // weight packing helpers (device side; run once at amx_create / amx_set_inventory)
 void launch_pack_matrix(int prec, const float* src, int rows, int cols, int64_t src_row_stride, int64_t src_col_stride,
                         float scale, void* dst, int64_t dst_plane, int64_t ldd, int cols_pad, hipStream_t s);

@@ -7,6 +7,8 @@ Mirrors (reference file:line):
   * ``Estimator.predict``    allophant/estimator.py:1035-1046
   * ``Estimator.restore``    allophant/estimator.py:1085-1126 (checkpoint dict schema estimator.py:199-249)
   * ``GreedyCTCDecoder``     allophant/predictions.py:189-207
+  * ``Estimator.map_allophones``  allophant/estimator.py:1048-1049 -> AllophoneMapping.map_allophones
+                             (allophant/network/acoustic_model.py:142-159)
 
 PyTorch is used only as plumbing (device memory for inputs/outputs, the current HIP stream); all arithmetic happens in the
 HIP kernels behind the C ABI.
@@ -200,6 +202,14 @@ def _spec_to_structs(spec: Dict[str, Any], precision: str):
     return cfg, descs
 
 
+ALLOPHONE_MATRICES_KEY = "_projection._layers.phoneme._allophone_layer._allophone_matrices"
+_NO_ALLOPHONE_LAYER = "Can't map phones to allophones with a model without an allophone layer"  # acoustic_model.py:546
+
+
+def _allophone_field(mapping, name: str):
+    return mapping.get(name) if isinstance(mapping, dict) else getattr(mapping, name, None)
+
+
 class Estimator:
     """Prediction-side replacement of the reference ``Estimator`` running on one MI355X.
 
@@ -220,9 +230,13 @@ class Estimator:
         cfg, descs = _spec_to_structs(spec, precision)
         keep = []
         tensors = (_lib.AmxTensor * len(state_dict))()
+        # the trained allophone matrices stay on the host: set_allophones compresses them under the mapping's structure
+        self._allophone_values: Optional[Tensor] = None
         for i, (k, v) in enumerate(state_dict.items()):
             t = v.detach().to("cpu", torch.float32).contiguous()
             keep.append(t)
+            if k == ALLOPHONE_MATRICES_KEY:
+                self._allophone_values = t
             tensors[i].name = k.encode()
             tensors[i].data = C.cast(t.data_ptr(), C.POINTER(C.c_float))
             tensors[i].numel = t.numel()
@@ -231,6 +245,8 @@ class Estimator:
         _lib.check(self._lib, None, code)
         self._handle = handle
         self._classes = [c["name"] for c in spec["classes"]]
+        self._allophone_shape: Optional[Tuple[int, int, int]] = None  # (languages, P+1, Q+1) of the installed structure
+        self._allophone_index_map: Optional[Dict[str, int]] = None
         self._inventory: Optional[Tensor] = None
         self._training_inventory: Optional[Tensor] = None
         cats = spec.get("composition_categories")
@@ -272,6 +288,11 @@ class Estimator:
             # (`_dense_feature_table`, acoustic_model.py:214-221); it is a non-persistent buffer there, rebuilt from the
             # indexer at construction, so it is rebuilt from the embedded table here as well
             estimator.set_training_inventory(indexer.composition_feature_matrix(training))
+        language_allophones = (checkpoint_or_path.get("phonetic_indexer_state") or {}).get("language_allophones")
+        if spec.get("allophone_layer") and language_allophones:
+            # upstream rebuilds the allophone layer's structure from the same dump (`Allophant.from_config` ->
+            # AllophoneMapping.__init__), with or without an embedded attribute table
+            estimator.set_allophones(language_allophones)
         return estimator, indexer
 
     def set_training_inventory(self, target_feature_indices: Tensor) -> None:
@@ -280,6 +301,95 @@ class Estimator:
         if not self._spec.get("embedding_size"):
             raise ValueError("model has no embedding composition layer")
         self._training_inventory = target_feature_indices.detach().to("cpu", torch.int64).contiguous()
+
+    # -- allophone layer ---------------------------------------------------------------------------------------------
+    def set_allophones(self, language_allophones) -> None:
+        """Installs the allophone layer of ``map_allophones``: the structure (``_allophone_mask``) comes from the
+        ``LanguageAllophoneMappings`` dump like upstream's ``AllophoneMapping.__init__`` (acoustic_model.py:105-136), the
+        values from the state dict's trained ``_allophone_matrices``.  A second call replaces the first."""
+        from .allophones import build_structure
+
+        if not self._spec.get("allophone_layer"):
+            raise ValueError(_NO_ALLOPHONE_LAYER)
+        if self._allophone_values is None:
+            raise ValueError(f"the state dict lacks {ALLOPHONE_MATRICES_KEY}")
+        if not hasattr(self._lib, "amx_set_allophones"):
+            raise RuntimeError(f"{_lib.LIB_PATH} predates the allophone layer (amx_set_allophones): rebuild it")
+        P1, Q1 = self._allophone_widths()
+        values = self._allophone_values
+        shared = list(_allophone_field(language_allophones, "shared_phones") or [])
+        if shared and len(shared) + _spec.BLANK_OFFSET != P1:
+            raise ValueError(f"language_allophones lists {len(shared)} shared phones, the model predicts {P1 - _spec.BLANK_OFFSET}")
+        structure = build_structure(language_allophones, P1, Q1)
+        n_lang = structure.mask.shape[0]
+        if tuple(values.shape) != (n_lang, P1, Q1):
+            raise ValueError(f"_allophone_matrices is {list(values.shape)}, the mapping and the model need {[n_lang, P1, Q1]}")
+        mask = structure.mask.to(torch.uint8).contiguous()
+        with torch.cuda.device(self._device):
+            code = self._lib.amx_set_allophones(self._handle, n_lang, P1, Q1, C.cast(values.data_ptr(), C.POINTER(C.c_float)),
+                                                C.cast(mask.data_ptr(), C.POINTER(C.c_uint8)))
+        _lib.check(self._lib, self._handle, code)
+        self._allophone_shape = (n_lang, P1, Q1)
+        self._allophone_index_map = structure.index_map
+
+    @property
+    def allophone_languages(self) -> Dict[str, int]:
+        """Language code -> matrix index of the installed allophone layer (upstream ``AllophoneMapping.index_map``): the
+        ``language_ids`` ``map_allophones`` takes."""
+        if self._allophone_index_map is None:
+            raise ValueError(_NO_ALLOPHONE_LAYER if not self._spec.get("allophone_layer") else
+                             "no allophone mapping installed: restore from a checkpoint with language_allophones or call set_allophones()")
+        return dict(self._allophone_index_map)
+
+    def _allophone_widths(self) -> Tuple[int, int]:
+        phoneme = next(c for c in self._spec["classes"] if c["name"] == _spec.PHONEME)
+        return int(self._spec.get("shared_phones", phoneme["size"])) + _spec.BLANK_OFFSET, int(phoneme["size"]) + _spec.BLANK_OFFSET
+
+    def map_allophones(self, phone_logits: Tensor, language_ids) -> Tensor:
+        """``Estimator.map_allophones`` (reference estimator.py:1048-1049, AllophoneMapping.map_allophones
+        acoustic_model.py:142-159): language-specific phoneme outputs ``[T, N, Q+1]`` from phone outputs ``[T, N, P+1]``
+        (``predict(...).outputs["phone"]`` goes in as it is; any strides with a unit class stride), on the device and the
+        current stream.  ``out[t, n, q] = max_p(x[t, n, p] * W[l, p, q])`` over the allophones p of phoneme q in language
+        ``l = int(language_ids[n])`` (Python indexing: -1 is the last language), ``finfo(float32).min`` standing in for every
+        masked pair; bitwise upstream's values.  Not renormalised.  There is no CPU path."""
+        if not self._spec.get("allophone_layer"):
+            raise ValueError(_NO_ALLOPHONE_LAYER)
+        if phone_logits.device.type != "cuda":
+            raise RuntimeError("allophant_amd maps allophones on an MI355X only (phone_logits must be a cuda tensor); there is no CPU fallback")
+        if self._allophone_shape is None:
+            raise RuntimeError("no allophone mapping installed: restore from a checkpoint with language_allophones or call set_allophones()")
+        if phone_logits.device != self._device:
+            raise ValueError(f"phone_logits is on {phone_logits.device}, the estimator on {self._device}")
+        if phone_logits.dim() != 3:
+            raise ValueError("phone_logits must be [T, N, P+1]")
+        n_lang, P1, Q1 = self._allophone_shape
+        T, N, width = phone_logits.shape
+        if width != P1:
+            raise ValueError(f"phone_logits has {width} classes, the allophone layer maps {P1} (shared phones + blank): a "
+                             "custom composition inventory has no allophone matrices")
+        if phone_logits.dtype != torch.float32:
+            phone_logits = phone_logits.float()
+        if phone_logits.stride(2) != 1:
+            phone_logits = phone_logits.contiguous()
+        ids_host = language_ids.detach().cpu() if isinstance(language_ids, Tensor) else language_ids
+        ids = [int(v) for v in ids_host]  # upstream: map(int, language_ids)
+        if len(ids) != N:
+            raise ValueError(f"{len(ids)} language ids for {N} utterances")
+        for i, v in enumerate(ids):
+            if not -n_lang <= v < n_lang:
+                raise IndexError(f"index {v} is out of bounds for dimension 0 with size {n_lang}")
+            ids[i] = v % n_lang
+        out = torch.empty(T, N, Q1, dtype=torch.float32, device=self._device)
+        if N == 0 or T == 0:
+            return out
+        with torch.cuda.device(self._device):
+            dense = torch.tensor(ids, dtype=torch.int32).to(self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            code = self._lib.amx_map_allophones(
+                self._handle, C.c_void_p(phone_logits.data_ptr()), phone_logits.stride(0), phone_logits.stride(1),
+                C.c_void_p(dense.data_ptr()), N, T, C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(self._lib, self._handle, code)
+        return out
 
     def _set_inventory(self, tfi: Tensor) -> None:
         tfi_cpu = tfi.detach().to("cpu", torch.int64).contiguous()

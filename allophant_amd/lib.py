@@ -36,6 +36,8 @@ EXPORTS = [
     "amx_max_utterances", "amx_greedy_ctc_emissions", "amx_check_finite", "amx_gather_outputs", "amx_dist_last_error",
     "amx_graph_info", "amx_pass_info",
 ]
+# the allophone-layer entry points (include/allophant_amx_allophones.h; added to ABI 6, detected by name)
+ALLOPHONE_EXPORTS = ["amx_set_allophones", "amx_map_allophones"]
 
 
 def dep_output_layer(i: int) -> int:
@@ -106,6 +108,11 @@ def load() -> C.CDLL:
     if hasattr(lib, "amx_pass_info") or AMX_ABI_VERSION >= 6:  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_pass_info.argtypes = [vp, C.POINTER(C.c_int32), i32]
         lib.amx_pass_info.restype = i32
+    if hasattr(lib, "amx_map_allophones"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_set_allophones.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
+        lib.amx_set_allophones.restype = i32
+        lib.amx_map_allophones.argtypes = [vp, vp, i64, i64, vp, i32, i64, vp, vp]
+        lib.amx_map_allophones.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
