@@ -409,12 +409,8 @@ static void fold_layer_norm(const float* W, const float* b, const float* gamma, 
 }
 
 // power of two that puts the largest |w * pre| of the listed tensors into [4096, 8192); 1 for empty / zero / non-finite data
-static bool pack_scale_off() {  // AMX_NO_PACK_SCALE=1: developer A/B switch (unscaled planes, as before round 3)
-    static const bool off = dev_switch("AMX_NO_PACK_SCALE");
-    return off;
-}
 static float pow2_for(float m) {
-    if (pack_scale_off() || !(m > 0.f) || !std::isfinite(m)) return 1.f;
+    if (!(m > 0.f) || !std::isfinite(m)) return 1.f;
     return std::ldexp(1.f, 12 - std::ilogb(m));
 }
 static float pack_scale(std::initializer_list<std::pair<const amx_tensor*, float>> tensors) {
@@ -480,12 +476,9 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
     h->gn = cfg->feat_extract_norm == AMX_NORM_GROUP;
     h->stable = cfg->stable_layer_norm != 0;
     h->masked = cfg->use_attention_mask != 0;
-    {
-        static const bool plain = dev_switch("AMX_PLAIN_PLANES");  // developer A/B switch
-        // (hidden too -- round 6: the residual-stream planes [M, hidden] are GEMM operands like the others; a hidden size off the
-        // 32-element blocks -- 240 = 2 heads of 120 -- ran interleaved planes through kernels that assume block-aligned rows)
-        h->il = h->NT > 1 && !plain && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
-    }
+    // (hidden too -- round 6: the residual-stream planes [M, hidden] are GEMM operands like the others; a hidden size off the
+    // 32-element blocks -- 240 = 2 heads of 120 -- ran interleaved planes through kernels that assume block-aligned rows)
+    h->il = h->NT > 1 && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
     h->classes.assign(classes, classes + n_classes);
     auto bail = [&](int code) {
         g_create_error = h->err;
@@ -1478,9 +1471,8 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
 #define WS(name, bytes, ptr) do { if ((rc = ws_get(h, name, (size_t)(bytes), &ptr))) return rc; } while (0)
     // split-K workspace (fp32 partial slabs of products too small to fill the chip; see launch_gemm): the partials of one
     // product never exceed CUs x 256 x 256 floats
-    void* splitk = nullptr;
-    static const bool no_splitk = dev_switch("AMX_NO_SPLITK");  // developer A/B switch
-    if (!no_splitk) WS("splitk", SPLITK_BYTES, splitk);
+    void* splitk;
+    WS("splitk", SPLITK_BYTES, splitk);
     WS("len", (size_t)N * 8, d_len);
     WS("frames", (size_t)N * 4, d_frames);
     void* d_rowoff;
@@ -1509,12 +1501,11 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     // utterances back to back): every kernel of a layer is row-wise except the attention, which takes the offsets.  A row's
     // arithmetic does not depend on its position, so the valid frames come out as in the padded layout (the same bits when
     // the products pick the same kernels for the smaller row count, within rounding of the K-chunk order otherwise).  Used
-    // when at least a tenth of the padded rows are padding (not under AMX_FLAG_KEEP_HIDDEN); AMX_FLAG_NO_PACK /
-    // AMX_NO_PACKED_ROWS=1 keep the padded layout.
-    static const bool no_pack_env = dev_switch("AMX_NO_PACKED_ROWS");
+    // when at least a tenth of the padded rows are padding (not under AMX_FLAG_KEEP_HIDDEN); AMX_FLAG_NO_PACK keeps the padded
+    // layout.
     const bool any_hidden = keep;  // the debug capture wants every hidden state in the padded layout, padding included
     const int TpTot = round_up((int)Mp, 64) + 64;  // rows per head of the packed Q / K / V planes
-    bool packed = !no_pack_env && !(flags & AMX_FLAG_NO_PACK) && !any_hidden && D % 4 == 0 && Mp * 10 <= M * 9 &&
+    bool packed = !(flags & AMX_FLAG_NO_PACK) && !any_hidden && D % 4 == 0 && Mp * 10 <= M * 9 &&
                   (int64_t)TpTot <= (int64_t)N * Tp;
     // Packed from the feature projection on ("early"): the last conv layer's LayerNorm pass gathers the valid frames, so the
     // feature projection, the positional convolution (window kernel: skips the frame blocks beyond an utterance), the final
@@ -1522,14 +1513,12 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     // Needs the window kernel (the grouped-GEMM form of the positional convolution addresses padded rows) and no time-layer
     // head (its attention walks (utterance, frame) pairs); otherwise the rows are packed after the positional convolution
     // and unpacked before the final LayerNorm, as in round 2.
-    static const bool no_window = dev_switch("AMX_NO_POSCONV_WINDOW");  // developer A/B switch
-    static const bool late_pack = dev_switch("AMX_PACK_LATE");          // developer A/B switch
-    const bool window_ok = !no_window && posconv_window_eligible(D, c.pos_groups, c.pos_kernel, N, T, Tpad, (int64_t)N * Tpad * D);
+    const bool window_ok = posconv_window_eligible(D, c.pos_groups, c.pos_kernel, N, T, Tpad, (int64_t)N * Tpad * D);
     bool any_time_layer = false;
     for (auto& st : h->steps) any_time_layer |= st.time_heads > 0;
     // (the post-LN encoder has no LayerNorm pass between its last layer and the heads to unpack behind: it packs early or not at all)
-    if (!h->stable && !(window_ok && !any_time_layer && !late_pack)) packed = false;
-    const bool packed_early = packed && window_ok && !any_time_layer && !late_pack;
+    if (!h->stable && !(window_ok && !any_time_layer)) packed = false;
+    const bool packed_early = packed && window_ok && !any_time_layer;
     void* hpk = nullptr;
     if (packed) WS("h_packed", (size_t)Mp * D * 4, hpk);
     const float* d_audio = audio;
@@ -1568,7 +1557,7 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     // (only from a tenth of padding on -- the threshold of the packed rows: below it the padded frames are simply computed, and
     // NOTHING of the pass depends on the lengths by value any more -- lengths, frame counts and masks are device buffers the plan
     // refreshes -- so a recording of this (N, L) geometry serves every batch of that geometry: see the key below)
-    const bool ragged = Mp < M && Mp * 10 <= M * 9 && !keep && !no_pack_env && !(flags & AMX_FLAG_NO_PACK);
+    const bool ragged = Mp < M && Mp * 10 <= M * 9 && !keep && !(flags & AMX_FLAG_NO_PACK);
     // per conv layer i >= 1: the ascending list of its 128-row output tiles that hold a row some utterance owns
     int* d_tiles = nullptr;
     size_t tile_first[AMX_MAX_CONV + 1] = {0};
@@ -1752,11 +1741,9 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
         P.rowoff_host.assign(pin_rowoff, pin_rowoff + N);
         P.frames_host.assign(pin_frames, pin_frames + N);
     }
-    // LayerNorm fold: decided on the products as they will be launched (AMX_NO_LN_FOLD / AMX_FOLD_F32_STREAM: developer A/B switches)
-    static const bool no_ln_fold = dev_switch("AMX_NO_LN_FOLD");
-    static const bool f32_stream = dev_switch("AMX_FOLD_F32_STREAM");
-    P.stream_in_planes = NT == 2 && !f32_stream;
-    if (stable && !no_ln_fold && c.layers > 0 && D % 64 == 0 && D <= 2048) {
+    // LayerNorm fold: decided on the products as they will be launched
+    P.stream_in_planes = NT == 2;
+    if (stable && c.layers > 0 && D % 64 == 0 && D <= 2048) {
         WS("ln_rowps", (size_t)Mrows * 16, P.ln_rowps);
         WS("ln_coef", (size_t)Mrows * 8, P.ln_coef);
         WS("ln_partial", (size_t)Mrows * (D / 64) * 8, P.ln_partial);
@@ -1934,9 +1921,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
             GemmParams f = g;
             f.act = 1; f.ln_gamma = h->conv_g[i]; f.ln_beta = h->conv_be[i]; f.ln_eps = 1e-5f;
             f.out_p = other; f.out_plane = out_plane; f.ldp = C;
-            // AMX_NO_FUSED_CONV_LN=1: developer A/B switch (separate fp32 GEMM output + row kernel)
-            static const bool no_fuse = dev_switch("AMX_NO_FUSED_CONV_LN");
-            if (!no_fuse && gemm_fuses_ln(prec, f)) {
+            if (gemm_fuses_ln(prec, f)) {
                 if (h->conv_w_tm[i] && gemm_ln_tap_minor_slice(prec, f) == h->conv_tm_slice) {
                     // tap-minor K order: the input row two output rows share is fetched in adjacent slices (an L2 hit)
                     f.W = h->conv_w_tm[i];
@@ -1992,7 +1977,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         float* hcur = (float*)(packed_early ? hpk : hbuf);
         { Timed t_(h, AMX_KC_OTHER); launch_posconv_pack(prec, hcur, N, T, D, c.pos_groups, c.pos_kernel / 2, Tpad, hg,
                             (int64_t)N * Tpad * D, pk_off, pk_len, s); }
-        // AMX_NO_POSCONV_WINDOW=1: developer A/B switch (grouped implicit GEMM on the tile kernels instead)
+        // the window kernel where it takes the shape, the grouped implicit GEMM on the tile kernels otherwise
         if (window_ok) {
             Timed t_(h, AMX_KC_GEMM_TILE);
             launch_posconv_window(prec, hg, (int64_t)N * Tpad * D, h->pos_w, (int64_t)D * cg * c.pos_kernel,
@@ -2017,12 +2002,10 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         hbuf = hpk;
     }
     // A residual product that launch_gemm cuts into K chunks (short batches) leaves its fix-up -- slab sum + bias + residual
-    // -> h -- to the LayerNorm that follows it: one kernel instead of the fix-up and a LayerNorm pass that re-reads h
-    // (AMX_NO_FUSED_FIXUP=1: developer A/B switch).
-    static const bool no_fused_fixup = dev_switch("AMX_NO_FUSED_FIXUP");
+    // -> h -- to the LayerNorm that follows it: one kernel instead of the fix-up and a LayerNorm pass that re-reads h.
     struct { bool on = false; GemmParams g; int splits = 0; } pending;
     auto residual_gemm = [&](GemmParams g, bool may_defer) {
-        const int splits = may_defer && !no_fused_fixup ? gemm_planned_splits(prec, g) : 1;
+        const int splits = may_defer ? gemm_planned_splits(prec, g) : 1;
         if (splits > 1 && fixup_rownorm_eligible(g)) {
             g.defer_fixup = 1;
             pending.on = true;
@@ -2052,10 +2035,8 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         Timed t_(h, AMX_KC_ROWNORM);
         launch_ln_finalize((const float2*)ln_partial, D / 64, Mrows, c.eps, (float4*)ln_rowps, (float2*)ln_coef, s);
     };
-    // developer timing switch (WRONG results: every layer runs on layer 0's weights): what weights that are already on the chip are worth
-    static const bool share_weights = dev_switch("AMX_DEV_SHARE_LAYER_WEIGHTS");
     for (int l = 0; l < c.layers; ++l) {
-        const Layer& ly = h->layers[share_weights ? 0 : l];
+        const Layer& ly = h->layers[l];
         if (fold) {
             // the first norm of the stack from the stream itself; later ones: the previous FFN2 left planes and statistics
             if (l == 0) {
@@ -2275,13 +2256,6 @@ extern "C" int amx_forward(amx_handle h, const float* audio, const int64_t* leng
                     entry.key = key;
                     entry.exec = exec;
                     entry.graph = graph;
-                    // AMX_GRAPH_DROP_TEMPLATE=1 (developer switch, tools/r06_graph_fault.sh): the round-5 code before its fix --
-                    // the template destroyed right after instantiation, only the executable kept
-                    static const bool drop_template = dev_switch("AMX_GRAPH_DROP_TEMPLATE");
-                    if (drop_template) {
-                        (void)hipGraphDestroy(graph);
-                        entry.graph = nullptr;
-                    }
                     entry.last_use = ++h->graph_clock;
                     entry.last_stream = s;
                     h->graphs.push_back(std::move(entry));

@@ -889,9 +889,8 @@ void launch_attn2_layout(const AttnParams& p, int cus, hipStream_t stream) {
     if (grid > items) grid = items;
     // WAVES == 4: one item per workgroup -- the hardware dispatcher hands them out as workgroups retire, which balances the two
     // workgroups of a CU (the younger one loses the issue arbitration and runs ~20 % slower: with a static split of the items
-    // it sets the span).  AMX_ATTN2_PERSISTENT=1: developer A/B switch
-    static const bool persistent4 = dev_switch("AMX_ATTN2_PERSISTENT");
-    if (WAVES == 4 && !persistent4) grid = items;
+    // it sets the span)
+    if (WAVES == 4) grid = items;
     hipLaunchKernelGGL((attn2_kernel<T, NT, PACKED, WAVES, STAGES>), dim3((unsigned)grid), dim3(WAVES * 64), lds, stream, p, items);
 }
 
@@ -910,15 +909,6 @@ void launch_attn_layout(const AttnParams& p, hipStream_t stream) {
 #endif
     const int qblocks = (p.T + WAVES * 32 - 1) / (WAVES * 32);
     dim3 grid((unsigned)(8 * ((p.N * p.H + 7) / 8) * qblocks));
-    static const bool narrow = dev_switch("AMX_ATTN_NARROW_STORES");  // developer A/B switch: 8-byte stores straight from the registers
-    if (narrow) {
-        static OncePerDevice attr_n;
-        if (attr_n.first())
-            (void)hipFuncSetAttribute((const void*)attn_kernel<T, NT, WAVES, KT, PACKED, KS, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      lds);
-        hipLaunchKernelGGL((attn_kernel<T, NT, WAVES, KT, PACKED, KS, false>), grid, dim3(WAVES * KS * 64), lds, stream, p);
-        return;
-    }
     static OncePerDevice attr;
     if (attr.first())
         (void)hipFuncSetAttribute((const void*)attn_kernel<T, NT, WAVES, KT, PACKED, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -949,9 +939,8 @@ void launch_attn_other_dh(const AttnParams& p, hipStream_t stream) {
 // 128-wide rows: the instance whose score chain / output blocks stop at the real columns (80: XLS-R 1B; 96; otherwise all 128)
 template <typename T, int NT, bool PACKED>
 void launch_attn_wide(const AttnParams& p, hipStream_t stream) {
-    static const bool whole = dev_switch("AMX_ATTN_WHOLE_ROW");  // developer A/B switch: every padded column, as until round 6
-    if (!whole && p.dh <= 80) launch_attn_other_dh<T, NT, PACKED, 2, 5>(p, stream);
-    else if (!whole && p.dh <= 96) launch_attn_other_dh<T, NT, PACKED, 2, 6>(p, stream);
+    if (p.dh <= 80) launch_attn_other_dh<T, NT, PACKED, 2, 5>(p, stream);
+    else if (p.dh <= 96) launch_attn_other_dh<T, NT, PACKED, 2, 6>(p, stream);
     else launch_attn_other_dh<T, NT, PACKED, 2>(p, stream);
 }
 
@@ -977,27 +966,20 @@ void launch_attn_any(const AttnParams& p, hipStream_t stream) {
         cus = hipGetDeviceProperties(&prop, current_device()) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     const int64_t wg8 = (int64_t)p.N * p.H * ((p.T + 255) / 256);
-    static const int force = dev_int("AMX_ATTN_WAVES", 0);  // developer A/B switch
-    {
-        // 64 queries per wave (attn2_kernel, 256-query workgroups) for long key loops on a full chip (AMX_ATTN_V2 = 0 / 1 forces
-        // the choice: developer A/B switch)
-        static const int v2 = dev_int("AMX_ATTN_V2", -1);
-        // (crossover measured at 12-15 key tiles per item with the chip full: T = 749 123 -> 147 us, T = 999 235 -> 221,
-        // T = 1499 246 -> 234, T = 1999 640 -> 558, T = 2999 849 -> 752; one utterance alone keeps the 32-query waves)
-        const bool fits = wg8 * 2 >= 3 * (int64_t)cus && p.T >= 960;
-        if (v2 == 1 || (v2 < 0 && fits && !force)) {
-            launch_attn2<T, NT, 4, 2>(p, cus, stream);
-            return;
-        }
+    // 64 queries per wave (attn2_kernel, 256-query workgroups) for long key loops on a full chip
+    // (crossover measured at 12-15 key tiles per item with the chip full: T = 749 123 -> 147 us, T = 999 235 -> 221,
+    // T = 1499 246 -> 234, T = 1999 640 -> 558, T = 2999 849 -> 752; one utterance alone keeps the 32-query waves)
+    if (wg8 * 2 >= 3 * (int64_t)cus && p.T >= 960) {
+        launch_attn2<T, NT, 4, 2>(p, cus, stream);
+        return;
     }
-    const bool small = force ? force == 4 : wg8 * 2 <= cus;
+    const bool small = wg8 * 2 <= cus;
     // ... and when even the 128-query workgroups are at most one per CU, the key tiles of a query block are split over two wave
-    // groups (KS = 2): two waves per SIMD instead of one, half the serial key loop (AMX_ATTN_KSPLIT=0: developer A/B switch)
-    static const bool no_ksplit = dev_int("AMX_ATTN_KSPLIT", 1) == 0;
+    // groups (KS = 2): two waves per SIMD instead of one, half the serial key loop
     const int64_t wg4 = (int64_t)p.N * p.H * ((p.T + 127) / 128);
     // (tools/attn_bench.hip, per launch: 4 x 10 s 23.0 -> 21.2 us, 1 x 10 s 19.2 -> 17.4, 2 x 20 s 38.7 -> 34.4; 1 x 3 s -- three key
     // tiles -- 10.3 -> 10.9: from six tiles on)
-    if (small && !no_ksplit && !force && wg4 <= cus && p.T >= 384) launch_attn<T, NT, 4, 64, 2>(p, stream);
+    if (small && wg4 <= cus && p.T >= 384) launch_attn<T, NT, 4, 64, 2>(p, stream);
     else if (small) launch_attn<T, NT, 4, 64>(p, stream);
     else launch_attn<T, NT, 8, 64>(p, stream);
 }

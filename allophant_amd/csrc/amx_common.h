@@ -3,23 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
-#ifdef AMX_DEVELOPER
-#include <cstdlib>
-#endif
 
 namespace amx {
-
-// Developer A/B switches.  The PRODUCT library reads no environment variable on the compute path (the one variable of the
-// library is AMX_RCCL_LIBRARY in amx_dist.hip, which names a file, not a behaviour): these helpers are constants there and
-// the switch names do not even reach the binary.  `make DEVELOPER=1` (-DAMX_DEVELOPER; tools/ab_build.sh, the A/B scripts under
-// tools/) builds the library in which they read the environment.
-#ifdef AMX_DEVELOPER
-inline bool dev_switch(const char* name) { const char* v = getenv(name); return v && atoi(v) != 0; }
-inline int dev_int(const char* name, int otherwise) { const char* v = getenv(name); return v ? atoi(v) : otherwise; }
-#else
-constexpr bool dev_switch(const char*) { return false; }
-constexpr int dev_int(const char*, int otherwise) { return otherwise; }
-#endif
 
 typedef _Float16 f16;
 typedef __bf16 bf16;

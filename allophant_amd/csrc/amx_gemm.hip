@@ -34,8 +34,6 @@ int device_cus() {
     if (!cus) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        // developer switch: size the persistent grids for a CU-masked stream (tools/two_stream_probe.py)
-        if (dev_int("AMX_FORCE_CUS", 0) > 0) cus = dev_int("AMX_FORCE_CUS", 0);
         if (cus <= 0) cus = 256;
         cus -= cus % 8;  // the tile order assumes sequence numbers i and i + grid share an XCD
         if (cus < 8) cus = 8;
@@ -65,9 +63,8 @@ bool ln_eligible(int NT, const GemmParams& p) {
 
 // the whole-line kernel (gemm_ln_il_kernel) takes the product: the one that understands the tap-minor K order
 bool ln_uses_il(int NT, const GemmParams& p) {
-    static const bool plain_loop = dev_switch("AMX_LN_SEGMENT_LOOP");  // developer A/B
     const bool layout_ok = NT == 1 || (p.a_plane == PLANE_IL && p.w_plane == PLANE_IL && p.out_plane == PLANE_IL);
-    return !plain_loop && layout_ok && p.K % (128 / NT) == 0;
+    return layout_ok && p.K % (128 / NT) == 0;
 }
 
 template <typename T, int NT>
@@ -182,12 +179,7 @@ void launch_pp_fold(const GemmParams& p, hipStream_t stream) {
 }
 
 template <typename T, int NT, int MI, int NI = 4>
-void launch_pp_tiles(const GemmParams& p_in, int splits, hipStream_t stream) {
-    // developer timing switches (WRONG results: the fold's products run as plain products, to price its epilogues one side at a time)
-    static const bool producer_plain = dev_switch("AMX_FOLD_PRODUCER_PLAIN"), consumer_plain = dev_switch("AMX_FOLD_CONSUMER_PLAIN");
-    GemmParams p = p_in;
-    if (producer_plain && p.ln_partial) { p.ln_partial = nullptr; p.ln_rowps = nullptr; p.out_p = nullptr; p.ln_res_planes = 0; }
-    if (consumer_plain && p.row_coef) { p.row_coef = nullptr; p.col_c = nullptr; }
+void launch_pp_tiles(const GemmParams& p, int splits, hipStream_t stream) {
     if (p.ln_partial) {
         if constexpr (NI == 4) launch_pp_fold<T, NT, MI, 4, 2>(p, stream);
         return;
@@ -222,15 +214,12 @@ void launch_pp_tiles(const GemmParams& p_in, int splits, hipStream_t stream) {
 void pp_plan(int NT, const GemmParams& p, int* mi_out, int* splits_out, int* ni_out) {
     const int cus = device_cus();
     const double loop = (double)p.K * (NT > 1 ? 3 : 1);  // main loop of a 256 x 256 tile
-    static const bool no_narrow = dev_switch("AMX_NO_NARROW_TILES");  // developer A/B switch: 256-column tiles only
-    static const int force_ni = dev_int("AMX_PP_FORCE_NI", 0), force_mi = dev_int("AMX_PP_FORCE_MI", 0);  // developer: one tile shape
     double best = 1e30;
     *mi_out = 8;
     *splits_out = 1;
     *ni_out = 4;
     for (int mi = 8; mi >= 4; mi -= 4)
-        for (int ni = 4; ni >= (no_narrow ? 4 : 3); --ni) {
-            if ((force_ni && ni != force_ni) || (force_mi && mi != force_mi)) continue;
+        for (int ni = 4; ni >= 3; --ni) {
             const int tiles = ((p.N + ni * 64 - 1) / (ni * 64)) * ((p.M + mi * 32 - 1) / (mi * 32));
             const double per_unit = (480.0 + 60.0 * mi) * (ni == 4 ? 1.0 : 1.1);  // prologue + epilogue of a work unit
             const double unit_loop = loop * mi / 8.0 * (ni == 4 ? 1.0 : 0.75 * 1.06);
@@ -270,8 +259,7 @@ bool launch_gemm_pp(const GemmParams& p, hipStream_t stream) {
 }
 
 bool dma_tile_eligible(int NT, const GemmParams& p) {
-    static const bool off = dev_switch("AMX_NO_DMA_TILE");  // developer A/B switch
-    if (off || p.K % BK != 0) return false;
+    if (p.K % BK != 0) return false;
     if (p.lda % 8 || p.ldw % 8 || p.a_plane % 8 || p.w_plane % 8 || p.a_batch_stride % 8 || p.za % 8 || p.zw % 8) return false;
     if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15)) return false;
     // rows of a tile ascend in memory and stay inside 32-bit byte offsets from the tile's first row
@@ -324,16 +312,16 @@ void launch_gemm_dma_shape(int shape, const GemmParams& q, int zdim, hipStream_t
 // A product that fits one round of LDS-DMA tiles runs there instead of on the ping-pong kernel when it is short (below
 // ~768 rows: tools/geometry_sweep.py, 1 x 10 s 5.5 -> 4.0 ms) or when its 128 x 256 ping-pong tiles would occupy less than
 // half of the CUs (N = 1024 products of a few thousand rows: 64 tiles on 256 CUs) while 128 x 64 tiles fill them.
-// AMX_DMA_MAX_ROWS (developer switch) overrides the row threshold of the second rule.
+constexpr int DMA_MAX_ROWS = 4096;  // row limit of the second rule
+
 int dma_preferred_shape(int NT, const GemmParams& p) {
-    static const int max_rows = dev_int("AMX_DMA_MAX_ROWS", 4096);
     const int shape = dma_tile_shape(NT, p, 1);
     if (!shape) return 0;
     if (p.M < 768) return shape;
     const int pp_tiles = ((p.N + pp::BN - 1) / pp::BN) * ((p.M + 127) / 128);
     // (K = 4096 products stay on the ping-pong kernel: its K chunks beat a 128-sub-step loop per tile -- tools/gemm_bench
     // small, M = 1996: out-proj 40.6 -> 29.5 us on DMA tiles, FFN2 66.1 -> 74.8 us)
-    if (p.M < max_rows && p.K <= 2048 && pp_tiles * 2 <= device_cus()) return shape;
+    if (p.M < DMA_MAX_ROWS && p.K <= 2048 && pp_tiles * 2 <= device_cus()) return shape;
     return 0;
 }
 
@@ -430,10 +418,9 @@ static GemmParams with_vec_flag(const GemmParams& in) {
 bool gemm_fuses_ln(int prec, const GemmParams& p_in) { return ln_eligible(prec_planes(prec), with_vec_flag(p_in)); }
 
 int gemm_ln_tap_minor_slice(int prec, const GemmParams& p_in) {
-    static const bool tap_major = dev_switch("AMX_LN_TAP_MAJOR");  // developer A/B switch
     const int NT = prec_planes(prec);
     const GemmParams p = with_vec_flag(p_in);
-    if (tap_major || !ln_eligible(NT, p) || !ln_uses_il(NT, p)) return 0;
+    if (!ln_eligible(NT, p) || !ln_uses_il(NT, p)) return 0;
     return NT == 2 ? 32 : 64;
 }
 

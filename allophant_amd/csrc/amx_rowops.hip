@@ -1565,8 +1565,7 @@ static void conv0_launch_cpl(const float* audio, const int64_t* lengths, const f
 }
 
 bool conv0_mfma_eligible(int C, int k, int stride) {
-    static const bool off = dev_switch("AMX_NO_CONV0_MFMA");  // developer A/B switch: the VALU kernel
-    return !off && C == C0M_C && k == C0M_K && stride >= 1 && conv0_mfma_lds_bytes(2, stride) <= 64 * 1024;
+    return C == C0M_C && k == C0M_K && stride >= 1 && conv0_mfma_lds_bytes(2, stride) <= 64 * 1024;
 }
 
 template <typename T, int NT, bool GN = false>
@@ -1629,8 +1628,7 @@ void launch_conv0_groupnorm(int prec, const float* audio, const int64_t* lengths
     }
     const int blocks = (T1 + GN_FRAMES - 1) / GN_FRAMES;
     const size_t lds = (size_t)((GN_FRAMES - 1) * stride + k) * sizeof(float);
-    static const bool plain_stats = dev_switch("AMX_GN_PLAIN_STATS");  // developer A/B switch
-    if (k == 10 && C == 512 && !plain_stats) {
+    if (k == 10 && C == 512) {
         // register-blocked form (wav2vec 2.0 shape); its LDS also holds the 4 x 512 x 2 fp64 partials of the block
         const size_t lds8 = lds > (size_t)4 * 512 * 2 * sizeof(double) ? lds : (size_t)4 * 512 * 2 * sizeof(double);
         hipLaunchKernelGGL(conv0_gn_stats8_kernel<10>, dim3(blocks, N), dim3(256), lds8, s, audio, lengths, mean_rstd, L, T1, C, stride, w, b,
@@ -1816,20 +1814,8 @@ __global__ __launch_bounds__(256) void zero_fill_2d_kernel(unsigned char* __rest
 }
 }  // namespace
 
-// Developer switches that put the round-5 replay fault back (tools/r06_graph_fault.sh: which of the two changes removed it?):
-// AMX_GRAPH_MEMSET_NODES=1 -- zero fills and device copies of a pass as hipMemsetAsync / hipMemcpyAsync again, i.e. memset / memcpy
-// NODES in a recording.  (Constants in the product build: amx_common.h dev_switch.)
-static bool graph_memset_nodes() {
-    static const bool on = dev_switch("AMX_GRAPH_MEMSET_NODES");
-    return on;
-}
-
 void launch_zero(void* p, size_t bytes, hipStream_t s) {
     if (bytes == 0) return;
-    if (graph_memset_nodes()) {
-        (void)hipMemsetAsync(p, 0, bytes, s);
-        return;
-    }
     const size_t words = bytes / 4;
     size_t blocks = (words / 4 + 255) / 256 + 1;
     if (blocks > 4096) blocks = 4096;
@@ -1839,10 +1825,6 @@ void launch_zero(void* p, size_t bytes, hipStream_t s) {
 // device-to-device copy of a pass as a kernel, for the same reason (bytes a multiple of 4)
 void launch_copy(void* dst, const void* src, size_t bytes, hipStream_t s) {
     if (bytes == 0) return;
-    if (graph_memset_nodes()) {
-        (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s);
-        return;
-    }
     const size_t words = bytes / 4;
     size_t blocks = (words / 4 + 255) / 256 + 1;
     if (blocks > 8192) blocks = 8192;
@@ -1851,10 +1833,6 @@ void launch_copy(void* dst, const void* src, size_t bytes, hipStream_t s) {
 
 void launch_zero_2d(void* base, size_t pitch, size_t width_bytes, size_t rows, hipStream_t s) {
     if (width_bytes == 0 || rows == 0) return;
-    if (graph_memset_nodes()) {
-        (void)hipMemset2DAsync(base, pitch, 0, width_bytes, rows, s);
-        return;
-    }
     const size_t words = width_bytes / 4;
     size_t bx = (words + 255) / 256;
     if (bx > 64) bx = 64;

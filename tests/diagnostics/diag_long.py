@@ -1,5 +1,5 @@
-"""Developer diagnostic: one long utterance alone / inside a padded slice of a larger batch, under both GEMM routings, each
-against the CPU oracle (per-output max-abs error on valid frames).  Lives under tests/ because it runs the CPU oracle (test infrastructure)."""
+"""Developer diagnostic: one long utterance alone / inside a padded slice of a larger batch, each against the CPU oracle
+(per-output max-abs error on valid frames).  Lives under tests/ because it runs the CPU oracle (test infrastructure)."""
 import os
 import subprocess
 import sys
@@ -28,16 +28,14 @@ if mode == "oracle":
     sys.exit(0)
 if mode == "driver":
     subprocess.check_call([sys.executable, __file__, "oracle"])
-    for env in ({}, {"AMX_DMA_MAX_ROWS": "768"}):
-        e = dict(os.environ, **env)
-        subprocess.check_call([sys.executable, __file__, "gpu"], env=e)
+    subprocess.check_call([sys.executable, __file__, "gpu"])
     sys.exit(0)
 ref = torch.load("/tmp/diag_ref.pt")
 est = Estimator(spec, state, "cuda:0", "f16x3")
 solo = est.predict(Batch(audio[i:i + 1, :n_i].contiguous().cuda(), lengths[i:i + 1], torch.zeros(1, dtype=torch.long)), tfi)
 t_i = int(solo.lengths[0])
 full = est.predict(Batch(audio.cuda(), lengths, torch.zeros(n_batch, dtype=torch.long)), tfi)
-print("routing", os.environ.get("AMX_DMA_MAX_ROWS", "default"), "frames", t_i)
+print("frames", t_i)
 for name, pred, col in (("solo", solo, 0), ("batch", full, i)):
     errs = {k: (pred.outputs[k][:t_i, col].cpu() - ref[k][:t_i]).abs().max().item() for k in ref}
     worst = sorted(errs.items(), key=lambda kv: -kv[1])[:4]

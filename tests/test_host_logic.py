@@ -334,3 +334,24 @@ def test_bench_work_model_matches_the_survey_accounting():
         assert (big["gemm_pp_launches"], big["gemm_ln_launches"]) == (4 * 48 + 2, 5)
         assert abs(big["total"] / 1e12 - total) < 0.01 and abs(big["attention"] / 1e12 - attention) < 0.001, (name, big["total"], big["attention"])
         assert big["gemm_ln"] == w["gemm_ln"] and big["conv0"] == w["conv0"]
+
+
+def test_library_reads_no_environment_and_has_no_developer_switches():
+    """The compute path has one build: no file of the library but the RCCL loader calls getenv, and neither the developer-switch
+    build macro nor the switch helper is left in the library or the tools.  A/B runs compare two revisions (tools/ab_build.sh)."""
+    # (the names are assembled so that a plain grep for them over the repository finds nothing, this file included)
+    switch_names = re.compile("AMX_" + "DEVELOPER|dev_" + "switch")
+
+    def files(top):
+        for dirpath, _, names in os.walk(os.path.join(ROOT, top)):
+            for name in sorted(names):
+                path = os.path.join(dirpath, name)
+                with open(path, errors="ignore") as f:
+                    yield os.path.relpath(path, ROOT), f.read()
+
+    csrc = dict(files(os.path.join("allophant_amd", "csrc")))
+    assert "allophant_amd/csrc/amx_dist.hip" in csrc
+    readers = sorted(p for p, text in csrc.items() if re.search(r"\bgetenv\s*\(", text))
+    assert readers == ["allophant_amd/csrc/amx_dist.hip"], readers
+    switches = sorted(p for p, text in list(csrc.items()) + list(files("tools")) if switch_names.search(text))
+    assert not switches, switches

@@ -1,8 +1,9 @@
 """Developer check: SHA-256 of the flat output of predict() per batch geometry, for comparing two builds of the library bit for bit
 (a change that claims "same values" -- a store pattern, a cheaper instruction sequence for the same arithmetic):
 
+    tools/ab_build.sh HEAD head
     AMX_LIB_PATH=$PWD/build/ab/head.so python tools/ab_bitwise.py f16x3 32:10 8:60 > a.txt
-    AMX_LIB_PATH=$PWD/build/liballophant_amx_dev.so python tools/ab_bitwise.py f16x3 32:10 8:60 > b.txt; diff a.txt b.txt
+    python tools/ab_bitwise.py f16x3 32:10 8:60 > b.txt; diff a.txt b.txt    # the working tree's library
 
 Ragged variants (packed rows, the masked last key tile) are hashed as well.  AB_ENCODER selects the encoder (bench.py --encoder)."""
 import hashlib

@@ -1,8 +1,8 @@
 // Developer micro-benchmark + self-check of the GEMM kernels of liballophant_amx (includes the translation unit directly so
-// that ablation macros apply).  Build (-DAMX_DEVELOPER: the AMX_* A/B switches read the environment, e.g. AMX_PP_FORCE_NI=3):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DAMX_DEVELOPER -Iallophant_amd/csrc -Iinclude -o build/gemm_bench tools/gemm_bench.hip
+// that ablation macros apply).  Build:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iallophant_amd/csrc -Iinclude -o build/gemm_bench tools/gemm_bench.hip
 //   hipcc ... -DAMX_ABLATE_NO_EPI -o build/gemm_bench_noepi tools/gemm_bench.hip
-// Run:  build/gemm_bench check   (ping-pong kernel vs generic tile kernel on edge-case shapes)
+// Run:  build/gemm_bench check   (ping-pong kernel, on both tile widths, vs generic tile kernel on edge-case shapes)
 //       build/gemm_bench time    (model shapes of BASELINE config 2, both kernels, f16x3 and bf16)
 #include "../allophant_amd/csrc/amx_gemm.hip"
 #include <cmath>
@@ -96,7 +96,28 @@ static bool g_compare_nosplit = false;
 static float* g_splitk_ws = nullptr;
 static const int64_t SPLITK_ELEMS = (int64_t)18 << 20;
 
-static double run_case(int prec, const Case& c, bool timing_only, double* us_pp, double* us_gen) {
+// a ping-pong product on the given tile width (NI = 4: 256 columns, 3: 192 columns) with the plan's tile height and K chunks
+template <typename T, int NT>
+static void launch_pp_width_t(const GemmParams& p, int ni, hipStream_t s) {
+    int mi, splits, plan_ni;
+    pp_plan(NT, p, &mi, &splits, &plan_ni);
+    if (mi == 8 && ni == 4) launch_pp_tiles<T, NT, 8, 4>(p, splits, s);
+    else if (mi == 8) launch_pp_tiles<T, NT, 8, 3>(p, splits, s);
+    else if (ni == 4) launch_pp_tiles<T, NT, 4, 4>(p, splits, s);
+    else launch_pp_tiles<T, NT, 4, 3>(p, splits, s);
+}
+static void launch_pp_width(int prec, const GemmParams& g, int ni, hipStream_t s) {
+    const GemmParams p = with_vec_flag(g);
+    switch (prec) {
+        case PREC_BF16: launch_pp_width_t<bf16, 1>(p, ni, s); break;
+        case PREC_F16: launch_pp_width_t<f16, 1>(p, ni, s); break;
+        case PREC_BF16X3: launch_pp_width_t<bf16, 2>(p, ni, s); break;
+        default: launch_pp_width_t<f16, 2>(p, ni, s); break;
+    }
+}
+
+// ni: 0 = launch_gemm's own choice; 4 / 3 = a product that takes the ping-pong kernel runs on that tile width (*pp_out: it did)
+static double run_case(int prec, const Case& c, bool timing_only, double* us_pp, double* us_gen, int ni = 0, bool* pp_out = nullptr) {
     if (!g_splitk_ws) CK(hipMalloc(&g_splitk_ws, SPLITK_ELEMS * 4));
     const int NT = prec_planes(prec);
     const int64_t rows_per_batch = c.conv_rows_per_batch ? c.conv_rows_per_batch : c.M;
@@ -138,18 +159,24 @@ static double run_case(int prec, const Case& c, bool timing_only, double* us_pp,
         if (c.f32_out) { g.out_f32 = outf; g.ldo = c.N; }
         if (c.planes_out) { g.out_p = outp; g.out_plane = plane_of(prec, o_el); g.ldp = c.N; }
         if (c.qkv) {
-            g.mode = 1; g.q = q; g.k = k; g.v = vt; g.qk_plane = qk_el; g.T = T; g.Tp = Tp; g.H = H; g.dh = dh;
+            g.mode = 1; g.q = q; g.k = k; g.v = vt; g.qk_plane = qk_el; g.T = T; g.Tp = Tp; g.H = H; g.dh = dh; g.dhp = dh;
             if (c.mask) g.row_len = row_len;  // (the model's QKV product carries no row mask: the branch-free scatter epilogue)
         }
         g_force_generic_gemm = variant == 1 && !g_compare_nosplit;
         if (variant == 0) { g.splitk_ws = g_splitk_ws; g.splitk_ws_elems = SPLITK_ELEMS; }
-        launch_gemm(prec, g, 0);
+        const bool width = variant == 0 && ni && gemm_uses_pp(prec, g);
+        if (variant == 0 && pp_out) *pp_out = width;
+        auto launch = [&]() {
+            if (width) launch_pp_width(prec, g, ni, 0);
+            else launch_gemm(prec, g, 0);
+        };
+        launch();
         CK(hipDeviceSynchronize());
         hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         const int iters = timing_only ? 20 : 2;
-        for (int i = 0; i < 2; ++i) launch_gemm(prec, g, 0);
+        for (int i = 0; i < 2; ++i) launch();
         CK(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; ++i) launch_gemm(prec, g, 0);
+        for (int i = 0; i < iters; ++i) launch();
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         (variant == 0 ? *us_pp : *us_gen) = ms * 1e3 / iters;
@@ -358,7 +385,7 @@ int main(int argc, char** argv) {
             {"split generic gelu->planes", 149, 4096, 1024, 1, 0, 0, 1, 0, 0, 0, 0, 1.0f},
             {"split generic conv-like", 598, 512, 1536, 0, 0, 0, 0, 1, 0, 299, 1024, 1.0f},
             {"split generic qkv scatter", 499, 3072, 1024, 0, 0, 0, 0, 0, 1, 0, 0, 1.0f},
-            // shapes the plan gives 192-column tiles (NI = 3), and -- under AMX_PP_FORCE_NI=3 -- their N tails
+            // shapes the plan gives 192-column tiles (NI = 3), and N tails of both tile widths
             {"192-wide qkv scatter 8 x 10 s", 3992, 3072, 1024, 0, 0, 0, 0, 0, 1, 0, 0, 1.0f},
             {"192-wide qkv scatter 16 x 10 s", 7984, 3072, 512, 0, 0, 0, 0, 0, 1, 0, 0, 1.0f},
             {"N tail f32 +res +mask", 2100, 640, 384, 0, 1, 1, 0, 1, 0, 0, 0, 0.5f},
@@ -368,15 +395,19 @@ int main(int argc, char** argv) {
         int precs[] = {PREC_F16X3, PREC_BF16X3, PREC_F16, PREC_BF16};
         int bad = 0;
         for (int prec : precs)
-            for (auto& c : cases) {
-                double a, b;
-                double e = run_case(prec, c, false, &a, &b);
-                // x3: both kernels are ~fp32-exact; 1 plane: identical products, different summation order + fast GELU,
-                // results quantised to 16 bit on plane outputs
-                double tol = prec_planes(prec) > 1 ? 2e-4 : ((c.planes_out || c.qkv) ? (prec == PREC_BF16 ? 8e-3 : 1e-3) : 2e-4);
-                printf("CHECK prec=%d %-36s max rel err %.3e  %s\n", prec, c.name, e, e <= tol ? "ok" : "FAIL");
-                if (!(e <= tol)) ++bad;
-            }
+            for (auto& c : cases)
+                for (int ni : {4, 3}) {  // a ping-pong product on 256- and on 192-column tiles
+                    double a, b;
+                    bool pp = false;
+                    double e = run_case(prec, c, false, &a, &b, ni, &pp);
+                    // x3: both kernels are ~fp32-exact; 1 plane: identical products, different summation order + fast GELU,
+                    // results quantised to 16 bit on plane outputs
+                    double tol = prec_planes(prec) > 1 ? 2e-4 : ((c.planes_out || c.qkv) ? (prec == PREC_BF16 ? 8e-3 : 1e-3) : 2e-4);
+                    printf("CHECK prec=%d %-36s %-8s max rel err %.3e  %s\n", prec, c.name, pp ? (ni == 4 ? "pp 256" : "pp 192") : "",
+                           e, e <= tol ? "ok" : "FAIL");
+                    if (!(e <= tol)) ++bad;
+                    if (!pp) break;  // not a ping-pong product: one run covers it
+                }
         printf("gemm check: %s\n", bad ? "FAILED" : "all ok");
         if (bad) return 1;
     }

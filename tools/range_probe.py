@@ -1,7 +1,7 @@
-"""Developer probe: max-abs log-prob error against the CPU oracle for the weight families of tests/test_gpu_range.py, with
-and without the per-tensor power-of-two pack scales (AMX_NO_PACK_SCALE=1), per precision mode.
+"""Developer probe: max-abs log-prob error against the CPU oracle for the weight families of tests/test_gpu_range.py, per
+precision mode.
 
-    python tools/range_probe.py            # run twice: plain and with AMX_NO_PACK_SCALE=1
+    python tools/range_probe.py
 """
 import os
 import sys
@@ -21,7 +21,6 @@ spec["shared_phones"] = 80
 tfi = synthetic.make_inventory(spec, 27, seed=3)
 audio, lengths = synthetic.make_audio(2, 48000, seed=777, ragged=True)
 batch = Batch(audio.cuda(), lengths, torch.zeros(2, dtype=torch.long))
-tag = "unscaled planes" if os.environ.get("AMX_NO_PACK_SCALE") == "1" else "pack scales"
 for kind in ["plain", "scales", "student_t", "ln_gain", "outlier", "tiny_weights"]:
     if kind == "plain":
         state = synthetic.make_state_dict(spec, seed=0)
@@ -41,4 +40,4 @@ for kind in ["plain", "scales", "student_t", "ln_gain", "outlier", "tiny_weights
         pred = est.predict(batch, tfi)
         row.append(f"{precision} {R._worst(pred, ref, ref_len):.2e}")
         est.close()
-    print(f"RANGE [{tag}] {kind:13s} " + "   ".join(row), flush=True)
+    print(f"RANGE {kind:13s} " + "   ".join(row), flush=True)
