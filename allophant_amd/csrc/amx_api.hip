@@ -1748,8 +1748,11 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
         WS("ln_coef", (size_t)Mrows * 8, P.ln_coef);
         WS("ln_partial", (size_t)Mrows * (D / 64) * 8, P.ln_partial);
         const Layer& ly = h->layers[0];
-        P.fold = gemm_ln_fold_ok(prec, P.as_consumer(P.qkv_params(ly), ly.c_qkv)) && gemm_ln_fold_ok(prec, P.as_producer(P.oproj_params(ly))) &&
-                 gemm_ln_fold_ok(prec, P.as_consumer(P.ffn1_params(ly), ly.c_1)) && gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(ly)));
+        // (the producers as enqueue_pass launches them: the out-projection without fp32 rows, FFN2 with and without)
+        P.fold = gemm_ln_fold_ok(prec, P.as_consumer(P.qkv_params(ly), ly.c_qkv)) &&
+                 gemm_ln_fold_ok(prec, P.as_producer(P.oproj_params(ly), false)) &&
+                 gemm_ln_fold_ok(prec, P.as_consumer(P.ffn1_params(ly), ly.c_1)) &&
+                 gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(ly), false)) && gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(ly), true));
     }
     ++h->pass_counter;
     h->last_fold = P.fold;
@@ -2004,6 +2007,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
     // A residual product that launch_gemm cuts into K chunks (short batches) leaves its fix-up -- slab sum + bias + residual
     // -> h -- to the LayerNorm that follows it: one kernel instead of the fix-up and a LayerNorm pass that re-reads h.
     struct { bool on = false; GemmParams g; int splits = 0; } pending;
+    bool refused = false;  // a fold product launch_gemm had no kernel for (never expected: P.fold checked these very params)
     auto residual_gemm = [&](GemmParams g, bool may_defer) {
         const int splits = may_defer ? gemm_planned_splits(prec, g) : 1;
         if (splits > 1 && fixup_rownorm_eligible(g)) {
@@ -2012,7 +2016,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
             pending.g = g;
             pending.splits = splits;
         }
-        { Timed t_(h, gemm_class(prec, g)); launch_gemm(prec, g, s); }
+        { Timed t_(h, gemm_class(prec, g)); refused |= !launch_gemm(prec, g, s); }
     };
     // LayerNorm of the residual stream (rows of hbuf) -> planes (and the fp32 rows, for the final one)
     auto stream_norm = [&](const float* gamma, const float* beta, int64_t rows, int64_t plane, float* out_ln) {
@@ -2031,9 +2035,12 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
     if (!stable) stream_norm(h->fln_g, h->fln_b, Mrows, xp_plane, ln_inplace);
     // (pre-LN layers: gamma / beta of both norms live in the QKV / FFN1 weights -- fold_layer_norm at amx_create -- so a row pass
     // normalises with (1, 0))
+    // the fold's padded frames (padded layout of a ragged batch, keys the attention masks) are written under a smaller scale: see
+    // ln_plane_scale.  Without the attention mask every frame is a key, and none is padding.
+    const int* const fold_frames = packed || !masked ? nullptr : (const int*)d_frames_enc;
     auto ln_finalize = [&]() {
         Timed t_(h, AMX_KC_ROWNORM);
-        launch_ln_finalize((const float2*)ln_partial, D / 64, Mrows, c.eps, (float4*)ln_rowps, (float2*)ln_coef, s);
+        launch_ln_finalize((const float2*)ln_partial, D / 64, Mrows, c.eps, (float4*)ln_rowps, (float2*)ln_coef, fold_frames, T, s);
     };
     for (int l = 0; l < c.layers; ++l) {
         const Layer& ly = h->layers[l];
@@ -2041,7 +2048,8 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
             // the first norm of the stack from the stream itself; later ones: the previous FFN2 left planes and statistics
             if (l == 0) {
                 Timed t_(h, AMX_KC_ROWNORM);
-                launch_ln_rowprep(prec, (const float*)hbuf, D, Mrows, D, c.eps, xp, xp_plane, D, (float4*)ln_rowps, (float2*)ln_coef, s);
+                launch_ln_rowprep(prec, (const float*)hbuf, D, Mrows, D, c.eps, xp, xp_plane, D, (float4*)ln_rowps, (float2*)ln_coef,
+                                  fold_frames, T, s);
             }
         } else if (stable) {
             stream_norm(h->unit_g, h->zero_b, Mrows, xp_plane, nullptr);  // (completes the previous layer's FFN2 when that was deferred)
@@ -2060,7 +2068,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         {
             GemmParams g = P.qkv_params(ly);
             if (fold) g = P.as_consumer(g, ly.c_qkv);
-            { Timed t_(h, gemm_class(prec, g)); launch_gemm(prec, g, s); }
+            { Timed t_(h, gemm_class(prec, g)); refused |= !launch_gemm(prec, g, s); }
         }
         {
             AttnParams a{};
@@ -2085,7 +2093,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         {
             GemmParams g = P.ffn1_params(ly);
             if (fold) g = P.as_consumer(g, ly.c_1);
-            { Timed t_(h, gemm_class(prec, g)); launch_gemm(prec, g, s); }
+            { Timed t_(h, gemm_class(prec, g)); refused |= !launch_gemm(prec, g, s); }
         }
         if (fold && (l + 1 < c.layers || stream_in_planes)) {
             // fp32 rows where the next reader needs them: hidden state l + 1 is published, or this is the last layer (final LayerNorm,
@@ -2099,6 +2107,7 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         }
         if (!stable) stream_norm(ly.ln2_g, ly.ln2_b, Mrows, xp_plane, ln_inplace);  // `final_layer_norm` closes the post-LN layer
     }
+    if (refused) return fail(h, AMX_EINVAL, "internal: an encoder product of the LayerNorm fold had no kernel for its plan and was not launched");
     if (packed && !packed_early) {
         // back to the padded layout for the final LayerNorm and the projection (padded frames keep their pre-encoder rows)
         { Timed t_(h, AMX_KC_OTHER); launch_pack_rows((const float*)hpad, (float*)hpk, (const int*)d_rowoff, (const int*)d_frames, N, T, D, true, s); }

@@ -317,7 +317,9 @@ struct GemmParams {
 };
 
 extern bool g_force_generic_gemm;
-void launch_gemm(int prec, const GemmParams& p, hipStream_t stream);
+// false: nothing was launched -- a LayerNorm-fold product (ln_partial / row_coef) on a plan without its epilogue; every
+// plan gemm_ln_fold_ok admits launches
+bool launch_gemm(int prec, const GemmParams& p, hipStream_t stream);
 // true when launch_gemm routes this product to the 256x256 ping-pong kernel (else: generic tile kernel)
 bool gemm_uses_pp(int prec, const GemmParams& p);
 // true when a product with ln_gamma / ln_beta set can run on the row-complete kernel with fused LayerNorm + GELU
@@ -402,13 +404,16 @@ void launch_rownorm(int prec, const float* x, int64_t ldx, int64_t M, int D, con
                     int64_t out_plane, int64_t ldp, float* out_f32, int64_t ldo, hipStream_t s);
 // LayerNorm fold (GemmParams.ln_partial / row_coef): the FIRST norm of the encoder stack, from the fp32 stream itself: exact row
 // statistics (two passes over the row in registers, like launch_rownorm) -> planes of u = (x - mu) * s with s the power of two
-// that puts 16 / sigma ... 8 / sigma into it, rowps[m] = (mu, s, mu, s), coef[m] = (rstd / s, 0)
+// that puts 2 / sigma ... 1 / sigma into it, rowps[m] = (mu, s, mu, s), coef[m] = (rstd / s, 0).  frame_len (may be null: no
+// padded rows): rows n * T_rows + t with t >= frame_len[n] are padded frames, written under 2^-6 of that scale (ln_plane_scale)
 void launch_ln_rowprep(int prec, const float* x, int64_t ldx, int64_t M, int D, float eps, void* out_p, int64_t out_plane, int64_t ldp,
-                       float4* rowps, float2* coef, hipStream_t s);
+                       float4* rowps, float2* coef, const int* frame_len, int T_rows, hipStream_t s);
 // merges the per-block statistics a producer left in `partial` [M][blocks] (of v - pivot, 64 columns per block) into
 // coef[m] = (rstd / s_m, -rstd * (mu - p_m)) for the consumer of those planes, then moves rowps[m] on: the pair the producer wrote
 // under becomes "what the planes hold now", (mu, scale of the new rstd) what the next producer writes under
-void launch_ln_finalize(const float2* partial, int blocks, int64_t M, float eps, float4* rowps, float2* coef, hipStream_t s);
+// (frame_len, T_rows: as launch_ln_rowprep)
+void launch_ln_finalize(const float2* partial, int blocks, int64_t M, float eps, float4* rowps, float2* coef, const int* frame_len,
+                        int T_rows, hipStream_t s);
 // the same with the rows of a ragged batch gathered on the way out: input row n * T_rows + t -> plane row row_off[n] + t,
 // frames t >= frame_len[n] dropped (the feature projection of a ragged batch then runs on the valid frames only)
 void launch_rownorm_to_packed(int prec, const float* x, int64_t ldx, int64_t M, int D, const float* gamma1, const float* beta1,

@@ -178,15 +178,18 @@ void launch_pp_fold(const GemmParams& p, hipStream_t stream) {
     hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI, FOLD>), dim3(tiles < cus ? tiles : cus, 1, 1), dim3(512), lds, stream, p);
 }
 
+// false: nothing was launched -- a fold producer (p.ln_partial) planned on 192-column tiles, which have no producer epilogue
+// (gemm_ln_fold_ok refuses that plan; the caller reports the refusal instead of going on without the residual product)
 template <typename T, int NT, int MI, int NI = 4>
-void launch_pp_tiles(const GemmParams& p, int splits, hipStream_t stream) {
+bool launch_pp_tiles(const GemmParams& p, int splits, hipStream_t stream) {
     if (p.ln_partial) {
-        if constexpr (NI == 4) launch_pp_fold<T, NT, MI, 4, 2>(p, stream);
-        return;
+        if constexpr (NI != 4) return false;
+        launch_pp_fold<T, NT, MI, 4, 2>(p, stream);
+        return true;
     }
     if (p.row_coef) {
         launch_pp_fold<T, NT, MI, NI, 1>(p, stream);
-        return;
+        return true;
     }
     static OncePerDevice attr;
     constexpr int lds = pp::lds_bytes(NT, MI, NI);
@@ -202,6 +205,7 @@ void launch_pp_tiles(const GemmParams& p, int splits, hipStream_t stream) {
     } else {
         hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI>), grid, dim3(512), lds, stream, p);
     }
+    return true;
 }
 
 // Tile height (256 or 128 rows) and number of K chunks of a ping-pong product, by a cost model in units of one 32-deep MFMA
@@ -246,16 +250,15 @@ void pp_plan(int NT, const GemmParams& p, int* mi_out, int* splits_out, int* ni_
         }
 }
 
+// (the caller has checked pp_eligible) false: nothing was launched, see launch_pp_tiles
 template <typename T, int NT>
 bool launch_gemm_pp(const GemmParams& p, hipStream_t stream) {
-    if (!pp_eligible(NT, p)) return false;
     int mi, splits, ni;
     pp_plan(NT, p, &mi, &splits, &ni);
-    if (mi == 8 && ni == 4) launch_pp_tiles<T, NT, 8, 4>(p, splits, stream);
-    else if (mi == 8) launch_pp_tiles<T, NT, 8, 3>(p, splits, stream);
-    else if (ni == 4) launch_pp_tiles<T, NT, 4, 4>(p, splits, stream);
-    else launch_pp_tiles<T, NT, 4, 3>(p, splits, stream);
-    return true;
+    if (mi == 8 && ni == 4) return launch_pp_tiles<T, NT, 8, 4>(p, splits, stream);
+    if (mi == 8) return launch_pp_tiles<T, NT, 8, 3>(p, splits, stream);
+    if (ni == 4) return launch_pp_tiles<T, NT, 4, 4>(p, splits, stream);
+    return launch_pp_tiles<T, NT, 4, 3>(p, splits, stream);
 }
 
 bool dma_tile_eligible(int NT, const GemmParams& p) {
@@ -326,8 +329,9 @@ int dma_preferred_shape(int NT, const GemmParams& p) {
 }
 
 template <typename T, int NT>
-void launch_gemm_t(const GemmParams& p, hipStream_t stream) {
-    if (!dma_preferred_shape(NT, p) && launch_gemm_pp<T, NT>(p, stream)) return;
+bool launch_gemm_t(const GemmParams& p, hipStream_t stream) {
+    if (!dma_preferred_shape(NT, p) && pp_eligible(NT, p)) return launch_gemm_pp<T, NT>(p, stream);
+    if (p.ln_partial || p.row_coef) return false;  // the fold's epilogues exist in the ping-pong kernel only
     const int shape = dma_tile_shape(NT, p, 1);  // preferred, or the ping-pong kernel rejected the product
     if (shape) {
         // the ring hides the memory latency, so the K loop is only cut where it is long (K = 4096) and the grid small
@@ -343,7 +347,7 @@ void launch_gemm_t(const GemmParams& p, hipStream_t stream) {
         }
         launch_gemm_dma_shape<T, NT>(shape, q, splits, stream);
         if (splits > 1 && !p.defer_fixup) launch_fixup<T, NT>(p, splits, stream);
-        return;
+        return true;
     }
     // narrow outputs (grouped pos-conv, small classifier heads) use the 128x64 tile
     const bool narrow = p.N <= 64;
@@ -363,6 +367,7 @@ void launch_gemm_t(const GemmParams& p, hipStream_t stream) {
     if (narrow) hipLaunchKernelGGL((gemm_kernel<T, NT, 128, 64, 4, 1>), grid, dim3(256), lds, stream, q);
     else hipLaunchKernelGGL((gemm_kernel<T, NT, 128, 128, 2, 2>), grid, dim3(256), lds, stream, q);
     if (splits > 1 && !p.defer_fixup) launch_fixup<T, NT>(p, splits, stream);
+    return true;
 }
 
 // the K chunks launch_gemm_t will use: the same decisions, without the launches
@@ -474,7 +479,7 @@ void launch_fixup_rownorm(int prec, const GemmParams& p, int splits, const float
     }
 }
 
-void launch_gemm(int prec, const GemmParams& p_in, hipStream_t stream) {
+bool launch_gemm(int prec, const GemmParams& p_in, hipStream_t stream) {
     const GemmParams p = with_vec_flag(p_in);
     if (p.ln_gamma) {
         // fused LayerNorm + GELU: only the row-complete kernel implements it (callers check gemm_fuses_ln first)
@@ -484,13 +489,13 @@ void launch_gemm(int prec, const GemmParams& p_in, hipStream_t stream) {
             case PREC_BF16X3: launch_gemm_ln<bf16, 2>(p, stream); break;
             default: launch_gemm_ln<f16, 2>(p, stream); break;
         }
-        return;
+        return true;
     }
     switch (prec) {
-        case PREC_BF16: launch_gemm_t<bf16, 1>(p, stream); break;
-        case PREC_F16: launch_gemm_t<f16, 1>(p, stream); break;
-        case PREC_BF16X3: launch_gemm_t<bf16, 2>(p, stream); break;
-        default: launch_gemm_t<f16, 2>(p, stream); break;
+        case PREC_BF16: return launch_gemm_t<bf16, 1>(p, stream);
+        case PREC_F16: return launch_gemm_t<f16, 1>(p, stream);
+        case PREC_BF16X3: return launch_gemm_t<bf16, 2>(p, stream);
+        default: return launch_gemm_t<f16, 2>(p, stream);
     }
 }
 

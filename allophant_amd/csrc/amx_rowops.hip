@@ -918,21 +918,32 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* x, int64_t ld
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// LayerNorm fold (GemmParams.ln_partial / row_coef, amx_common.h).  The power of two a row's planes are written under: 16 * rstd
-// rounded down to a power of two, i.e. sigma * s in (8, 16] -- |x - mu| <= sqrt(D) sigma keeps a row itself below 512, and the NEXT
-// state of the row (written under this scale before its own statistics are known) may grow a hundredfold before an fp16 plane
-// overflows (which the range report of the pass would then show); values below 2^-6 sigma lose bits of their lo plane.
+// LayerNorm fold (GemmParams.ln_partial / row_coef, amx_common.h).  The power of two a row's planes are written under: 2 * rstd
+// rounded down to a power of two, i.e. sigma * s in (1, 2] -- |x - mu| <= sqrt(D) sigma keeps a row itself below 64, and an element
+// of the NEXT state of the row (written under this scale before its own statistics are known) may move 32 768 .. 65 504 of the
+// previous sigmas before an fp16 plane overflows (which the range report of the pass then shows): a sublayer's sudden outlier
+// channel stays in range.  The lo plane of a two-plane pair turns subnormal below 2^-3 / s, 0.06 .. 0.125 sigma, and keeps its
+// bits down to 2^-24 / s (tests/diagnostics/emulate_ln_fold.py: no measurable cost against a scale of 16 * rstd).
+// Padded frames of a ragged batch in the padded layout (frame_len, T_rows given) take 2^-6 of that scale: their sigma is 2 .. 7
+// times smaller than that of the valid frames, and the same bias jump would overflow them first.  Nothing valid reads them -- the
+// attention masks their keys, hidden states publish zeros there -- but a non-finite padded V row times a masked P = 0 is NaN.
 // ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ln_plane_scale(float rstd) {
-    const float t = fminf(fmaxf(16.0f * rstd, 1.0e-12f), 1.0e12f);
-    return __uint_as_float(__float_as_uint(t) & 0x7F800000u);
+constexpr float LN_PAD_SCALE = 0x1p-6f;
+__device__ __forceinline__ float ln_plane_scale(float rstd, bool padded) {
+    const float t = fminf(fmaxf(2.0f * rstd, 1.0e-12f), 1.0e12f);
+    const float s = __uint_as_float(__float_as_uint(t) & 0x7F800000u);
+    return padded ? s * LN_PAD_SCALE : s;
+}
+__device__ __forceinline__ bool ln_padded_row(int64_t row, const int* frame_len, int T_rows) {
+    return frame_len && (int)(row % T_rows) >= frame_len[row / T_rows];
 }
 
 // the first norm of the stack: exact statistics from the fp32 row (the arithmetic of rownorm_kernel), planes of (x - mu) * s
 template <typename T, int NT, int V = 4>
 __global__ __launch_bounds__(256) void ln_rowprep_kernel(const float* __restrict__ x, int64_t ldx, int64_t M, int D, float eps,
                                                          T* __restrict__ out_p, int64_t out_plane, int64_t ldp,
-                                                         float4* __restrict__ rowps, float2* __restrict__ coef) {
+                                                         float4* __restrict__ rowps, float2* __restrict__ coef,
+                                                         const int* __restrict__ frame_len, int T_rows) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -958,7 +969,7 @@ __global__ __launch_bounds__(256) void ln_rowprep_kernel(const float* __restrict
         }
     }
     const float rs = 1.0f / sqrtf(wave_sum(q) * invD + eps);
-    const float sc = ln_plane_scale(rs);
+    const float sc = ln_plane_scale(rs, ln_padded_row(row, frame_len, T_rows));
     if (lane == 0) {
         rowps[row] = make_float4(mu, sc, mu, sc);
         coef[row] = make_float2(rs / sc, 0.f);
@@ -986,7 +997,8 @@ __global__ __launch_bounds__(256) void ln_rowprep_kernel(const float* __restrict
 
 // one thread per row: Chan's pairwise update over the row's 64-column blocks, in ascending order
 __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* __restrict__ partial, int blocks, int64_t M, float eps,
-                                                          float4* __restrict__ rowps, float2* __restrict__ coef) {
+                                                          float4* __restrict__ rowps, float2* __restrict__ coef,
+                                                          const int* __restrict__ frame_len, int T_rows) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= M) return;
     const float2* pr = partial + row * blocks;
@@ -1014,7 +1026,7 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* __restri
     const float m1 = mu * inv_w;  // mean of x - pivot
     const float rs = 1.0f / sqrtf(m2 * invD * inv_w * inv_w + eps);
     coef[row] = make_float2(rs * inv_w, -rs * m1);
-    rowps[row] = make_float4(ps.z, ps.w, ps.z + m1, ln_plane_scale(rs));
+    rowps[row] = make_float4(ps.z, ps.w, ps.z + m1, ln_plane_scale(rs, ln_padded_row(row, frame_len, T_rows)));
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -1665,19 +1677,21 @@ void launch_rownorm(int prec, const float* x, int64_t ldx, int64_t M, int D, con
 }
 
 void launch_ln_rowprep(int prec, const float* x, int64_t ldx, int64_t M, int D, float eps, void* out_p, int64_t out_plane, int64_t ldp,
-                       float4* rowps, float2* coef, hipStream_t s) {
+                       float4* rowps, float2* coef, const int* frame_len, int T_rows, hipStream_t s) {
     dim3 grid((unsigned)((M + 3) / 4));
     if (D <= 1024) {
         AMX_DISPATCH(prec, hipLaunchKernelGGL((ln_rowprep_kernel<T16, NT, 4>), grid, dim3(256), 0, s, x, ldx, M, D, eps, (T16*)out_p, out_plane,
-                                              ldp, rowps, coef));
+                                              ldp, rowps, coef, frame_len, T_rows));
     } else {
         AMX_DISPATCH(prec, hipLaunchKernelGGL((ln_rowprep_kernel<T16, NT, 8>), grid, dim3(256), 0, s, x, ldx, M, D, eps, (T16*)out_p, out_plane,
-                                              ldp, rowps, coef));
+                                              ldp, rowps, coef, frame_len, T_rows));
     }
 }
 
-void launch_ln_finalize(const float2* partial, int blocks, int64_t M, float eps, float4* rowps, float2* coef, hipStream_t s) {
-    hipLaunchKernelGGL(ln_finalize_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, partial, blocks, M, eps, rowps, coef);
+void launch_ln_finalize(const float2* partial, int blocks, int64_t M, float eps, float4* rowps, float2* coef, const int* frame_len,
+                        int T_rows, hipStream_t s) {
+    hipLaunchKernelGGL(ln_finalize_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, partial, blocks, M, eps, rowps, coef,
+                       frame_len, T_rows);
 }
 
 void launch_rownorm_to_packed(int prec, const float* x, int64_t ldx, int64_t M, int D, const float* gamma1, const float* beta1,

@@ -16,10 +16,18 @@ Linear-shaped product of a layer as hi.hi + lo.hi + hi.lo on f16 planes with fp3
   fold_planes_fixed   the same with the pivot and the scale of a row FIXED for the whole stack at what the first norm gave (one pair
                  of row parameters per pass instead of one per product)
 
-Weight families: those of tests/test_gpu_range.py (plain, scales, student_t, ln_gain, outlier) plus `dc30`: every row of the
-residual stream carries a DC offset of ~ 30 sigma.
+The power of two s of a row is LN_PLANE_HEADROOM * rstd rounded down (sigma * s in (H / 2, H]), as ln_plane_scale in
+amx_rowops.hip; `--headroom H` runs another value.  An fp16 plane overflows to inf: an element that moves more than about
+65504 / H of its row's previous sigmas leaves the planes (the fold columns then read inf).  The batch runs in the padded layout
+(every row of [N, T] holds planes, as the fold does for ragged batches with under 10 % padding): padded frames, whose sigma is
+2 .. 7 times smaller than that of the valid ones, take LN_PAD_SCALE times the scale, as in the kernels.  `peak` is the largest
+|u| a plane was asked to hold on valid / padded rows.
 
-    python tests/diagnostics/emulate_ln_fold.py [seconds] [family ...]
+Weight families: those of tests/test_gpu_range.py (plain, scales, student_t, ln_gain, outlier), `dc30`: every row of the
+residual stream carries a DC offset of ~ 30 sigma, and `jump:<layer>:<out_proj|ffn2>:<m>`: one channel of that sublayer's bias
+raised by m x the smallest valid-row sigma of the oracle's hidden state `layer` (tests/jump_util.py).
+
+    python tests/diagnostics/emulate_ln_fold.py [--headroom H] [--pad-scale P] [seconds] [family ...]
 """
 import math
 import os
@@ -31,10 +39,14 @@ import torch.nn.functional as F
 
 from allophant_amd import spec as S, synthetic
 from oracle import allophant_oracle as O
+from tests.jump_util import add_jump
 from tests.test_gpu_range import _variant
 
 torch.set_num_threads(8)
 AM = O._AM
+LN_PLANE_HEADROOM = 2.0  # ln_plane_scale (amx_rowops.hip): s = 2 * rstd rounded down to a power of two
+LN_PAD_SCALE = 2.0 ** -6  # ... times this on padded frames (LN_PAD_SCALE, amx_rowops.hip)
+PEAK = {}  # (scheme, "valid" / "padded") -> largest |u| a plane was asked to hold in the last run
 
 
 def split(x):
@@ -80,7 +92,7 @@ def row_partials(e, width=64):
     return mean, M2 / D
 
 
-def encoder_layers(h, bias, state, spec, scheme):
+def encoder_layers(h, bias, state, spec, scheme, headroom=LN_PLANE_HEADROOM, pad_scale=LN_PAD_SCALE):
     """h [N,T,D] after the positional convolution -> hidden_states list (as oracle.wav2vec2_hidden_states)"""
     eps = spec["eps"]
     H = spec["heads"]
@@ -90,6 +102,8 @@ def encoder_layers(h, bias, state, spec, scheme):
     fold = scheme.startswith("fold")
     pivot = scheme in ("fold", "fold_planes", "fold_planes_fixed")
     planes_only = scheme in ("fold_planes", "fold_planes_fixed")
+    valid = (bias[:, 0, 0, :] == 0).reshape(N * T)
+    row_pad = torch.where(valid, 1.0, pad_scale)  # (an exact power of two per row)
     fixed = scheme == "fold_planes_fixed"  # pivot and scale of a row stay what the first norm of the stack gave
     x = h.reshape(N * T, D).clone()
     M = x.shape[0]
@@ -99,7 +113,7 @@ def encoder_layers(h, bias, state, spec, scheme):
         var = ((x - mu[:, None]) ** 2).mean(-1)
         rstd = 1.0 / torch.sqrt(var + eps)
         p = mu if pivot else torch.zeros(M)
-        s = pow2_floor(16.0 * rstd) if pivot else torch.ones(M)
+        s = pow2_floor(headroom * rstd) * row_pad if pivot else torch.ones(M)
         u = (x - p[:, None]) * s[:, None]
         alpha = rstd / s
         beta = -rstd * (mu - p)
@@ -127,6 +141,9 @@ def encoder_layers(h, bias, state, spec, scheme):
         if fold:
             e = v - p[:, None]
             u = e * s[:, None]
+            for part, rows in (("valid", valid), ("padded", ~valid)):
+                if rows.any():
+                    PEAK[scheme, part] = max(PEAK.get((scheme, part), 0.0), float(u[rows].abs().max()))
             m1, var = row_partials(e)
             rstd = 1.0 / torch.sqrt(var + eps)
             alpha = rstd / s
@@ -138,7 +155,7 @@ def encoder_layers(h, bias, state, spec, scheme):
             if pivot and not fixed:
                 # what the NEXT producer writes its planes under
                 p = p + m1
-                s = pow2_floor(16.0 * rstd)
+                s = pow2_floor(headroom * rstd) * row_pad
 
     for i in range(spec["layers"]):
         hidden.append(x.reshape(N, T, D).clone())
@@ -159,7 +176,7 @@ def encoder_layers(h, bias, state, spec, scheme):
     return hidden
 
 
-def run(audio, lengths, state, spec, tfi, offsets, scheme):
+def run(audio, lengths, state, spec, tfi, offsets, scheme, headroom=LN_PLANE_HEADROOM, pad_scale=LN_PAD_SCALE):
     with torch.inference_mode():
         eps = spec["eps"]
         mask = O.mask_sequence(lengths, None)
@@ -182,21 +199,29 @@ def run(audio, lengths, state, spec, tfi, offsets, scheme):
         if scheme == "exact":
             hidden, _, _ = O.wav2vec2_hidden_states(audio, lengths, state, spec)
         else:
-            hidden = encoder_layers(h, bias, state, spec, scheme)
+            hidden = encoder_layers(h, bias, state, spec, scheme, headroom, pad_scale)
         logits = O.projection_forward([t.transpose(0, 1) for t in hidden], state, spec, tfi, offsets, fl)
         return {k_: F.log_softmax(v, -1) for k_, v in logits.items()}, fl, hidden
 
 
 def main():
-    seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 2.0
-    families = sys.argv[2:] or ["plain", "dc30", "scales", "student_t", "ln_gain", "outlier"]
+    args = sys.argv[1:]
+    headroom, pad_scale = LN_PLANE_HEADROOM, LN_PAD_SCALE
+    while args[:1] in (["--headroom"], ["--pad-scale"]):
+        if args[0] == "--headroom":
+            headroom = float(args[1])
+        else:
+            pad_scale = float(args[1])
+        args = args[2:]
+    seconds = float(args[0]) if args else 2.0
+    families = args[1:] or ["plain", "dc30", "scales", "student_t", "ln_gain", "outlier"]
     spec = S.multitask_spec(S.xlsr_300m_encoder(), allophone_layer=True)
     spec["shared_phones"] = 80
     tfi = synthetic.make_inventory(spec, 27, seed=0)
     offsets = synthetic.category_offsets(spec)
     audio, lengths = synthetic.make_audio(2, int(seconds * 16000), seed=1234, ragged=True)
     for fam in families:
-        if fam in ("plain", "dc30"):
+        if fam in ("plain", "dc30") or fam.startswith("jump:"):
             state = synthetic.make_state_dict(spec, seed=0)
         else:
             state = _variant(spec, 0, fam)
@@ -204,17 +229,23 @@ def main():
             # a DC offset on every channel of the stream: ~ 30 x the row's standard deviation (measured below)
             key = AM + "encoder.layers.0.attention.out_proj.bias"
             state[key] = state[key] + 80.0
+        if fam.startswith("jump:"):
+            _, layer, sublayer, m = fam.split(":")
+            add_jump(state, spec, int(layer), sublayer, float(m))
         exact, fl, hid = run(audio, lengths, state, spec, tfi, offsets, "exact")
         row = hid[2].reshape(-1, hid[2].shape[-1])
         ratio = (row.mean(-1).abs() / row.std(-1)).median().item()
-        line = f"{fam:10s} |mean|/sigma of stream rows (layer 2) = {ratio:6.2f}  "
+        line = f"{fam:18s} |mean|/sigma of stream rows (layer 2) = {ratio:6.2f}  "
         for scheme in ("current", "fold", "fold_planes", "fold_planes_fixed"):
-            got, _, _ = run(audio, lengths, state, spec, tfi, offsets, scheme)
+            PEAK.clear()
+            got, _, _ = run(audio, lengths, state, spec, tfi, offsets, scheme, headroom, pad_scale)
             worst = 0.0
             for k_ in exact:
                 valid = (torch.arange(got[k_].shape[0]).unsqueeze(1) < fl.unsqueeze(0)).unsqueeze(-1)
-                worst = max(worst, ((got[k_] - exact[k_]).abs() * valid).max().item())
-            line += f" {scheme} {worst:.2e} "
+                err = torch.where(valid, (got[k_] - exact[k_]).abs(), 0.0)
+                worst = max(worst, err.max().item() if torch.isfinite(err).all() else math.inf)  # (an overflowed plane: inf / nan)
+            peak = "/".join(f"{PEAK[scheme, part]:.3g}" for part in ("valid", "padded") if (scheme, part) in PEAK)
+            line += f" {scheme} {worst:.2e}" + (f" (peak {peak})" if peak else "") + " "
         print(line, flush=True)
 
 
