@@ -2,6 +2,7 @@
 // composition, and the forward pass orchestration (kernel sequence on one HIP stream).
 #include "../../include/allophant_amx.h"
 #include "../../include/allophant_amx_allophones.h"
+#include "../../include/allophant_amx_beam.h"
 #include "amx_common.h"
 
 #include <algorithm>
@@ -2382,6 +2383,90 @@ extern "C" int amx_greedy_ctc_emissions(int device, const float* emissions, int6
     launch_greedy_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, tokens, timesteps, counts,
                                 scores, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "greedy CTC kernel launch failed");
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// CTC beam search
+// =================================================================================================================
+namespace {
+int beam_check(amx_handle h, int beam_width, int n_best, uint32_t flags) {
+    if (beam_width < 1 || beam_width > BEAM_MAX)
+        return fail(h, AMX_EINVAL, "beam_width must be 1 to " + std::to_string(BEAM_MAX) + ", got " + std::to_string(beam_width));
+    if (n_best < 1 || n_best > beam_width)
+        return fail(h, AMX_EINVAL, "n_best must be 1 to beam_width (" + std::to_string(beam_width) + "), got " + std::to_string(n_best));
+    if (flags & ~AMX_BEAM_EXP_EMISSIONS) return fail(h, AMX_EINVAL, "unknown beam-search flags");
+    return AMX_OK;
+}
+int beam_check_classes(amx_handle h, int C) {
+    if (C < 2 || C > BEAM_MAX_CLASSES)
+        return fail(h, AMX_EINVAL, "beam search needs 2 to " + std::to_string(BEAM_MAX_CLASSES) + " classes, got " + std::to_string(C));
+    return AMX_OK;
+}
+}  // namespace
+
+extern "C" int amx_beam_ctc_workspace(int beam_width, int64_t rows, int64_t T, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = beam_check(nullptr, beam_width, 1, 0)) return rc;
+    if (rows < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative beam-search geometry");
+    *bytes = (size_t)rows * (size_t)T * (size_t)beam_width * sizeof(uint32_t);
+    return AMX_OK;
+}
+
+extern "C" int amx_beam_ctc(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L, int beam_width, int n_best,
+                            uint32_t flags, void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* timesteps,
+                            int32_t* counts, double* scores, int32_t* hyp_counts, void* stream) {
+    if (!h) return AMX_EINVAL;
+    if (!out || !frame_lengths || !tokens || !timesteps || !counts || !scores || !hyp_counts) return fail(h, AMX_EINVAL, "null buffer");
+    if (int rc = beam_check(h, beam_width, n_best, flags)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = compute_layout(h, N, L);
+    if (rc) return rc;
+    const int T = (int)h->layout_T;
+    for (const OutDesc& d : h->out_all)
+        if ((rc = beam_check_classes(h, d.C))) return rc;
+    const int64_t rows = (int64_t)h->out_all.size() * N;
+    size_t need = 0;
+    amx_beam_ctc_workspace(beam_width, rows, T, &need);
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(h, AMX_EINVAL, "beam-search workspace too small: " + std::to_string(need) + " bytes needed");
+    std::vector<int> fl(N);
+    for (int n = 0; n < N; ++n) {
+        if (frame_lengths[n] < 0 || frame_lengths[n] > T) return fail(h, AMX_EINVAL, "frame length out of range");
+        fl[n] = (int)frame_lengths[n];
+    }
+    void* d_fl;
+    if ((rc = ws_get(h, "ctc_frames", (size_t)N * 4, &d_fl))) return rc;
+    HIPCHK(h, hipMemcpyAsync(d_fl, fl.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));  // fl is pageable host memory
+    launch_beam_ctc(h->out_all_dev, (int)h->out_all.size(), out, (const int*)d_fl, N, T, beam_width, n_best,
+                    (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores, hyp_counts, s);
+    HIPCHK(h, hipGetLastError());
+    return AMX_OK;
+}
+
+extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                      const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index, int beam_width,
+                                      int n_best, uint32_t flags, void* workspace, size_t workspace_bytes, int64_t* tokens,
+                                      int64_t* timesteps, int32_t* counts, double* scores, int32_t* hyp_counts, void* stream) {
+    if (int rc = beam_check(nullptr, beam_width, n_best, flags)) return rc;
+    if (int rc = beam_check_classes(nullptr, C)) return rc;
+    if (blank_index < 0 || blank_index >= C) return fail(nullptr, AMX_EINVAL, "blank_index out of range");
+    if (N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative emission geometry");
+    if (T > INT32_MAX) return fail(nullptr, AMX_EINVAL, "too many frames");
+    if (N == 0) return AMX_OK;
+    if (!emissions || !frame_lengths || !tokens || !timesteps || !counts || !scores || !hyp_counts)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    size_t need = 0;
+    amx_beam_ctc_workspace(beam_width, N, T, &need);
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(nullptr, AMX_EINVAL, "beam-search workspace too small: " + std::to_string(need) + " bytes needed");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_beam_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, beam_width, n_best,
+                              (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores,
+                              hyp_counts, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "beam-search kernel launch failed");
     return AMX_OK;
 }
 

@@ -466,6 +466,20 @@ void launch_greedy_ctc(const OutDesc* descs_dev, int n_out, const float* out, co
 void launch_greedy_ctc_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T,
                                  int C, int blank, int64_t* tokens, int64_t* timesteps, int* counts, float* scores, hipStream_t s);
 
+// CTC prefix beam search (amx_ctc_beam.hip), one workgroup per row: the reference's BeamCTCDecoder (lexicon-free, no LM).
+// Per row: tokens / timesteps int64 [n_best, T], counts int32 [n_best], scores fp64 [n_best], hyp_counts int32; the workspace
+// holds a uint32 backpointer per (row, frame, slot), rows x T x beam.  launch_beam_ctc decodes every output block of `out`
+// (rows o * N + n, blank 0), launch_beam_ctc_emissions one [N, T, C] tensor read with element strides (stride_n, stride_t, 1).
+// Limits (checked by the callers): 1 <= n_best <= beam <= BEAM_MAX, 2 <= C <= 65535.
+constexpr int BEAM_MAX = 64;
+constexpr int BEAM_MAX_CLASSES = 65535;
+void launch_beam_ctc(const OutDesc* descs_dev, int n_out, const float* out, const int* frame_len, int N, int T, int beam, int n_best,
+                     int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps, int* counts, double* scores, int* hyp_counts,
+                     hipStream_t s);
+void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
+                               int blank, int beam, int n_best, int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps,
+                               int* counts, double* scores, int* hyp_counts, hipStream_t s);
+
 // allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
 // strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]
 // of ent_p / ent_w and the accumulator start col_init[l * Q1 + q]; language_ids int32 [N] in [0, n_lang)

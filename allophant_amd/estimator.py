@@ -7,6 +7,7 @@ Mirrors (reference file:line):
   * ``Estimator.predict``    allophant/estimator.py:1035-1046
   * ``Estimator.restore``    allophant/estimator.py:1085-1126 (checkpoint dict schema estimator.py:199-249)
   * ``GreedyCTCDecoder``     allophant/predictions.py:189-207
+  * ``BeamCTCDecoder``, ``_ctc_decoder``, ``feature_decoders``  allophant/predictions.py:210-254
   * ``Estimator.map_allophones``  allophant/estimator.py:1048-1049 -> AllophoneMapping.map_allophones
                              (allophant/network/acoustic_model.py:142-159)
 
@@ -141,6 +142,43 @@ class Decoded(NamedTuple):
                 hyps.append([CTCHypothesis(tokens_h[o, n, :k].clone(), [], float(scores_h[o, n]), timesteps_h[o, n, :k].clone())])
             result[name] = hyps
         return result
+
+
+
+def _beam_hypotheses(tokens: Tensor, timesteps: Tensor, counts: Tensor, scores: Tensor, hyp_counts: Tensor
+                     ) -> List[List[CTCHypothesis]]:
+    """Host form of beam-search rows: ``tokens`` / ``timesteps`` ``[R, n_best, T]``, ``counts`` / ``scores`` ``[R, n_best]``,
+    ``hyp_counts`` ``[R]`` -> per row the list of its hypotheses, best first."""
+    tokens_h, timesteps_h, counts_h = tokens.cpu(), timesteps.cpu(), counts.cpu()
+    scores_h, hyp_h = scores.cpu(), hyp_counts.cpu()
+    result = []
+    for r in range(hyp_h.shape[0]):
+        hyps = []
+        for h in range(int(hyp_h[r])):
+            k = int(counts_h[r, h])
+            hyps.append(CTCHypothesis(tokens_h[r, h, :k].clone(), [], float(scores_h[r, h]), timesteps_h[r, h, :k].clone()))
+        result.append(hyps)
+    return result
+
+
+class BeamDecoded(NamedTuple):
+    """CTC beam-search results of a batch, one row per output: ``tokens`` / ``timesteps`` ``[O, N, n_best, T]`` int64 of which
+    the first ``counts[o, n, h]`` entries are valid (timesteps 1-based), ``counts`` ``[O, N, n_best]`` int32, ``scores``
+    ``[O, N, n_best]`` fp64 (descending), ``hyp_counts`` ``[O, N]`` int32 hypotheses found.  Device tensors when produced by
+    ``Estimator.beam_decode_device``."""
+    names: List[str]
+    tokens: Tensor
+    timesteps: Tensor
+    counts: Tensor
+    scores: Tensor
+    hyp_counts: Tensor
+
+    def hypotheses(self) -> Dict[str, List[List[CTCHypothesis]]]:
+        """Host form: per output and utterance the reference's list of up to ``n_best`` ``CTCHypothesis``."""
+        O, N, B, T = self.tokens.shape
+        rows = _beam_hypotheses(self.tokens.reshape(O * N, B, T), self.timesteps.reshape(O * N, B, T),
+                                self.counts.reshape(O * N, B), self.scores.reshape(O * N, B), self.hyp_counts.reshape(O * N))
+        return {name: rows[o * N:(o + 1) * N] for o, name in enumerate(self.names)}
 
 
 def _spec_to_structs(spec: Dict[str, Any], precision: str):
@@ -542,6 +580,45 @@ class Estimator:
         scores cross PCIe."""
         return self.greedy_decode_device(predictions).hypotheses()
 
+    def beam_decode_device(self, predictions: Predictions, beam_width: int, n_best: int = 1,
+                           exp_emissions: bool = True) -> "BeamDecoded":
+        """On-device ``BeamCTCDecoder`` (reference predictions.py:210-235) over every output of ``predictions``, as the
+        reference's decode loop applies it per classifier (run.py:767-785).  ``exp_emissions`` (default, like upstream's
+        ``log_emissions.exp()``) adds probabilities; False adds the log-probabilities as given.  The result stays in HBM."""
+        if predictions._flat is None or predictions._geometry is None:
+            raise ValueError("predictions were not produced by this estimator")
+        _check_beam(beam_width, n_best)
+        N, L = predictions._geometry
+        if predictions._inventory is not None:
+            self._set_inventory(predictions._inventory)  # decode under the inventory of THESE predictions (greedy_decode_device)
+        names = list(predictions.outputs.keys())
+        T = next(iter(predictions.outputs.values())).shape[0]
+        O = len(names)
+        with torch.cuda.device(self._device):
+            size = C.c_size_t()
+            _lib.check(self._lib, None, self._lib.amx_beam_ctc_workspace(beam_width, O * N, T, C.byref(size)))
+            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=self._device)
+            tokens = torch.empty(O, N, n_best, T, dtype=torch.int64, device=self._device)
+            timesteps = torch.empty_like(tokens)
+            counts = torch.empty(O, N, n_best, dtype=torch.int32, device=self._device)
+            scores = torch.empty(O, N, n_best, dtype=torch.float64, device=self._device)
+            hyp_counts = torch.empty(O, N, dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
+            code = self._lib.amx_beam_ctc(
+                self._handle, C.c_void_p(predictions._flat.data_ptr()),
+                C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)), N, L, beam_width, n_best,
+                _lib.BEAM_EXP_EMISSIONS if exp_emissions else 0, C.c_void_p(workspace.data_ptr()), size.value,
+                C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()),
+                C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
+            _lib.check(self._lib, self._handle, code)
+        return BeamDecoded(names, tokens, timesteps, counts, scores, hyp_counts)
+
+    def beam_decode(self, predictions: Predictions, beam_width: int, n_best: int = 1,
+                    exp_emissions: bool = True) -> Dict[str, List[List[CTCHypothesis]]]:
+        """``beam_decode_device`` fetched to the host: per output and utterance up to ``n_best`` hypotheses, best first."""
+        return self.beam_decode_device(predictions, beam_width, n_best, exp_emissions).hypotheses()
+
     def debug_fetch(self, what: str, index: int = 0) -> Tensor:
         """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors."""
         code_of = {"conv": 0, "hidden": 1, "logits": 2}
@@ -694,11 +771,103 @@ def greedy_ctc_decode(log_emissions: Tensor, lengths: Tensor, blank_index: int =
     return result
 
 
-def feature_decoders(indexer, beam_width: int = 1, feature_names=None, n_best: int = 1) -> Dict[str, GreedyCTCDecoder]:
-    """``predictions.feature_decoders`` (reference predictions.py:245-254) for greedy decoding: one decoder per feature
-    name of ``indexer`` (an ``AttributeTable`` or anything with ``feature_names``).  Beam search (``beam_width > 1``) is the
-    torchaudio/flashlight CPU decoder upstream and is not part of this path."""
-    if beam_width != 1 or n_best != 1:
-        raise NotImplementedError("only greedy decoding (beam_width=1) runs on the device; beam search is out of scope")
+def _check_beam(beam_width: int, n_best: int) -> None:
+    if n_best > beam_width:
+        raise ValueError("N-best can not exceed beam width")
+    if not 1 <= beam_width <= _lib.BEAM_MAX_WIDTH:
+        raise ValueError(f"beam_width must be 1 to {_lib.BEAM_MAX_WIDTH} on the device, got {beam_width}")
+    if n_best < 1:
+        raise ValueError(f"n_best must be at least 1, got {n_best}")
+
+
+class BeamCTCDecoder:
+    """``BeamCTCDecoder`` with the reference's signature (predictions.py:210-229), decoding on the device:
+
+        decoder = BeamCTCDecoder(["<blank>", *categories], beam_width, n_best)
+        hypotheses = decoder(outputs.transpose(1, 0), model_outputs.lengths)
+
+    Upstream this is torchaudio's flashlight ``ctc_decoder`` (lexicon-free, no LM, blank = silence, log_add) called on
+    ``log_emissions.exp()``; here ``amx_beam_ctc_emissions`` reads the fp32 ``[N, T, C]`` tensor in place (any strides with a
+    unit class stride) and exponentiates each value as it is read.  Returns, per utterance, up to ``n_best``
+    ``CTCHypothesis(tokens, [], score, timesteps)``, best first.  There is no CPU path."""
+
+    def __init__(self, tokens: List[str], beam_width: int, n_best: int = 1, blank_index: int = 0) -> None:
+        _check_beam(beam_width, n_best)
+        self._tokens = list(tokens)
+        if not 0 <= blank_index < len(self._tokens):
+            raise ValueError("blank_index out of range")
+        self._beam_width = int(beam_width)
+        self._n_best = int(n_best)
+        self._blank_index = int(blank_index)
+
+    def __call__(self, log_emissions: Tensor, lengths: Optional[Tensor] = None) -> List[List[CTCHypothesis]]:
+        if log_emissions.dim() == 3 and log_emissions.shape[2] != len(self._tokens):
+            raise ValueError(f"emissions have {log_emissions.shape[2]} classes, the decoder {len(self._tokens)} tokens")
+        return beam_ctc_decode(log_emissions, lengths, self._beam_width, self._n_best, self._blank_index)
+
+
+def beam_ctc_decode(log_emissions: Tensor, lengths: Optional[Tensor], beam_width: int, n_best: int = 1, blank_index: int = 0,
+                    exp_emissions: bool = True) -> List[List[CTCHypothesis]]:
+    """``BeamCTCDecoder.__call__`` (reference predictions.py:231-233) through ``amx_beam_ctc_emissions``; ``exp_emissions``
+    False adds the values as given instead of their exponentials."""
+    if log_emissions.dim() != 3:
+        raise ValueError("log_emissions must be [N, T, C]")
+    if log_emissions.device.type != "cuda":
+        raise RuntimeError("allophant_amd decodes on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    _check_beam(beam_width, n_best)
+    lib = _lib.load()
+    device = log_emissions.device
+    if log_emissions.dtype != torch.float32:
+        log_emissions = log_emissions.float()
+    if log_emissions.stride(2) != 1:
+        log_emissions = log_emissions.contiguous()
+    N, T, Cn = log_emissions.shape
+    if not 0 <= blank_index < Cn:
+        raise ValueError("blank_index out of range")
+    if N == 0:
+        return []
+    with torch.cuda.device(device):
+        if lengths is None:
+            frame_lengths = torch.full((N,), T, dtype=torch.int32, device=device)
+        else:
+            frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        size = C.c_size_t()
+        _lib.check(lib, None, lib.amx_beam_ctc_workspace(beam_width, N, T, C.byref(size)))
+        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        tokens = torch.empty(N, n_best, T, dtype=torch.int64, device=device)
+        timesteps = torch.empty_like(tokens)
+        counts = torch.empty(N, n_best, dtype=torch.int32, device=device)
+        scores = torch.empty(N, n_best, dtype=torch.float64, device=device)
+        hyp_counts = torch.empty(N, dtype=torch.int32, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        code = lib.amx_beam_ctc_emissions(
+            index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
+            C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, beam_width, n_best,
+            _lib.BEAM_EXP_EMISSIONS if exp_emissions else 0, C.c_void_p(workspace.data_ptr()), size.value,
+            C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()),
+            C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
+        _lib.check(lib, None, code)
+        return _beam_hypotheses(tokens, timesteps, counts, scores, hyp_counts)
+
+
+def _ctc_decoder(categories, beam_width: int = 1, n_best: int = 1):
+    """``predictions._ctc_decoder`` (reference predictions.py:236-242): greedy for a beam of one, else a beam-search decoder
+    over ``["<blank>", *categories]``."""
+    if n_best > beam_width:
+        raise ValueError("N-best can not exceed beam width")
+    if beam_width == 1:
+        return GreedyCTCDecoder()
+    return BeamCTCDecoder(["<blank>", *categories], beam_width, n_best)
+
+
+def feature_decoders(indexer, beam_width: int = 1, feature_names=None, n_best: int = 1) -> Dict[str, Any]:
+    """``predictions.feature_decoders`` (reference predictions.py:245-254): one decoder per feature name of ``indexer`` (an
+    ``AttributeTable`` or anything with ``feature_names``, and ``feature_categories`` for a beam): ``GreedyCTCDecoder`` for
+    ``beam_width == 1``, else ``BeamCTCDecoder`` over ``["<blank>", *indexer.feature_categories(name)]``."""
+    if n_best > beam_width:
+        raise ValueError("N-best can not exceed beam width")
     names = indexer.feature_names if feature_names is None else feature_names
-    return {name: GreedyCTCDecoder() for name in names}
+    if beam_width == 1:
+        return {name: GreedyCTCDecoder() for name in names}
+    return {name: _ctc_decoder(indexer.feature_categories(name), beam_width, n_best) for name in names}

@@ -38,6 +38,10 @@ EXPORTS = [
 ]
 # the allophone-layer entry points (include/allophant_amx_allophones.h; added to ABI 6, detected by name)
 ALLOPHONE_EXPORTS = ["amx_set_allophones", "amx_map_allophones"]
+# the CTC beam-search entry points (include/allophant_amx_beam.h; added to ABI 6, detected by name)
+BEAM_EXPORTS = ["amx_beam_ctc_workspace", "amx_beam_ctc", "amx_beam_ctc_emissions"]
+BEAM_EXP_EMISSIONS = 1  # AMX_BEAM_EXP_EMISSIONS
+BEAM_MAX_WIDTH = 64
 
 
 def dep_output_layer(i: int) -> int:
@@ -113,6 +117,14 @@ def load() -> C.CDLL:
         lib.amx_set_allophones.restype = i32
         lib.amx_map_allophones.argtypes = [vp, vp, i64, i64, vp, i32, i64, vp, vp]
         lib.amx_map_allophones.restype = i32
+    if hasattr(lib, "amx_beam_ctc"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_beam_ctc_workspace.argtypes = [i32, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_beam_ctc_workspace.restype = i32
+        lib.amx_beam_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, i32, i32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        lib.amx_beam_ctc.restype = i32
+        lib.amx_beam_ctc_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, i32, i32, C.c_uint32, vp, C.c_size_t,
+                                               vp, vp, vp, vp, vp, vp]
+        lib.amx_beam_ctc_emissions.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
