@@ -19,6 +19,12 @@ transformer encoder, all 36 attribute heads + the composed phoneme head, per-hea
 
 Weights are procedural (seed 0): real checkpoints are not reachable offline.  Rank 0 prints ONE JSON line (DESIGN.md
 section "Measurement" defines every field).
+
+A plain run does only what the headline needs: set-up, the warm-up and timed steps, `--dump-outputs`, the result line.
+`--full` adds everything else this file measures or checks, each after the timed region: the per-kernel timing pass and the
+roofline figures built on it, the PCIe-inclusive rate, the second precision (`--also`), the ragged batch, the CPU baseline and
+the parity spot check against the CPU oracle (N = 1), the weak-scaling leg (N > 1).  The `--no-*` switches, `--also` and
+`--cpu-sample` shape those legs.
 """
 from __future__ import annotations
 
@@ -365,17 +371,20 @@ def main():
     ap.add_argument("--utterances", type=int, default=None, help="utterances of the (global) batch (default: the config's)")
     ap.add_argument("--seconds", type=float, default=None)
     ap.add_argument("--phones", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: per-kernel timing pass + roofline, PCIe-inclusive rate, "
+                         "--also precision, ragged batch, CPU baseline + parity spot check (N = 1), weak scaling (N > 1)")
     ap.add_argument("--also", default="bf16", choices=["", "f16x3", "bf16x3", "f16", "bf16"],
-                    help="second precision mode reported under throughput_mode (N=1 only; empty string to skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: second precision mode reported under throughput_mode (N=1 only; empty string to skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=0,
-                    help="utterances of the batch the CPU baseline (and the parity spot check) runs on; 0 = the whole batch "
-                         "(config 2: 32 x 10 s, ~25 s per oracle run on the box)")
-    ap.add_argument("--no-spot-check", action="store_true", help="skip the oracle spot check of the timed path")
+                    help="--full: utterances of the batch the CPU baseline (and the parity spot check) runs on; 0 = the whole "
+                         "batch (config 2: 32 x 10 s, ~25 s per oracle run on the host of an MI355X node)")
+    ap.add_argument("--no-spot-check", action="store_true", help="--full: skip the oracle spot check of the timed path")
     ap.add_argument("--decoded-gather", action="store_true",
                     help="N > 1: also time the step that gathers greedy CTC alignments of the phoneme output instead of log-probs")
-    ap.add_argument("--no-ragged", action="store_true", help="N = 1: skip the informational ragged-batch leg")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the weak-scaling leg (32 x 10 s per GPU)")
+    ap.add_argument("--no-ragged", action="store_true", help="--full, N = 1: skip the informational ragged-batch leg")
+    ap.add_argument("--no-weak", action="store_true", help="--full, N > 1: skip the weak-scaling leg (32 x 10 s per GPU)")
     ap.add_argument("--no-graph", action="store_true",
                     help="enqueue every pass launch by launch (AMX_FLAG_NO_GRAPH) instead of replaying its HIP graph: the same kernels; "
                          "used under rocprofv3 counter collection (tools/profile_bench.sh)")
@@ -434,9 +443,9 @@ def main():
 
     def measure(precision, steps, warmup, batch, timing_pass=True, keep_outputs=False):
         """K timed steps (no per-kernel events: recording ~370 events costs 0.3-1.2 ms per step) bracketed by barrier +
-        synchronize, max over ranks; then a second pass of K steps with HIP events around every launch for the per-kernel
-        numbers.  `batch` is this rank's device-resident shard.  `keep_outputs`: the predictions of the last timed step (on
-        rank 0: the gathered global batch) are copied to the host into `last_outputs[precision]`."""
+        synchronize, max over ranks; then, with `timing_pass`, a second pass of K steps with HIP events around every launch
+        for the per-kernel numbers.  `batch` is this rank's device-resident shard.  `keep_outputs`: the predictions of the
+        last timed step (on rank 0: the gathered global batch) are copied to the host into `last_outputs[precision]`."""
         est = Estimator(spec, state, device, precision)
         # equal shards are established on the host below (shard_bounds of equal-length utterances): no per-step agreement
         runner = parallel.DataParallelRunner(lambda b: est.predict(b, tfi, True, _no_graph=args.no_graph), device, dst=0,
@@ -492,10 +501,11 @@ def main():
         est.close()
         return elapsed, timing
 
-    def summarize(precision, steps, timing, n_local):
-        planes = 2 if precision.endswith("x3") else 1
-        issue = 3 if planes == 2 else 1
-        w = work_model(spec, n_local, length, planes)
+    def work(precision, n_local):
+        return work_model(spec, n_local, length, 2 if precision.endswith("x3") else 1)
+
+    def summarize(precision, steps, timing, w):
+        issue = 3 if precision.endswith("x3") else 1
         traffic, traffic_source = load_traffic(precision)
         if args.config != 2 or args.utterances != CONFIG_PRESETS[2][0] or args.seconds != CONFIG_PRESETS[2][1] or world != 1 or args.encoder != "xlsr":
             # the committed PMC passes are those of config 2 on one GPU: another workload has other launches
@@ -585,7 +595,7 @@ def main():
             "timing": "HIP events around every launch in a second pass of the same K steps (recording them costs 0.3-1.2 ms per "
                       "step, so the timed region that yields `value` runs without them)",
         }
-        return w, roofline
+        return roofline
 
     def kernel_table(timing, steps):
         return {k: {"ms_per_step": round(v[0] / steps, 4), "launches_per_step": v[1] // max(1, steps)} for k, v in timing.items()}
@@ -610,8 +620,9 @@ def main():
         n_local = n_global
         local = Batch(audio.to(device), lengths, global_batch.language_ids)
 
-    elapsed, timing = measure(args.precision, args.steps, args.warmup, local, keep_outputs=args.dump_outputs is not None)
-    w, roofline = summarize(args.precision, args.steps, timing, n_local)
+    elapsed, timing = measure(args.precision, args.steps, args.warmup, local, timing_pass=args.full,
+                              keep_outputs=args.dump_outputs is not None)
+    w = work(args.precision, n_local)
     frames_global = w["frames_per_utt"] * n_global
     result = None
     if rank == 0:
@@ -648,8 +659,6 @@ def main():
                 "precision_mode": args.precision,
                 "encoder": args.encoder,
             },
-            "roofline": roofline,
-            "kernels": kernel_table(timing, args.steps),
             "whole_step_tflops": w["total"] * args.steps * world / elapsed / 1e12,
             # launch collapse (ABI 5): the timed steps replay ONE HIP graph of the ~185 launches of a pass
             "launch_collapse": {"graphs_recorded": graph_stats[args.precision][0], "passes_replayed": graph_stats[args.precision][1],
@@ -658,10 +667,13 @@ def main():
             # products around them: `kernels.rownorm` is then the fold's row statistics + the first / final norm), packed rows, graph
             "pass": pass_stats.get(args.precision),
         }
+        if args.full:
+            result["roofline"] = summarize(args.precision, args.steps, timing, w)
+            result["kernels"] = kernel_table(timing, args.steps)
         if args.dump_outputs is not None:
             result["dump_outputs"] = dump_outputs(args.dump_outputs, *last_outputs[args.precision])
     # N > 1: the weak-scaling leg (config 2 on every GPU), reported beside the strong-scaling headline
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         w_audio, w_lengths = synthetic.make_audio(n_global, length, seed=1234 + rank)
         weak_batch = Batch(w_audio.to(device), w_lengths, torch.zeros(n_global, dtype=torch.long))
         e_weak, _ = measure(args.precision, args.steps, args.warmup, weak_batch, timing_pass=False)
@@ -703,7 +715,7 @@ def main():
             }
     # N = 1: the same step when the boundary hands over HOST buffers (pinned audio in, log-probabilities fetched into pinned
     # memory, synchronised every step): the PCIe-inclusive rate.  Reported beside `value`, never as `value`.
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         try:
             est = Estimator(spec, state, device, args.precision)
             host_audio = audio.pin_memory()
@@ -735,9 +747,9 @@ def main():
             result["pcie_inclusive"] = {"error": repr(exc)}
     # the single-plane 16-bit throughput mode of the same workload (error measured and bounded in tests/, not a parity
     # mode): reported beside the parity-mode headline, never as `value`
-    if args.also and args.also != args.precision and world == 1:
+    if args.full and args.also and args.also != args.precision and world == 1:
         e2, t2 = measure(args.also, args.steps, args.warmup, local)
-        w2, roof2 = summarize(args.also, args.steps, t2, n_local)
+        roof2 = summarize(args.also, args.steps, t2, work(args.also, n_local))
         if rank == 0:
             result["throughput_mode"] = {
                 "dtype": args.also, "value": frames_global * args.steps / e2, "unit": "frames/s", "ms_per_step": e2 / args.steps * 1e3,
@@ -748,7 +760,7 @@ def main():
             }
     # N = 1: what a ragged batch gets (informational; `value` is the equal-length config above): the encoder layers run on the
     # valid frames only and the conv stack skips tiles that lie in padding, against the padded layout of the same batch
-    if world == 1 and not args.no_ragged and n_global > 1:
+    if args.full and world == 1 and not args.no_ragged and n_global > 1:
         try:
             g = torch.Generator().manual_seed(9)
             r_lengths = torch.randint(int(0.2 * length), length + 1, (n_global,), generator=g)
@@ -780,7 +792,9 @@ def main():
             }
         except Exception as exc:  # informational leg: never costs the headline
             result["ragged_batch"] = {"error": repr(exc)}
-    if rank == 0:
+    if rank == 0 and not args.full:
+        result["ok"] = None  # not checked: the parity spot check is a --full leg
+    elif rank == 0:
         # CPU baseline on the first `cpu_sample` utterances of the benchmark batch (N = 1 only), and -- AFTER every timed
         # region -- the parity spot check of the path that was timed: the outputs of one more `predict` of the benchmark batch
         # against the CPU oracle on those utterances (each result is independent of the batch it sits in: SURVEY.md Appendix

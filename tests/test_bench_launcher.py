@@ -53,6 +53,16 @@ def test_self_launch_relays_rank0_line(tmp_path):
     assert "chatter from rank" in done.stderr.decode()
 
 
+def test_full_reaches_the_ranks(tmp_path):
+    """`--full` (every leg beyond the headline) is an option of the launcher's parser and is handed to every rank."""
+    stub = tmp_path / "stub_rank.py"
+    stub.write_text(STUB)
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
+    done = _run(tmp_path, {"AMX_BENCH_CHILD_SCRIPT": str(stub)}, args)
+    assert done.returncode == 0, done.stderr.decode()[-2000:]
+    assert json.loads(done.stdout.decode())["argv"] == args
+
+
 def test_self_launch_reports_a_failing_rank(tmp_path):
     stub = tmp_path / "stub_rank.py"
     stub.write_text(STUB)

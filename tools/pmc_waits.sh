@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/waits_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_WAVES --kernel-trace --output-format csv -d "$OUT/pmc" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --also "" "$@" > "$OUT/bench.json" 2> "$OUT/pmc.err"
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_WAVES --kernel-trace --output-format csv -d "$OUT/pmc" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --also "" "$@" > "$OUT/bench.json" 2> "$OUT/pmc.err"
 python3 "$ROOT/tools/pmc_summary.py" "$OUT/pmc" "$OUT/summary.json" > "$OUT/summary.txt" 2>&1
 find "$OUT" -name "*kernel_trace.csv" -delete
 find "$OUT" -name "*counter_collection.csv" -delete
