@@ -121,19 +121,14 @@ struct amx_handle_s {
     };
     static constexpr int INV_CAP = 16;
     std::vector<Inventory> inventories;
-    int inv = -1;  // current entry, -1 = composition model without an inventory yet
+    int inv = -1;  // current entry (cur_inv), -1 = composition model without an inventory yet
     uint64_t inv_clock = 0;
-    int P1 = 0;    // of the current inventory
-    float r_composed = 1.f;
-    void* composed_w = nullptr;
-    float* composed_f32 = nullptr;
 
     // logits layout
     std::vector<int> col, width;  // per class
     int ld_logits = 0;
     std::vector<amx_output_desc> outputs;  // relative to N, T of the last layout computation
     std::vector<OutDesc> out_unique, out_all;
-    OutDesc *out_unique_dev = nullptr, *out_all_dev = nullptr;  // of the current inventory
     int layout_inv = -2;  // inventory slot the host-side layout was computed for ...
     uint64_t layout_gen = 0, inv_gen = 0;  // ... and the install generation of that slot: slots are reused after eviction
     int layout_N = -1;
@@ -346,41 +341,33 @@ static int install_inventory(amx_handle h, std::vector<int64_t>&& key, const std
 // =================================================================================================================
 // creation
 // =================================================================================================================
-static int upload_f32(amx_handle h, const TensorMap& tm, const std::string& key, int64_t numel, float** out, float scale = 1.f,
-                      float* staging = nullptr) {
+#define TRY(x) do { if (int rc_ = (x)) return rc_; } while (0)
+
+static int upload_f32(amx_handle h, const TensorMap& tm, const std::string& key, int64_t numel, float** out) {
     const amx_tensor* t = tm.get(key);
     if (!t) return fail(h, AMX_EINVAL, "missing tensor in state_dict: " + key);
     if (t->numel != numel)
         return fail(h, AMX_EINVAL, "tensor " + key + " has " + std::to_string(t->numel) + " elements, expected " + std::to_string(numel));
     float* d = (float*)dev_alloc(h, (size_t)numel * 4);
     if (!d) return fail(h, AMX_ENOMEM, "device allocation failed for " + key);
-    if (scale == 1.f) {
-        HIPCHK(h, hipMemcpy(d, t->data, (size_t)numel * 4, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(h, hipMemcpy(staging, t->data, (size_t)numel * 4, hipMemcpyHostToDevice));
-        launch_scale_copy(staging, d, numel, scale, 0);
-        HIPCHK(h, hipDeviceSynchronize());
-    }
+    HIPCHK(h, hipMemcpy(d, t->data, (size_t)numel * 4, hipMemcpyHostToDevice));
     *out = d;
     return AMX_OK;
 }
 
-// uploads a [rows, cols] fp32 matrix and packs it as planes at row offset `row0` of dst [*, ldd]
-static int pack_linear(amx_handle h, const TensorMap& tm, const std::string& key, int rows, int cols, float scale, void* dst,
-                       int64_t plane, int64_t ldd, int row0, int cols_pad, float* staging) {
-    const amx_tensor* t = tm.get(key);
-    if (!t) return fail(h, AMX_EINVAL, "missing tensor in state_dict: " + key);
-    if (t->numel != (int64_t)rows * cols)
-        return fail(h, AMX_EINVAL, "tensor " + key + " has " + std::to_string(t->numel) + " elements, expected " +
-                                       std::to_string((int64_t)rows * cols));
-    HIPCHK(h, hipMemcpy(staging, t->data, (size_t)t->numel * 4, hipMemcpyHostToDevice));
-    launch_pack_matrix(h->prec, staging, rows, cols, cols, 1, scale, (char*)dst + (size_t)row0 * ldd * 2 * (plane == PLANE_IL ? 2 : 1), plane, ldd,
-                       cols_pad, 0);
-    HIPCHK(h, hipDeviceSynchronize());
+// a weight buffer amx_create could not allocate or fill
+static int alloc_failed(amx_handle h) { return fail(h, AMX_ENOMEM, "device allocation failed"); }
+
+// a weight buffer of `bytes` holding a copy of host `src` (zeros when null)
+template <class T>
+static int dev_upload(amx_handle h, T** out, const void* src, size_t bytes) {
+    *out = (T*)dev_alloc(h, bytes);
+    if (!*out || (src ? hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice) : hipMemset(*out, 0, bytes)) != hipSuccess)
+        return alloc_failed(h);
     return AMX_OK;
 }
 
-// the same from host data (weights amx_create folds before packing)
+// uploads a [rows, cols] fp32 host matrix and packs it as planes at row offset `row0` of dst [*, ldd]
 static int pack_linear_host(amx_handle h, const float* data, int rows, int cols, float scale, void* dst, int64_t plane, int64_t ldd,
                             int row0, int cols_pad, float* staging) {
     HIPCHK(h, hipMemcpy(staging, data, (size_t)rows * cols * 4, hipMemcpyHostToDevice));
@@ -388,6 +375,17 @@ static int pack_linear_host(amx_handle h, const float* data, int rows, int cols,
                        cols_pad, 0);
     HIPCHK(h, hipDeviceSynchronize());
     return AMX_OK;
+}
+
+// the same for a tensor of the state_dict
+static int pack_linear(amx_handle h, const TensorMap& tm, const std::string& key, int rows, int cols, float scale, void* dst,
+                       int64_t plane, int64_t ldd, int row0, int cols_pad, float* staging) {
+    const amx_tensor* t = tm.get(key);
+    if (!t) return fail(h, AMX_EINVAL, "missing tensor in state_dict: " + key);
+    if (t->numel != (int64_t)rows * cols)
+        return fail(h, AMX_EINVAL, "tensor " + key + " has " + std::to_string(t->numel) + " elements, expected " +
+                                       std::to_string((int64_t)rows * cols));
+    return pack_linear_host(h, t->data, rows, cols, scale, dst, plane, ldd, row0, cols_pad, staging);
 }
 
 // LayerNorm(gamma, beta) folded into the Linear(W [rows, cols], b) behind it:  LN(x) W^T + b = rstd ((x - p) . (gamma (.) W)^T)
@@ -437,10 +435,9 @@ static void* alloc_planes(amx_handle h, int64_t elems_per_plane) {
     return dev_alloc(h, (size_t)elems_per_plane * 2 * h->NT + PLANE_SLACK);
 }
 
-extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, const amx_class_desc* classes, int n_classes,
-                          const amx_tensor* tensors, int n_tensors) {
-    if (!out || !cfg || !classes || !tensors) return fail(nullptr, AMX_EINVAL, "null argument");
-    *out = nullptr;
+// ---- amx_create, section by section (each returns an AMX_* code with the message set; amx_create destroys the handle) ----
+
+static int check_config(const amx_config* cfg, int n_classes) {
     if (cfg->abi_version != AMX_ABI_VERSION) return fail(nullptr, AMX_EINVAL, "ABI version mismatch");
     if (cfg->n_conv < 2 || cfg->n_conv > AMX_MAX_CONV) return fail(nullptr, AMX_EINVAL, "n_conv out of range");
     if (cfg->heads < 1 || cfg->hidden % cfg->heads != 0 || (cfg->hidden / cfg->heads) % 8 || cfg->hidden / cfg->heads > 128)
@@ -462,259 +459,208 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
         return fail(nullptr, AMX_EINVAL, "`feat_extract_norm` has to be one of ['group', 'layer']");
     if (cfg->embedding_size % 8) return fail(nullptr, AMX_EINVAL, "embedding_size must be a multiple of 8");
     if (n_classes < 1) return fail(nullptr, AMX_EINVAL, "Each model needs at least one classifier");
+    return AMX_OK;
+}
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(nullptr, AMX_EHIP, "no HIP device available: liballophant_amx has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(nullptr, AMX_EINVAL, "device index out of range");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
-
-    amx_handle h = new amx_handle_s();
-    h->device = device;
-    h->cfg = *cfg;
-    h->prec = cfg->precision;
-    h->NT = prec_planes(cfg->precision);
-    h->gn = cfg->feat_extract_norm == AMX_NORM_GROUP;
-    h->stable = cfg->stable_layer_norm != 0;
-    h->masked = cfg->use_attention_mask != 0;
-    // (hidden too -- round 6: the residual-stream planes [M, hidden] are GEMM operands like the others; a hidden size off the
-    // 32-element blocks -- 240 = 2 heads of 120 -- ran interleaved planes through kernels that assume block-aligned rows)
-    h->il = h->NT > 1 && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
-    h->classes.assign(classes, classes + n_classes);
-    auto bail = [&](int code) {
-        g_create_error = h->err;
-        amx_destroy(h);
-        return code;
-    };
-
-    // ---- validate the classifier graph (mirrors the ValueErrors of acoustic_model.py:353-466) ----
+// the classifier graph (mirrors the ValueErrors of acoustic_model.py:353-466) and its evaluation order
+static int check_classes(amx_handle h) {
+    const int n_classes = (int)h->classes.size();
     bool uses_output = false;
     for (int i = 0; i < n_classes; ++i) {
         const auto& c = h->classes[i];
         for (int j = 0; j < i; ++j)
-            if (!strncmp(c.name, h->classes[j].name, AMX_NAME_LEN)) { h->err = "Dependencies contain duplicate keys"; return bail(AMX_EINVAL); }
-        if (!strncmp(c.name, "OUTPUT", 6)) { h->err = "'OUTPUT' is a reserved keyword"; return bail(AMX_EINVAL); }
-        if (c.n_deps < 1 || c.n_deps > AMX_MAX_DEPS) { h->err = "Each class projection requires a dependency"; return bail(AMX_EINVAL); }
-        if (c.out_features < 1) { h->err = "classifier without outputs"; return bail(AMX_EINVAL); }
-        if (c.time_heads < 0 || (c.time_heads > 0 && c.out_features % c.time_heads)) {
-            h->err = "embed_dim must be divisible by num_heads";  // nn.MultiheadAttention's assertion
-            return bail(AMX_EINVAL);
-        }
-        if (c.time_heads > 0 && c.time_positional && (c.out_features & 1)) {
-            h->err = "sinusoidal position embeddings need an even number of classifier outputs";
-            return bail(AMX_EINVAL);
-        }
+            if (!strncmp(c.name, h->classes[j].name, AMX_NAME_LEN)) return fail(h, AMX_EINVAL, "Dependencies contain duplicate keys");
+        if (!strncmp(c.name, "OUTPUT", 6)) return fail(h, AMX_EINVAL, "'OUTPUT' is a reserved keyword");
+        if (c.n_deps < 1 || c.n_deps > AMX_MAX_DEPS) return fail(h, AMX_EINVAL, "Each class projection requires a dependency");
+        if (c.out_features < 1) return fail(h, AMX_EINVAL, "classifier without outputs");
+        if (c.time_heads < 0 || (c.time_heads > 0 && c.out_features % c.time_heads))
+            return fail(h, AMX_EINVAL, "embed_dim must be divisible by num_heads");  // nn.MultiheadAttention's assertion
+        if (c.time_heads > 0 && c.time_positional && (c.out_features & 1))
+            return fail(h, AMX_EINVAL, "sinusoidal position embeddings need an even number of classifier outputs");
         for (int d = 0; d < c.n_deps; ++d) {
             if (c.deps[d] < 0) {
                 uses_output = true;
-                if (c.deps[d] < -1 && -2 - c.deps[d] > cfg->layers) { h->err = "OUTPUT_i exceeds the number of encoder layers"; return bail(AMX_EINVAL); }
-            } else if (c.deps[d] >= n_classes) { h->err = "unknown dependency"; return bail(AMX_EINVAL); }
+                if (c.deps[d] < -1 && -2 - c.deps[d] > h->cfg.layers) return fail(h, AMX_EINVAL, "OUTPUT_i exceeds the number of encoder layers");
+            } else if (c.deps[d] >= n_classes) {
+                return fail(h, AMX_EINVAL, "unknown dependency");
+            }
         }
     }
-    if (!uses_output) { h->err = "At least one of the input layers requires 'OUTPUT' as a dependency"; return bail(AMX_EINVAL); }
-    {
-        int rc = evaluation_order(h->classes, h->order, h->err);
-        if (rc) return bail(rc);
-    }
+    if (!uses_output) return fail(h, AMX_EINVAL, "At least one of the input layers requires 'OUTPUT' as a dependency");
+    return evaluation_order(h->classes, h->order, h->err);
+}
 
-    TensorMap tm;
-    int64_t max_numel = 0;
-    for (int i = 0; i < n_tensors; ++i) {
-        tm.m[tensors[i].name] = &tensors[i];
-        max_numel = std::max(max_numel, tensors[i].numel);
-    }
-    // (the fused, LayerNorm-folded Q / K / V matrix is packed from one host buffer of 3 hidden^2 floats: larger than any single
-    // tensor when ffn < 3 hidden)
-    max_numel = std::max<int64_t>(max_numel, (int64_t)3 * cfg->hidden * cfg->hidden);
-    float* staging = nullptr;
-    if (hipMalloc(&staging, (size_t)max_numel * 4 + 16) != hipSuccess) { h->err = "staging allocation failed"; return bail(AMX_ENOMEM); }
-    struct StagingGuard {
-        float* p;
-        ~StagingGuard() { (void)hipFree(p); }
-    } guard{staging};
-
-    const int C = cfg->conv_dim, D = cfg->hidden, F = cfg->ffn;
-    const float eps = cfg->eps;
-    (void)eps;
-    int rc;
-#define TRY(x) do { rc = (x); if (rc) return bail(rc); } while (0)
-
-    // ---- feature extractor ----
-    {
-        std::string p = AM + "feature_extractor.conv_layers.0.";
-        TRY(upload_f32(h, tm, p + "conv.weight", (int64_t)C * cfg->conv_kernel[0], &h->c0_w));
-        int c_in = 1;
-        for (int i = 0; i < cfg->n_conv; ++i) {
-            p = AM + "feature_extractor.conv_layers." + std::to_string(i) + ".";
-            int k = cfg->conv_kernel[i];
-            if (cfg->conv_bias) {
-                TRY(upload_f32(h, tm, p + "conv.bias", C, &h->conv_b[i]));
-            } else {
-                // config.conv_bias = False (wav2vec2-base / -large): nn.Conv1d(bias=False) -- a zero bias for the kernels
-                h->conv_b[i] = (float*)dev_alloc(h, (size_t)C * 4);
-                if (!h->conv_b[i] || hipMemset(h->conv_b[i], 0, (size_t)C * 4) != hipSuccess) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-            }
-            // "layer": LayerNorm(C) behind every conv layer; "group": GroupNorm(C, C) behind layer 0 only -- the same key names
-            // (`layer_norm.{weight,bias}`, transformers Wav2Vec2GroupNormConvLayer / Wav2Vec2NoLayerNormConvLayer)
-            if (!h->gn || i == 0) {
-                TRY(upload_f32(h, tm, p + "layer_norm.weight", C, &h->conv_g[i]));
-                TRY(upload_f32(h, tm, p + "layer_norm.bias", C, &h->conv_be[i]));
-            }
-            if (i > 0) {
-                const amx_tensor* t = tm.get(p + "conv.weight");
-                if (!t || t->numel != (int64_t)C * c_in * k) { h->err = "missing or mis-shaped tensor " + p + "conv.weight"; return bail(AMX_EINVAL); }
-                int64_t plane = (int64_t)C * c_in * k;
-                h->conv_w[i] = alloc_planes(h, plane);
-                if (!h->conv_w[i]) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-                if (hipMemcpy(staging, t->data, (size_t)t->numel * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "H2D failed"; return bail(AMX_EHIP); }
-                const float ps = pack_scale({{t, 1.f}});
-                h->conv_r[i] = 1.f / ps;
-                launch_pack_conv_w(h->prec, staging, C, c_in, k, ps, h->conv_w[i], pln(h, plane), 0);
-                // layers the row-complete kernel may take (LayerNorm variant, conv_dim 512, k > 1 taps): a tap-minor copy too
-                const int tm_slice = h->NT == 2 ? 32 : 64;
-                if (!h->gn && i < cfg->n_conv - 1 && k > 1 && C == 512 && c_in % tm_slice == 0) {
-                    h->conv_w_tm[i] = alloc_planes(h, plane);
-                    if (!h->conv_w_tm[i]) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-                    launch_pack_conv_w(h->prec, staging, C, c_in, k, ps, h->conv_w_tm[i], pln(h, plane), 0, tm_slice);
-                    h->conv_tm_slice = tm_slice;
-                }
-                if (hipDeviceSynchronize() != hipSuccess) { h->err = "pack_conv_w failed"; return bail(AMX_EHIP); }
-            }
-            c_in = C;
+// the conv layers of the feature extractor, and the LayerNorm statistics table of conv layer 0 on the matrix pipe
+static int create_feature_extractor(amx_handle h, const TensorMap& tm, float* staging) {
+    const amx_config& cfg = h->cfg;
+    const int C = cfg.conv_dim;
+    const std::string p0 = AM + "feature_extractor.conv_layers.0.";
+    TRY(upload_f32(h, tm, p0 + "conv.weight", (int64_t)C * cfg.conv_kernel[0], &h->c0_w));
+    int c_in = 1;
+    for (int i = 0; i < cfg.n_conv; ++i) {
+        const std::string p = AM + "feature_extractor.conv_layers." + std::to_string(i) + ".";
+        const int k = cfg.conv_kernel[i];
+        if (cfg.conv_bias) {
+            TRY(upload_f32(h, tm, p + "conv.bias", C, &h->conv_b[i]));
+        } else {
+            // config.conv_bias = False (wav2vec2-base / -large): nn.Conv1d(bias=False) -- a zero bias for the kernels
+            TRY(dev_upload(h, &h->conv_b[i], nullptr, (size_t)C * 4));
         }
-        // conv layer 0 on the matrix pipe (LayerNorm variant, k = 10, C = 512): the LayerNorm statistics of a frame are a linear
-        // and a quadratic form of its 10 samples -- mean_c(w_c . x + b_c) = m . [x; 1], var_c = [x; 1]^T G [x; 1] with m / G the mean
-        // / covariance of the rows [w_c, b_c] over the channels -- tabulated here in fp64
-        if (conv0_mfma_eligible(C, cfg->conv_kernel[0], cfg->conv_stride[0]))
-            h->c0_wscale = pack_scale({{tm.get(AM + "feature_extractor.conv_layers.0.conv.weight"), 1.f}});
-        if (!h->gn && conv0_mfma_eligible(C, cfg->conv_kernel[0], cfg->conv_stride[0])) {
-            const amx_tensor* wt = tm.get(AM + "feature_extractor.conv_layers.0.conv.weight");
-            const amx_tensor* bt = cfg->conv_bias ? tm.get(AM + "feature_extractor.conv_layers.0.conv.bias") : nullptr;
-            const int k0 = cfg->conv_kernel[0], dim = k0 + 1;
-            std::vector<double> table((size_t)dim + (size_t)dim * dim, 0.0), row(dim);
-            for (int ch = 0; ch < C; ++ch)
-                for (int j = 0; j < dim; ++j) table[j] += (j < k0 ? (double)wt->data[(size_t)ch * k0 + j] : (bt ? (double)bt->data[ch] : 0.0)) / C;
-            for (int ch = 0; ch < C; ++ch) {
-                for (int j = 0; j < dim; ++j) row[j] = (j < k0 ? (double)wt->data[(size_t)ch * k0 + j] : (bt ? (double)bt->data[ch] : 0.0)) - table[j];
-                for (int a = 0; a < dim; ++a)
-                    for (int b2 = 0; b2 < dim; ++b2) table[(size_t)dim + (size_t)a * dim + b2] += row[a] * row[b2] / C;
-            }
-            h->c0_stats = (double*)dev_alloc(h, table.size() * 8);
-            if (!h->c0_stats || hipMemcpy(h->c0_stats, table.data(), table.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-                h->err = "device allocation failed";
-                return bail(AMX_ENOMEM);
-            }
-            h->c0_wscale = pack_scale({{wt, 1.f}});
+        // "layer": LayerNorm(C) behind every conv layer; "group": GroupNorm(C, C) behind layer 0 only -- the same key names
+        // (`layer_norm.{weight,bias}`, transformers Wav2Vec2GroupNormConvLayer / Wav2Vec2NoLayerNormConvLayer)
+        if (!h->gn || i == 0) {
+            TRY(upload_f32(h, tm, p + "layer_norm.weight", C, &h->conv_g[i]));
+            TRY(upload_f32(h, tm, p + "layer_norm.bias", C, &h->conv_be[i]));
         }
+        if (i > 0) {
+            const amx_tensor* t = tm.get(p + "conv.weight");
+            if (!t || t->numel != (int64_t)C * c_in * k) return fail(h, AMX_EINVAL, "missing or mis-shaped tensor " + p + "conv.weight");
+            int64_t plane = (int64_t)C * c_in * k;
+            h->conv_w[i] = alloc_planes(h, plane);
+            if (!h->conv_w[i]) return alloc_failed(h);
+            if (hipMemcpy(staging, t->data, (size_t)t->numel * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(h, AMX_EHIP, "H2D failed");
+            const float ps = pack_scale({{t, 1.f}});
+            h->conv_r[i] = 1.f / ps;
+            launch_pack_conv_w(h->prec, staging, C, c_in, k, ps, h->conv_w[i], pln(h, plane), 0);
+            // layers the row-complete kernel may take (LayerNorm variant, conv_dim 512, k > 1 taps): a tap-minor copy too
+            const int tm_slice = h->NT == 2 ? 32 : 64;
+            if (!h->gn && i < cfg.n_conv - 1 && k > 1 && C == 512 && c_in % tm_slice == 0) {
+                h->conv_w_tm[i] = alloc_planes(h, plane);
+                if (!h->conv_w_tm[i]) return alloc_failed(h);
+                launch_pack_conv_w(h->prec, staging, C, c_in, k, ps, h->conv_w_tm[i], pln(h, plane), 0, tm_slice);
+                h->conv_tm_slice = tm_slice;
+            }
+            if (hipDeviceSynchronize() != hipSuccess) return fail(h, AMX_EHIP, "pack_conv_w failed");
+        }
+        c_in = C;
     }
-    // ---- feature projection ----
+    if (!conv0_mfma_eligible(C, cfg.conv_kernel[0], cfg.conv_stride[0])) return AMX_OK;
+    const amx_tensor* wt = tm.get(p0 + "conv.weight");
+    h->c0_wscale = pack_scale({{wt, 1.f}});
+    if (h->gn) return AMX_OK;
+    // conv layer 0 on the matrix pipe (LayerNorm variant, k = 10, C = 512): the LayerNorm statistics of a frame are a linear
+    // and a quadratic form of its 10 samples -- mean_c(w_c . x + b_c) = m . [x; 1], var_c = [x; 1]^T G [x; 1] with m / G the mean
+    // / covariance of the rows [w_c, b_c] over the channels -- tabulated here in fp64
+    const amx_tensor* bt = cfg.conv_bias ? tm.get(p0 + "conv.bias") : nullptr;
+    const int k0 = cfg.conv_kernel[0], dim = k0 + 1;
+    std::vector<double> table((size_t)dim + (size_t)dim * dim, 0.0), row(dim);
+    for (int ch = 0; ch < C; ++ch)
+        for (int j = 0; j < dim; ++j) table[j] += (j < k0 ? (double)wt->data[(size_t)ch * k0 + j] : (bt ? (double)bt->data[ch] : 0.0)) / C;
+    for (int ch = 0; ch < C; ++ch) {
+        for (int j = 0; j < dim; ++j) row[j] = (j < k0 ? (double)wt->data[(size_t)ch * k0 + j] : (bt ? (double)bt->data[ch] : 0.0)) - table[j];
+        for (int a = 0; a < dim; ++a)
+            for (int b2 = 0; b2 < dim; ++b2) table[(size_t)dim + (size_t)a * dim + b2] += row[a] * row[b2] / C;
+    }
+    return dev_upload(h, &h->c0_stats, table.data(), table.size() * 8);
+}
+
+// the feature projection and the positional conv (weight-norm folded)
+static int create_projection(amx_handle h, const TensorMap& tm, float* staging) {
+    const amx_config& cfg = h->cfg;
+    const int C = cfg.conv_dim, D = cfg.hidden;
     {
         std::string p = AM + "feature_projection.";
         TRY(upload_f32(h, tm, p + "layer_norm.weight", C, &h->fp_g));
         TRY(upload_f32(h, tm, p + "layer_norm.bias", C, &h->fp_b));
         TRY(upload_f32(h, tm, p + "projection.bias", D, &h->fp_bias));
         h->fp_w = alloc_planes(h, (int64_t)D * C);
-        if (!h->fp_w) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
+        if (!h->fp_w) return alloc_failed(h);
         const float ps = pack_scale({{tm.get(p + "projection.weight"), 1.f}});
         h->fp_r = 1.f / ps;
         TRY(pack_linear(h, tm, p + "projection.weight", D, C, ps, h->fp_w, pln(h, (int64_t)D * C), C, 0, C, staging));
     }
-    // ---- positional conv (weight-norm folded) ----
-    {
-        std::string p = AM + "encoder.pos_conv_embed.conv.";
-        const int cg = D / cfg->pos_groups, k = cfg->pos_kernel;
-        const amx_tensor* g = tm.get(p + "parametrizations.weight.original0");
-        const amx_tensor* v = tm.get(p + "parametrizations.weight.original1");
-        if (!g) g = tm.get(p + "weight_g");
-        if (!v) v = tm.get(p + "weight_v");
-        if (!g || !v || g->numel != k || v->numel != (int64_t)D * cg * k) { h->err = "missing or mis-shaped positional conv weights"; return bail(AMX_EINVAL); }
-        TRY(upload_f32(h, tm, p + "bias", D, &h->pos_b));
-        float* gd = (float*)dev_alloc(h, (size_t)k * 4 * 2);
-        if (!gd) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-        if (hipMemcpy(gd, g->data, (size_t)k * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(staging, v->data, (size_t)v->numel * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "H2D failed"; return bail(AMX_EHIP); }
-        int64_t plane = (int64_t)D * cg * k;
-        h->pos_w = alloc_planes(h, plane);
-        if (!h->pos_w) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-        float ps = 1.f;
-        {   // largest folded weight |v * g[tap] / ||v[:, :, tap]|||, on the host (the device folds them while packing)
-            std::vector<double> sq(k, 0.0);
-            std::vector<float> mx(k, 0.f);
-            const int64_t rows = (int64_t)D * cg;
-            for (int64_t r = 0; r < rows; ++r)
-                for (int tap = 0; tap < k; ++tap) {
-                    const float x = v->data[r * k + tap];
-                    sq[tap] += (double)x * x;
-                    mx[tap] = std::max(mx[tap], std::fabs(x));
-                }
-            float m = 0.f;
-            for (int tap = 0; tap < k; ++tap)
-                if (sq[tap] > 0.0) m = std::max(m, (float)(mx[tap] * std::fabs(g->data[tap]) / std::sqrt(sq[tap])));
-            ps = pow2_for(m);
-        }
-        h->pos_r = 1.f / ps;
-        launch_pack_posconv_w(h->prec, gd, staging, D, cg, k, ps, gd + k, h->pos_w, plane, 0);
-        if (hipDeviceSynchronize() != hipSuccess) { h->err = "pack_posconv_w failed"; return bail(AMX_EHIP); }
-    }
-    // ---- encoder layers ----
-    h->layers.resize(cfg->layers);
-    // folded into W_q / b_q: dh^-0.5 and log2(e) -- the attention softmax runs in base 2 (v_exp_f32)
-    const float qscale = 1.44269504088896340736f / sqrtf((float)(D / cfg->heads));
-    for (int l = 0; l < cfg->layers; ++l) {
-        Layer& ly = h->layers[l];
-        std::string p = AM + "encoder.layers." + std::to_string(l) + ".";
-        TRY(upload_f32(h, tm, p + "layer_norm.weight", D, &ly.ln1_g));
-        TRY(upload_f32(h, tm, p + "layer_norm.bias", D, &ly.ln1_b));
-        TRY(upload_f32(h, tm, p + "final_layer_norm.weight", D, &ly.ln2_g));
-        TRY(upload_f32(h, tm, p + "final_layer_norm.bias", D, &ly.ln2_b));
-        ly.wqkv = alloc_planes(h, (int64_t)3 * D * D);
-        ly.wo = alloc_planes(h, (int64_t)D * D);
-        ly.w1 = alloc_planes(h, (int64_t)F * D);
-        ly.w2 = alloc_planes(h, (int64_t)D * F);
-        ly.bqkv = (float*)dev_alloc(h, (size_t)3 * D * 4);
-        if (!ly.wqkv || !ly.wo || !ly.w1 || !ly.w2 || !ly.bqkv) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-        const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-        if (h->stable) {
-            // pre-LN layer: `layer_norm` folded into Q / K / V, `final_layer_norm` into FFN1 (see fold_layer_norm)
-            const amx_tensor *g1 = tm.get(p + "layer_norm.weight"), *be1 = tm.get(p + "layer_norm.bias");
-            const amx_tensor *g2 = tm.get(p + "final_layer_norm.weight"), *be2 = tm.get(p + "final_layer_norm.bias");
-            std::vector<float> folded((size_t)std::max(3 * D, F) * D), cvec(std::max(3 * D, F)), dvec(std::max(3 * D, F));
-            for (int j = 0; j < 3; ++j) {
-                const amx_tensor* w = tm.get(p + "attention." + names[j] + ".weight");
-                const amx_tensor* b = tm.get(p + "attention." + names[j] + ".bias");
-                if (!w || w->numel != (int64_t)D * D || !b || b->numel != D) { h->err = "missing or mis-shaped tensor " + p + "attention." + names[j]; return bail(AMX_EINVAL); }
-                fold_layer_norm(w->data, b->data, g1->data, be1->data, D, D, j == 0 ? qscale : 1.f, folded.data() + (size_t)j * D * D,
-                                cvec.data() + j * D, dvec.data() + j * D);
+    std::string p = AM + "encoder.pos_conv_embed.conv.";
+    const int cg = D / cfg.pos_groups, k = cfg.pos_kernel;
+    const amx_tensor* g = tm.get(p + "parametrizations.weight.original0");
+    const amx_tensor* v = tm.get(p + "parametrizations.weight.original1");
+    if (!g) g = tm.get(p + "weight_g");
+    if (!v) v = tm.get(p + "weight_v");
+    if (!g || !v || g->numel != k || v->numel != (int64_t)D * cg * k) return fail(h, AMX_EINVAL, "missing or mis-shaped positional conv weights");
+    TRY(upload_f32(h, tm, p + "bias", D, &h->pos_b));
+    float* gd = (float*)dev_alloc(h, (size_t)k * 4 * 2);
+    if (!gd) return alloc_failed(h);
+    if (hipMemcpy(gd, g->data, (size_t)k * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(staging, v->data, (size_t)v->numel * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(h, AMX_EHIP, "H2D failed");
+    int64_t plane = (int64_t)D * cg * k;
+    h->pos_w = alloc_planes(h, plane);
+    if (!h->pos_w) return alloc_failed(h);
+    float ps = 1.f;
+    {   // largest folded weight |v * g[tap] / ||v[:, :, tap]|||, on the host (the device folds them while packing)
+        std::vector<double> sq(k, 0.0);
+        std::vector<float> mx(k, 0.f);
+        const int64_t rows = (int64_t)D * cg;
+        for (int64_t r = 0; r < rows; ++r)
+            for (int tap = 0; tap < k; ++tap) {
+                const float x = v->data[r * k + tap];
+                sq[tap] += (double)x * x;
+                mx[tap] = std::max(mx[tap], std::fabs(x));
             }
-            amx_tensor ft{};
-            ft.data = folded.data(); ft.numel = (int64_t)3 * D * D;
-            const float ps_qkv = pack_scale({{&ft, 1.f}});
-            ly.r_qkv = 1.f / ps_qkv;
-            TRY(pack_linear_host(h, folded.data(), 3 * D, D, ps_qkv, ly.wqkv, pln(h, (int64_t)3 * D * D), D, 0, D, staging));
-            ly.c_qkv = (float*)dev_alloc(h, (size_t)3 * D * 4);
-            if (!ly.c_qkv || hipMemcpy(ly.c_qkv, cvec.data(), (size_t)3 * D * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(ly.bqkv, dvec.data(), (size_t)3 * D * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-            const amx_tensor* w1 = tm.get(p + "feed_forward.intermediate_dense.weight");
-            const amx_tensor* b1 = tm.get(p + "feed_forward.intermediate_dense.bias");
-            if (!w1 || w1->numel != (int64_t)F * D || !b1 || b1->numel != F) { h->err = "missing or mis-shaped tensor " + p + "feed_forward.intermediate_dense"; return bail(AMX_EINVAL); }
-            fold_layer_norm(w1->data, b1->data, g2->data, be2->data, F, D, 1.f, folded.data(), cvec.data(), dvec.data());
-            ft.numel = (int64_t)F * D;
-            const float ps_1 = pack_scale({{&ft, 1.f}});
-            ly.r_1 = 1.f / ps_1;
-            TRY(pack_linear_host(h, folded.data(), F, D, ps_1, ly.w1, pln(h, (int64_t)F * D), D, 0, D, staging));
-            ly.c_1 = (float*)dev_alloc(h, (size_t)F * 4);
-            ly.b1 = (float*)dev_alloc(h, (size_t)F * 4);
-            if (!ly.c_1 || !ly.b1 || hipMemcpy(ly.c_1, cvec.data(), (size_t)F * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(ly.b1, dvec.data(), (size_t)F * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-            const float ps_o = pack_scale({{tm.get(p + "attention.out_proj.weight"), 1.f}});
-            const float ps_2 = pack_scale({{tm.get(p + "feed_forward.output_dense.weight"), 1.f}});
-            ly.r_o = 1.f / ps_o; ly.r_2 = 1.f / ps_2;
-            TRY(pack_linear(h, tm, p + "attention.out_proj.weight", D, D, ps_o, ly.wo, pln(h, (int64_t)D * D), D, 0, D, staging));
-            TRY(upload_f32(h, tm, p + "attention.out_proj.bias", D, &ly.bo));
-            TRY(pack_linear(h, tm, p + "feed_forward.output_dense.weight", D, F, ps_2, ly.w2, pln(h, (int64_t)D * F), F, 0, F, staging));
-            TRY(upload_f32(h, tm, p + "feed_forward.output_dense.bias", D, &ly.b2));
-            continue;
+        float m = 0.f;
+        for (int tap = 0; tap < k; ++tap)
+            if (sq[tap] > 0.0) m = std::max(m, (float)(mx[tap] * std::fabs(g->data[tap]) / std::sqrt(sq[tap])));
+        ps = pow2_for(m);
+    }
+    h->pos_r = 1.f / ps;
+    launch_pack_posconv_w(h->prec, gd, staging, D, cg, k, ps, gd + k, h->pos_w, plane, 0);
+    if (hipDeviceSynchronize() != hipSuccess) return fail(h, AMX_EHIP, "pack_posconv_w failed");
+    return AMX_OK;
+}
+
+// encoder layer l: Q / K / V as one product, the out-projection, the FFN
+static int create_layer(amx_handle h, const TensorMap& tm, int l, float* staging) {
+    const int D = h->cfg.hidden, F = h->cfg.ffn;
+    // folded into W_q / b_q: dh^-0.5 and log2(e) -- the attention softmax runs in base 2 (v_exp_f32)
+    const float qscale = 1.44269504088896340736f / sqrtf((float)(D / h->cfg.heads));
+    Layer& ly = h->layers[l];
+    const std::string p = AM + "encoder.layers." + std::to_string(l) + ".";
+    TRY(upload_f32(h, tm, p + "layer_norm.weight", D, &ly.ln1_g));
+    TRY(upload_f32(h, tm, p + "layer_norm.bias", D, &ly.ln1_b));
+    TRY(upload_f32(h, tm, p + "final_layer_norm.weight", D, &ly.ln2_g));
+    TRY(upload_f32(h, tm, p + "final_layer_norm.bias", D, &ly.ln2_b));
+    ly.wqkv = alloc_planes(h, (int64_t)3 * D * D);
+    ly.wo = alloc_planes(h, (int64_t)D * D);
+    ly.w1 = alloc_planes(h, (int64_t)F * D);
+    ly.w2 = alloc_planes(h, (int64_t)D * F);
+    ly.bqkv = (float*)dev_alloc(h, (size_t)3 * D * 4);
+    if (!ly.wqkv || !ly.wo || !ly.w1 || !ly.w2 || !ly.bqkv) return alloc_failed(h);
+    // a Linear [rows, cols] as it is: weight planes under their own power of two, fp32 bias
+    auto linear = [&](const std::string& name, int rows, int cols, void* w, float& r, float** b) {
+        const float ps = pack_scale({{tm.get(p + name + ".weight"), 1.f}});
+        r = 1.f / ps;
+        TRY(pack_linear(h, tm, p + name + ".weight", rows, cols, ps, w, pln(h, (int64_t)rows * cols), cols, 0, cols, staging));
+        return upload_f32(h, tm, p + name + ".bias", rows, b);
+    };
+    const char* names[3] = {"q_proj", "k_proj", "v_proj"};
+    if (h->stable) {
+        // pre-LN layer: `layer_norm` folded into Q / K / V, `final_layer_norm` into FFN1 (see fold_layer_norm)
+        const amx_tensor *g1 = tm.get(p + "layer_norm.weight"), *be1 = tm.get(p + "layer_norm.bias");
+        const amx_tensor *g2 = tm.get(p + "final_layer_norm.weight"), *be2 = tm.get(p + "final_layer_norm.bias");
+        std::vector<float> folded((size_t)std::max(3 * D, F) * D), cvec(std::max(3 * D, F)), dvec(std::max(3 * D, F));
+        for (int j = 0; j < 3; ++j) {
+            const amx_tensor* w = tm.get(p + "attention." + names[j] + ".weight");
+            const amx_tensor* b = tm.get(p + "attention." + names[j] + ".bias");
+            if (!w || w->numel != (int64_t)D * D || !b || b->numel != D) return fail(h, AMX_EINVAL, "missing or mis-shaped tensor " + p + "attention." + names[j]);
+            fold_layer_norm(w->data, b->data, g1->data, be1->data, D, D, j == 0 ? qscale : 1.f, folded.data() + (size_t)j * D * D,
+                            cvec.data() + j * D, dvec.data() + j * D);
         }
+        amx_tensor ft{};
+        ft.data = folded.data(); ft.numel = (int64_t)3 * D * D;
+        const float ps_qkv = pack_scale({{&ft, 1.f}});
+        ly.r_qkv = 1.f / ps_qkv;
+        TRY(pack_linear_host(h, folded.data(), 3 * D, D, ps_qkv, ly.wqkv, pln(h, (int64_t)3 * D * D), D, 0, D, staging));
+        TRY(dev_upload(h, &ly.c_qkv, cvec.data(), (size_t)3 * D * 4));
+        if (hipMemcpy(ly.bqkv, dvec.data(), (size_t)3 * D * 4, hipMemcpyHostToDevice) != hipSuccess) return alloc_failed(h);
+        const amx_tensor* w1 = tm.get(p + "feed_forward.intermediate_dense.weight");
+        const amx_tensor* b1 = tm.get(p + "feed_forward.intermediate_dense.bias");
+        if (!w1 || w1->numel != (int64_t)F * D || !b1 || b1->numel != F) return fail(h, AMX_EINVAL, "missing or mis-shaped tensor " + p + "feed_forward.intermediate_dense");
+        fold_layer_norm(w1->data, b1->data, g2->data, be2->data, F, D, 1.f, folded.data(), cvec.data(), dvec.data());
+        ft.numel = (int64_t)F * D;
+        const float ps_1 = pack_scale({{&ft, 1.f}});
+        ly.r_1 = 1.f / ps_1;
+        TRY(pack_linear_host(h, folded.data(), F, D, ps_1, ly.w1, pln(h, (int64_t)F * D), D, 0, D, staging));
+        TRY(dev_upload(h, &ly.c_1, cvec.data(), (size_t)F * 4));
+        TRY(dev_upload(h, &ly.b1, dvec.data(), (size_t)F * 4));
+    } else {
         const float ps_qkv = pack_scale({{tm.get(p + "attention.q_proj.weight"), qscale}, {tm.get(p + "attention.k_proj.weight"), 1.f},
                                          {tm.get(p + "attention.v_proj.weight"), 1.f}});
         ly.r_qkv = 1.f / ps_qkv;
@@ -722,45 +668,33 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
             float sc = j == 0 ? qscale : 1.f;
             TRY(pack_linear(h, tm, p + "attention." + names[j] + ".weight", D, D, sc * ps_qkv, ly.wqkv, pln(h, (int64_t)3 * D * D), D, j * D, D, staging));
             const amx_tensor* b = tm.get(p + "attention." + names[j] + ".bias");
-            if (!b || b->numel != D) { h->err = "missing tensor " + p + "attention." + names[j] + ".bias"; return bail(AMX_EINVAL); }
-            if (hipMemcpy(staging, b->data, (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "H2D failed"; return bail(AMX_EHIP); }
+            if (!b || b->numel != D) return fail(h, AMX_EINVAL, "missing tensor " + p + "attention." + names[j] + ".bias");
+            if (hipMemcpy(staging, b->data, (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(h, AMX_EHIP, "H2D failed");
             launch_scale_copy(staging, ly.bqkv + j * D, D, sc, 0);
-            if (hipDeviceSynchronize() != hipSuccess) { h->err = "scale_copy failed"; return bail(AMX_EHIP); }
+            if (hipDeviceSynchronize() != hipSuccess) return fail(h, AMX_EHIP, "scale_copy failed");
         }
-        const float ps_o = pack_scale({{tm.get(p + "attention.out_proj.weight"), 1.f}});
-        const float ps_1 = pack_scale({{tm.get(p + "feed_forward.intermediate_dense.weight"), 1.f}});
-        const float ps_2 = pack_scale({{tm.get(p + "feed_forward.output_dense.weight"), 1.f}});
-        ly.r_o = 1.f / ps_o; ly.r_1 = 1.f / ps_1; ly.r_2 = 1.f / ps_2;
-        TRY(pack_linear(h, tm, p + "attention.out_proj.weight", D, D, ps_o, ly.wo, pln(h, (int64_t)D * D), D, 0, D, staging));
-        TRY(upload_f32(h, tm, p + "attention.out_proj.bias", D, &ly.bo));
-        TRY(pack_linear(h, tm, p + "feed_forward.intermediate_dense.weight", F, D, ps_1, ly.w1, pln(h, (int64_t)F * D), D, 0, D, staging));
-        TRY(upload_f32(h, tm, p + "feed_forward.intermediate_dense.bias", F, &ly.b1));
-        TRY(pack_linear(h, tm, p + "feed_forward.output_dense.weight", D, F, ps_2, ly.w2, pln(h, (int64_t)D * F), F, 0, F, staging));
-        TRY(upload_f32(h, tm, p + "feed_forward.output_dense.bias", D, &ly.b2));
     }
-    {   // the affine part of a folded LayerNorm lives in the weights: its row pass (short batches) normalises with (1, 0)
-        std::vector<float> ones(D, 1.f);
-        h->unit_g = (float*)dev_alloc(h, (size_t)D * 4);
-        h->zero_b = (float*)dev_alloc(h, (size_t)D * 4);
-        if (!h->unit_g || !h->zero_b || hipMemcpy(h->unit_g, ones.data(), (size_t)D * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(h->zero_b, 0, (size_t)D * 4) != hipSuccess) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-    }
-    TRY(upload_f32(h, tm, AM + "encoder.layer_norm.weight", D, &h->fln_g));
-    TRY(upload_f32(h, tm, AM + "encoder.layer_norm.bias", D, &h->fln_b));
+    TRY(linear("attention.out_proj", D, D, ly.wo, ly.r_o, &ly.bo));
+    if (!h->stable) TRY(linear("feed_forward.intermediate_dense", F, D, ly.w1, ly.r_1, &ly.b1));
+    return linear("feed_forward.output_dense", D, F, ly.w2, ly.r_2, &ly.b2);
+}
 
-    // ---- hierarchical projection plan ----
-    h->need_hidden.assign(cfg->layers + 1, false);
-    const bool blanks = cfg->dependency_blanks != 0;
+// the hierarchical projection: one HeadStep per classifier in evaluation order (direct-output classifiers stacked), then their
+// weights packed
+static int create_heads(amx_handle h, const TensorMap& tm, float* staging) {
+    const amx_config& cfg = h->cfg;
+    h->need_hidden.assign(cfg.layers + 1, false);
+    const bool blanks = cfg.dependency_blanks != 0;
     auto dep_width = [&](int dep) -> int {
-        if (dep < 0) return D;
+        if (dep < 0) return cfg.hidden;
         return h->classes[dep].size + (blanks ? 1 : 0);
     };
     for (size_t oi = 0; oi < h->order.size(); ++oi) {
         int ci = h->order[oi];
         const amx_class_desc& c = h->classes[ci];
-        bool composed = cfg->embedding_size > 0 && !strcmp(c.name, "phoneme");
+        bool composed = cfg.embedding_size > 0 && !strcmp(c.name, "phoneme");
         if (composed) {
-            if (c.out_features != cfg->embedding_size) { h->err = "phoneme out_features must equal embedding_size"; return bail(AMX_EINVAL); }
+            if (c.out_features != cfg.embedding_size) return fail(h, AMX_EINVAL, "phoneme out_features must equal embedding_size");
             h->composed_class = ci;
         }
         bool direct = c.n_deps == 1 && c.deps[0] == AMX_DEP_OUTPUT;
@@ -806,7 +740,7 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
     for (auto& st : h->steps) {
         st.W = alloc_planes(h, (int64_t)st.rows * st.Kpad);
         st.bias = (float*)dev_alloc(h, (size_t)st.rows * 4);
-        if (!st.W || !st.bias) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
+        if (!st.W || !st.bias) return alloc_failed(h);
         int row0 = 0;
         float ps_w = 1.f;
         {   // one scale for the stacked rows of the step
@@ -828,7 +762,7 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
                 const int64_t plane_in = (int64_t)3 * Co * st.Cpad, plane_out = (int64_t)Co * st.Cpad;
                 st.tl_win = alloc_planes(h, plane_in);
                 st.tl_wout = alloc_planes(h, plane_out);
-                if (!st.tl_win || !st.tl_wout) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
+                if (!st.tl_win || !st.tl_wout) return alloc_failed(h);
                 const float ps_in = pack_scale({{tm.get(p + "attention.in_proj_weight"), 1.f}});
                 const float ps_out = pack_scale({{tm.get(p + "attention.out_proj.weight"), 1.f}});
                 st.r_tin = 1.f / ps_in; st.r_tout = 1.f / ps_out;
@@ -849,39 +783,102 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
                         base[col] = (float)std::exp((double)arg);
                     }
                     st.tl_pe = (float*)dev_alloc(h, (size_t)Co * 4);
-                    if (!st.tl_pe) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-                    if (hipMemcpy(st.tl_pe, base.data(), (size_t)Co * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "H2D failed"; return bail(AMX_EHIP); }
+                    if (!st.tl_pe) return alloc_failed(h);
+                    if (hipMemcpy(st.tl_pe, base.data(), (size_t)Co * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(h, AMX_EHIP, "H2D failed");
                 }
                 p += "input_projection.";
             }
             TRY(pack_linear(h, tm, p + "weight", c.out_features, st.K, ps_w, st.W, pln(h, (int64_t)st.rows * st.Kpad), st.Kpad, row0, st.Kpad, staging));
             const amx_tensor* b = tm.get(p + "bias");
-            if (!b || b->numel != c.out_features) { h->err = "missing tensor " + p + "bias"; return bail(AMX_EINVAL); }
-            if (hipMemcpy(st.bias + row0, b->data, (size_t)c.out_features * 4, hipMemcpyHostToDevice) != hipSuccess) { h->err = "H2D failed"; return bail(AMX_EHIP); }
+            if (!b || b->numel != c.out_features) return fail(h, AMX_EINVAL, "missing tensor " + p + "bias");
+            if (hipMemcpy(st.bias + row0, b->data, (size_t)c.out_features * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(h, AMX_EHIP, "H2D failed");
             row0 += c.out_features;
         }
         if (!st.parts.empty()) {
             st.parts_dev = (ConcatPart*)dev_alloc(h, st.parts.size() * sizeof(ConcatPart));
-            if (!st.parts_dev) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
+            if (!st.parts_dev) return alloc_failed(h);
         }
     }
-    if (h->composed_class >= 0) {
-        std::string key = PROJ + "phoneme._composition_layer._attribute_embeddings.weight";
-        const amx_tensor* t = tm.get(key);
-        if (!t || t->numel % cfg->embedding_size) { h->err = "missing tensor " + key; return bail(AMX_EINVAL); }
-        h->emb_rows = (int)(t->numel / cfg->embedding_size);
-        h->emb_host.assign(t->data, t->data + t->numel);
-        TRY(upload_f32(h, tm, key, t->numel, &h->emb));
-    }
+    return AMX_OK;
+}
+
+// the composition embedding table (kept on the host too: install_inventory scales each composed matrix from it)
+static int create_composition(amx_handle h, const TensorMap& tm) {
+    const std::string key = PROJ + "phoneme._composition_layer._attribute_embeddings.weight";
+    const amx_tensor* t = tm.get(key);
+    if (!t || t->numel % h->cfg.embedding_size) return fail(h, AMX_EINVAL, "missing tensor " + key);
+    h->emb_rows = (int)(t->numel / h->cfg.embedding_size);
+    h->emb_host.assign(t->data, t->data + t->numel);
+    return upload_f32(h, tm, key, t->numel, &h->emb);
+}
 #undef TRY
-    h->nonfinite = (int*)dev_alloc(h, 16);
-    if (!h->nonfinite || hipMemset(h->nonfinite, 0, 16) != hipSuccess) { h->err = "device allocation failed"; return bail(AMX_ENOMEM); }
-    if (h->composed_class < 0) {
-        // no composition layer: one implicit inventory (fixed output widths)
-        int rc2 = install_inventory(h, std::vector<int64_t>{}, std::vector<int64_t>{}, 0, 0, 0);
-        if (rc2) return bail(rc2);
+
+extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, const amx_class_desc* classes, int n_classes,
+                          const amx_tensor* tensors, int n_tensors) {
+    if (!out || !cfg || !classes || !tensors) return fail(nullptr, AMX_EINVAL, "null argument");
+    *out = nullptr;
+    if (int rc = check_config(cfg, n_classes)) return rc;
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(nullptr, AMX_EHIP, "no HIP device available: liballophant_amx has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(nullptr, AMX_EINVAL, "device index out of range");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+
+    amx_handle h = new amx_handle_s();
+    h->device = device;
+    h->cfg = *cfg;
+    h->prec = cfg->precision;
+    h->NT = prec_planes(cfg->precision);
+    h->gn = cfg->feat_extract_norm == AMX_NORM_GROUP;
+    h->stable = cfg->stable_layer_norm != 0;
+    h->masked = cfg->use_attention_mask != 0;
+    // (hidden too -- round 6: the residual-stream planes [M, hidden] are GEMM operands like the others; a hidden size off the
+    // 32-element blocks -- 240 = 2 heads of 120 -- ran interleaved planes through kernels that assume block-aligned rows)
+    h->il = h->NT > 1 && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
+    h->classes.assign(classes, classes + n_classes);
+    auto bail = [&](int code) {
+        g_create_error = h->err;
+        amx_destroy(h);
+        return code;
+    };
+    int rc = check_classes(h);
+    if (rc) return bail(rc);
+
+    TensorMap tm;
+    int64_t max_numel = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        tm.m[tensors[i].name] = &tensors[i];
+        max_numel = std::max(max_numel, tensors[i].numel);
     }
-    if (hipDeviceSynchronize() != hipSuccess) { h->err = "device synchronisation failed after packing"; return bail(AMX_EHIP); }
+    // (the fused, LayerNorm-folded Q / K / V matrix is packed from one host buffer of 3 hidden^2 floats: larger than any single
+    // tensor when ffn < 3 hidden)
+    max_numel = std::max<int64_t>(max_numel, (int64_t)3 * cfg->hidden * cfg->hidden);
+    float* staging = nullptr;
+    if (hipMalloc(&staging, (size_t)max_numel * 4 + 16) != hipSuccess) { h->err = "staging allocation failed"; return bail(AMX_ENOMEM); }
+    struct StagingGuard {
+        float* p;
+        ~StagingGuard() { (void)hipFree(p); }
+    } guard{staging};
+
+    const int D = cfg->hidden;
+    rc = create_feature_extractor(h, tm, staging);
+    if (!rc) rc = create_projection(h, tm, staging);
+    h->layers.resize(cfg->layers);
+    for (int l = 0; l < cfg->layers && !rc; ++l) rc = create_layer(h, tm, l, staging);
+    // the affine part of a folded LayerNorm lives in the weights: its row pass (short batches) normalises with (1, 0)
+    const std::vector<float> ones(D, 1.f);
+    if (!rc) rc = dev_upload(h, &h->unit_g, ones.data(), (size_t)D * 4);
+    if (!rc) rc = dev_upload(h, &h->zero_b, nullptr, (size_t)D * 4);
+    if (!rc) rc = upload_f32(h, tm, AM + "encoder.layer_norm.weight", D, &h->fln_g);
+    if (!rc) rc = upload_f32(h, tm, AM + "encoder.layer_norm.bias", D, &h->fln_b);
+    if (!rc) rc = create_heads(h, tm, staging);
+    if (!rc && h->composed_class >= 0) rc = create_composition(h, tm);
+    if (!rc) rc = dev_upload(h, &h->nonfinite, nullptr, 16);
+    // no composition layer: one implicit inventory (fixed output widths)
+    if (!rc && h->composed_class < 0) rc = install_inventory(h, std::vector<int64_t>{}, std::vector<int64_t>{}, 0, 0, 0);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(h, AMX_EHIP, "device synchronisation failed after packing");
+    if (rc) return bail(rc);
     *out = h;
     return AMX_OK;
 }
@@ -958,16 +955,12 @@ static void free_inventory(amx_handle_s::Inventory& e) {
 }
 
 static void select_inventory(amx_handle h, int i) {
-    auto& e = h->inventories[i];
-    e.last_use = ++h->inv_clock;
+    h->inventories[i].last_use = ++h->inv_clock;
     h->inv = i;
-    h->P1 = e.P1;
-    h->r_composed = e.r_composed;
-    h->composed_w = e.composed_w;
-    h->composed_f32 = e.composed_f32;
-    h->out_unique_dev = e.out_unique_dev;
-    h->out_all_dev = e.out_all_dev;
 }
+
+// the inventory the next pass uses (callers have checked h->inv >= 0: compute_layout)
+static const amx_handle_s::Inventory& cur_inv(amx_handle h) { return h->inventories[h->inv]; }
 
 // builds a new cache entry on `s`: every buffer is fresh, so nothing in flight can be reading it
 static int install_inventory(amx_handle h, std::vector<int64_t>&& key, const std::vector<int64_t>& idx, int P1, int features,
@@ -1069,12 +1062,14 @@ extern "C" int amx_set_inventory(amx_handle h, const int64_t* tfi, int phones, i
 // =================================================================================================================
 // layout
 // =================================================================================================================
-// frontend.py:192-203 applied per conv layer (acoustic_model.py:832-835) with floor division; 0 as soon as a layer's input
-// is shorter than its kernel (the reference's formula goes non-positive there)
-static int64_t frames_of(const amx_config& c, int64_t len) {
+// frontend.py:192-203 applied per conv layer (acoustic_model.py:832-835) with floor division: the frames of `len` samples, and
+// in Ts (when given) Ts[0] = len and Ts[i + 1] = the output rows of layer i.  0 from the first layer whose input is shorter than
+// its kernel on (the reference's formula goes non-positive there)
+static int64_t conv_lengths(const amx_config& c, int64_t len, int64_t* Ts = nullptr) {
+    if (Ts) Ts[0] = len;
     for (int i = 0; i < c.n_conv; ++i) {
-        if (len < c.conv_kernel[i]) return 0;
-        len = (len - c.conv_kernel[i]) / c.conv_stride[i] + 1;
+        len = len < c.conv_kernel[i] ? 0 : (len - c.conv_kernel[i]) / c.conv_stride[i] + 1;
+        if (Ts) Ts[i + 1] = len;
     }
     return len;
 }
@@ -1084,12 +1079,8 @@ static int64_t frames_of(const amx_config& c, int64_t len) {
 // activation plane plus the largest offset inside a tile must stay below 4 GiB; row indices are 32-bit.
 static int64_t max_utterances_for(const amx_config& c, int NT, int64_t L) {
     int64_t Ts[AMX_MAX_CONV + 1];
-    Ts[0] = L;
-    for (int i = 0; i < c.n_conv; ++i) {
-        if (Ts[i] < c.conv_kernel[i]) return 0;
-        Ts[i + 1] = (Ts[i] - c.conv_kernel[i]) / c.conv_stride[i] + 1;
-    }
-    const int64_t T = Ts[c.n_conv], Tp = (T + 63) / 64 * 64;
+    const int64_t T = conv_lengths(c, L, Ts), Tp = (T + 63) / 64 * 64;
+    if (T == 0) return 0;
     const int64_t C = c.conv_dim, D = c.hidden, F = c.ffn, H = c.heads;
     const int64_t wide = std::max<int64_t>(F, 3 * D);
     const int64_t LIMIT = ((int64_t)1 << 32) - ((int64_t)64 << 20);  // 4 GiB minus slack for the offsets inside a tile
@@ -1114,17 +1105,14 @@ extern "C" int64_t amx_max_utterances(amx_handle h, int64_t L) {
 
 static int compute_layout(amx_handle h, int N, int64_t L) {
     if (N < 1 || L < 1) return fail(h, AMX_EINVAL, "empty batch");
-    int64_t T = L;
-    for (int i = 0; i < h->cfg.n_conv; ++i) {
-        if (T < h->cfg.conv_kernel[i]) return fail(h, AMX_EINVAL, "utterances are shorter than the receptive field of the feature extractor");
-        T = (T - h->cfg.conv_kernel[i]) / h->cfg.conv_stride[i] + 1;
-    }
+    const int64_t T = conv_lengths(h->cfg, L);
+    if (T == 0) return fail(h, AMX_EINVAL, "utterances are shorter than the receptive field of the feature extractor");
     if (T > 1 << 20) return fail(h, AMX_EINVAL, "utterance too long");
     if (h->inv < 0)
         return fail(h, AMX_ESTATE, "composition model needs amx_set_inventory before prediction (the training inventory is a non-persistent buffer upstream)");
-    if (h->layout_N == N && h->layout_T == T && h->layout_inv == h->inv && h->layout_gen == h->inventories[h->inv].generation)
+    if (h->layout_N == N && h->layout_T == T && h->layout_inv == h->inv && h->layout_gen == cur_inv(h).generation)
         return AMX_OK;
-    build_tables(h, h->P1, h->col, h->width, h->ld_logits, h->out_unique, h->out_all);
+    build_tables(h, cur_inv(h).P1, h->col, h->width, h->ld_logits, h->out_unique, h->out_all);
     h->outputs.clear();
     int64_t off = 0;
     for (int ci : h->order) {
@@ -1147,7 +1135,7 @@ static int compute_layout(amx_handle h, int N, int64_t L) {
     h->layout_N = N;
     h->layout_T = T;
     h->layout_inv = h->inv;
-    h->layout_gen = h->inventories[h->inv].generation;
+    h->layout_gen = cur_inv(h).generation;
     return AMX_OK;
 }
 
@@ -1182,6 +1170,20 @@ static void drop_graphs(amx_handle h) {
     h->graph_seen.clear();
 }
 
+// Reads a completed range slot: adds its frames to `total` and "pass #id: frames" to `readings`.  A continuation slice's reading is
+// the chain's running count: what it adds is the difference to its predecessor's reading.
+static void range_read(amx_handle h, amx_handle_s::RangeSlot& sl, int64_t& total, std::string& readings) {
+    sl.pending = false;
+    const int reading = *sl.host;
+    const int added = sl.cont && h->range_chain_open ? reading - h->range_chain_seen : reading;
+    h->range_chain_seen = reading;
+    h->range_chain_open = true;
+    if (added > 0) {
+        total += added;
+        readings += (readings.empty() ? "" : ", ") + std::string("pass #") + std::to_string(sl.pass_id) + ": " + std::to_string(added);
+    }
+}
+
 // Range report of EARLIER forward passes: reads the pinned count of every pass whose trailing event has completed (`wait`:
 // of every pass issued -- the caller has just synchronised or accepts to).  Returns AMX_ERANGE when one of them counted valid
 // frames with non-finite logits; the report is consumed by the call that returns it.
@@ -1200,16 +1202,7 @@ static int range_poll(amx_handle h, bool wait) {
             if (q == hipErrorNotReady) break;
             if (q != hipSuccess) { (void)hipGetLastError(); break; }
         }
-        sl.pending = false;
-        // a continuation slice's reading is the chain's running count: what it adds is the difference to its predecessor's reading
-        const int reading = *sl.host;
-        const int added = sl.cont && h->range_chain_open ? reading - h->range_chain_seen : reading;
-        h->range_chain_seen = reading;
-        h->range_chain_open = true;
-        if (added > 0) {
-            total += added;
-            readings += (readings.empty() ? "" : ", ") + std::string("pass #") + std::to_string(sl.pass_id) + ": " + std::to_string(added);
-        }
+        range_read(h, sl, total, readings);
     }
     if (h->range_carry > 0) {
         total += h->range_carry;
@@ -1237,15 +1230,7 @@ static int range_record(amx_handle h, bool cont, hipStream_t s) {
         // RANGE_SLOTS passes ago and never read since (the host ran that far ahead): wait for that pass and carry its count
         // into the next report instead of losing it
         HIPCHK(h, hipEventSynchronize(sl.ev));
-        const int reading = *sl.host;
-        const int added = sl.cont && h->range_chain_open ? reading - h->range_chain_seen : reading;
-        h->range_chain_seen = reading;
-        h->range_chain_open = true;
-        if (added > 0) {
-            h->range_carry += added;
-            h->range_carry_ids += (h->range_carry_ids.empty() ? "" : ", ") + std::string("pass #") + std::to_string(sl.pass_id) + ": " + std::to_string(added);
-        }
-        sl.pending = false;
+        range_read(h, sl, h->range_carry, h->range_carry_ids);
     }
     HIPCHK(h, hipMemcpyAsync(sl.host, h->nonfinite, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipEventRecord(sl.ev, s));
@@ -1269,7 +1254,6 @@ constexpr size_t SPLITK_BYTES = (size_t)72 << 20;
 // enqueue_pass() reads it and issues nothing but kernels -- eagerly on the caller's stream, or once on the capture stream when
 // the pass is recorded into a HIP graph.  (Round 6: until then "plan + enqueue" was a lambda inside one 800-line function.)
 struct PassPlan {
-    amx_handle h = nullptr;
     // the call
     uint32_t flags = 0;
     int N = 0;
@@ -1304,17 +1288,16 @@ struct PassPlan {
     // host copies the tail of amx_forward keeps for amx_debug_fetch (packed_early only)
     std::vector<int> rowoff_host, frames_host;
 
-    int64_t plane(int64_t separate) const { return h->il ? PLANE_IL : std::max<int64_t>(separate, 64); }  // pln(h, .)
     GemmParams with_ws(GemmParams g) const {
         g.splitk_ws = (float*)splitk;
         g.splitk_ws_elems = splitk ? (int64_t)(SPLITK_BYTES / 4) : 0;
         return g;
     }
     // ---- the products of an encoder layer ----
-    GemmParams qkv_params(const Layer& ly) const {
+    GemmParams qkv_params(amx_handle h, const Layer& ly) const {
         GemmParams g{};
         g.A = xp; g.a_plane = xp_plane; g.lda = D; g.rows_per_batch = Mrows;
-        g.W = ly.wqkv; g.w_plane = plane((int64_t)3 * D * D); g.ldw = D;
+        g.W = ly.wqkv; g.w_plane = pln(h, (int64_t)3 * D * D); g.ldw = D;
         g.M = (int)Mrows; g.N = 3 * D; g.K = D;
         g.scale = ly.r_qkv; g.bias = ly.bqkv;
         g.mode = 1; g.q = qb; g.k = kb; g.v = vtb;
@@ -1323,28 +1306,28 @@ struct PassPlan {
         g.T = packed ? (int)std::max<int64_t>(Mp, 8) : T; g.Tp = packed ? TpTot : Tp; g.H = H; g.dh = dh; g.dhp = dhp;
         return with_ws(g);
     }
-    GemmParams oproj_params(const Layer& ly) const {
+    GemmParams oproj_params(amx_handle h, const Layer& ly) const {
         GemmParams g{};
         g.A = ao; g.a_plane = xp_plane; g.lda = D; g.rows_per_batch = Mrows;
-        g.W = ly.wo; g.w_plane = plane((int64_t)D * D); g.ldw = D;
+        g.W = ly.wo; g.w_plane = pln(h, (int64_t)D * D); g.ldw = D;
         g.M = (int)Mrows; g.N = D; g.K = D;
         g.scale = ly.r_o; g.bias = ly.bo;
         g.residual = stream; g.ldr = D; g.out_f32 = stream; g.ldo = D;
         return with_ws(g);
     }
-    GemmParams ffn1_params(const Layer& ly) const {
+    GemmParams ffn1_params(amx_handle h, const Layer& ly) const {
         GemmParams g{};
         g.A = xp; g.a_plane = xp_plane; g.lda = D; g.rows_per_batch = Mrows;
-        g.W = ly.w1; g.w_plane = plane((int64_t)F * D); g.ldw = D;
+        g.W = ly.w1; g.w_plane = pln(h, (int64_t)F * D); g.ldw = D;
         g.M = (int)Mrows; g.N = F; g.K = D;
         g.scale = ly.r_1; g.bias = ly.b1; g.act = 1;
-        g.out_p = ff; g.out_plane = plane(Mrows * F); g.ldp = F;
+        g.out_p = ff; g.out_plane = pln(h, Mrows * F); g.ldp = F;
         return with_ws(g);
     }
-    GemmParams ffn2_params(const Layer& ly) const {
+    GemmParams ffn2_params(amx_handle h, const Layer& ly) const {
         GemmParams g{};
-        g.A = ff; g.a_plane = plane(Mrows * F); g.lda = F; g.rows_per_batch = Mrows;
-        g.W = ly.w2; g.w_plane = plane((int64_t)D * F); g.ldw = F;
+        g.A = ff; g.a_plane = pln(h, Mrows * F); g.lda = F; g.rows_per_batch = Mrows;
+        g.W = ly.w2; g.w_plane = pln(h, (int64_t)D * F); g.ldw = F;
         g.M = (int)Mrows; g.N = D; g.K = F;
         g.scale = ly.r_2; g.bias = ly.b2;
         g.residual = stream; g.ldr = D; g.out_f32 = stream; g.ldo = D;
@@ -1376,273 +1359,73 @@ struct PassPlan {
 
 }  // namespace
 
-// The plan region of a forward pass (see PassPlan): argument and geometry checks, pinned uploads of lengths / frame counts / row
-// offsets / tile lists, every workspace buffer (ws_get may allocate, free and synchronise), the concatenation recipes of dependent
-// classifiers, and the decisions that depend on the lengths.
-static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, int N, int64_t L, float* out, int64_t* out_lengths,
-                     uint32_t flags, hipStream_t s, PassPlan& P) {
-    int rc;
+// (re)allocates the pinned ring for batches of up to N utterances (waits for the stream: the old slots may be in use)
+static int pin_reserve(amx_handle h, int N, hipStream_t s) {
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int i = 0; i < amx_handle_s::PIN_SLOTS; ++i) {
+        if (h->h_lengths_pinned[i]) {
+            (void)hipHostFree(h->h_lengths_pinned[i]);
+            (void)hipHostFree(h->h_frames_pinned[i]);
+            (void)hipHostFree(h->h_rowoff_pinned[i]);
+        }
+        HIPCHK(h, hipHostMalloc((void**)&h->h_lengths_pinned[i], (size_t)N * 8));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_frames_pinned[i], (size_t)N * 4));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_rowoff_pinned[i], (size_t)(3 * N + 1) * 4));  // offsets, the order, encoder frames
+        if (!h->pin_event[i]) HIPCHK(h, hipEventCreateWithFlags(&h->pin_event[i], hipEventDisableTiming));
+        h->pin_busy[i] = false;
+    }
+    h->pinned_cap = N;
+    return AMX_OK;
+}
+
+// Ragged batch: per conv layer i >= 1 the ascending list of its 128-row output tiles that hold a row some utterance owns
+// (`valid_rows`: [conv layer][n]), staged in pinned slot `slot` and uploaded behind the lengths
+static int plan_conv_tiles(amx_handle h, PassPlan& P, int slot, const std::vector<int>& valid_rows, hipStream_t s) {
     const amx_config& c = h->cfg;
-    const int NT = h->NT, prec = h->prec;
-    const int C = c.conv_dim, D = c.hidden, F = c.ffn, H = c.heads;
-    const bool keep = (flags & AMX_FLAG_KEEP_HIDDEN) != 0;
-    h->timing = (flags & AMX_FLAG_TIMING) != 0;
-    h->timing_stream = s;
-
-    int64_t Ts[AMX_MAX_CONV + 1];
-    Ts[0] = L;
-    for (int i = 0; i < c.n_conv; ++i) Ts[i + 1] = (Ts[i] - c.conv_kernel[i]) / c.conv_stride[i] + 1;
-    const int T = (int)Ts[c.n_conv];
-    const int64_t M = (int64_t)N * T;
-    {
-        const int64_t nmax = max_utterances_for(c, NT, L);
-        if (N > nmax)
-            return fail(h, AMX_EINVAL, "batch too large for the 32-bit offsets of the kernels: at most " + std::to_string(nmax) +
-                                           " utterances of " + std::to_string(L) + " samples per call (amx_max_utterances); split the batch");
+    const int N = P.N;
+    size_t total_tiles = 0;
+    constexpr int64_t TR = GEMM_LN_TILE_ROWS;
+    for (int i = 1; i < c.n_conv; ++i) total_tiles += (size_t)((N * P.Ts[i + 1] + TR - 1) / TR);
+    if (h->tiles_cap[slot] < total_tiles) {  // the slot is idle: plan_pass waited for its event
+        if (h->h_tiles_pinned[slot]) (void)hipHostFree(h->h_tiles_pinned[slot]);
+        h->h_tiles_pinned[slot] = nullptr;
+        h->tiles_cap[slot] = 0;
+        HIPCHK(h, hipHostMalloc((void**)&h->h_tiles_pinned[slot], (total_tiles + total_tiles / 4 + 64) * 4));
+        h->tiles_cap[slot] = total_tiles + total_tiles / 4 + 64;
     }
-    const int Tp = round_up(T, 64);
-
-    int64_t maxlen = 0;
-    for (int n = 0; n < N; ++n) {
-        if (lengths[n] < 1 || lengths[n] > L) return fail(h, AMX_EINVAL, "lengths must lie in [1, L]");
-        maxlen = std::max(maxlen, lengths[n]);
-    }
-    if (maxlen != L && !(flags & AMX_FLAG_PADDED))
-        return fail(h, AMX_EINVAL, "the batch must be padded to exactly max(lengths) (reference utils.py:62-63, acoustic_model.py:765-767)");
-
-    // ---- pinned host staging of lengths (ring of event-guarded slots: no stream synchronisation on the hot path) ----
-    if (h->pinned_cap < N) {
-        HIPCHK(h, hipStreamSynchronize(s));
-        for (int i = 0; i < amx_handle_s::PIN_SLOTS; ++i) {
-            if (h->h_lengths_pinned[i]) {
-                (void)hipHostFree(h->h_lengths_pinned[i]);
-                (void)hipHostFree(h->h_frames_pinned[i]);
-                (void)hipHostFree(h->h_rowoff_pinned[i]);
-            }
-            HIPCHK(h, hipHostMalloc((void**)&h->h_lengths_pinned[i], (size_t)N * 8));
-            HIPCHK(h, hipHostMalloc((void**)&h->h_frames_pinned[i], (size_t)N * 4));
-            HIPCHK(h, hipHostMalloc((void**)&h->h_rowoff_pinned[i], (size_t)(3 * N + 1) * 4));  // offsets, the order, encoder frames
-            if (!h->pin_event[i]) HIPCHK(h, hipEventCreateWithFlags(&h->pin_event[i], hipEventDisableTiming));
-            h->pin_busy[i] = false;
-        }
-        h->pinned_cap = N;
-    }
-    const int slot = h->pin_next;
-    h->pin_next = (h->pin_next + 1) % amx_handle_s::PIN_SLOTS;
-    if (h->pin_busy[slot]) HIPCHK(h, hipEventSynchronize(h->pin_event[slot]));  // its copies ran PIN_SLOTS calls ago
-    int64_t* pin_len = h->h_lengths_pinned[slot];
-    int* pin_frames = h->h_frames_pinned[slot];
-    int* pin_rowoff = h->h_rowoff_pinned[slot];
-    std::vector<int> conv_rows((size_t)c.n_conv * N);  // [conv layer][n]: valid output rows
-    int64_t Mp = 0;  // valid frames of the batch = rows of the packed layout
-    for (int n = 0; n < N; ++n) {
-        pin_len[n] = lengths[n];
-        {
-            int64_t len_i = lengths[n];  // valid output rows of every conv layer (floor arithmetic of frontend.py:192-203)
-            for (int i = 0; i < c.n_conv; ++i) {
-                len_i = len_i < c.conv_kernel[i] ? 0 : (len_i - c.conv_kernel[i]) / c.conv_stride[i] + 1;
-                conv_rows[(size_t)i * N + n] = (int)len_i;
-            }
-        }
-        int64_t f = frames_of(c, lengths[n]);
-        if (f < 1) return fail(h, AMX_EINVAL, "utterance shorter than the receptive field of the feature extractor");
-        pin_frames[n] = (int)f;
-        pin_rowoff[n] = (int)Mp;
-        Mp += f;
-        if (out_lengths) out_lengths[n] = f;
-    }
-    pin_rowoff[N] = (int)Mp;
-    {   // utterances by descending length (ties by index): the order the packed attention dispatches them in
-        int* order = pin_rowoff + N + 1;
-        for (int n = 0; n < N; ++n) order[n] = n;
-        std::stable_sort(order, order + N, [&](int a, int b) { return pin_frames[a] > pin_frames[b]; });
-    }
-    // The frames the ENCODER treats as valid: the utterance's own, or -- a model whose preprocessor has
-    // return_attention_mask = False is called with attention_mask=None (acoustic_model.py:814,842-846) -- every frame of the
-    // padded length: nothing is zeroed, every key is attended to.  `Predictions.lengths` are the utterance's own either way.
-    const bool masked = h->masked;
-    for (int n = 0; n < N; ++n) pin_rowoff[2 * N + 1 + n] = masked ? pin_frames[n] : T;
-    if (!masked) Mp = M;  // no padding as far as the encoder is concerned: nothing to pack, nothing to skip
-
-    // ---- workspace ----
-    void *d_len, *d_frames, *d_partial, *d_stats, *actA, *actB, *preln, *hbuf, *xp, *hg, *qb, *kb, *vtb, *ao, *ff, *hfin, *logits;
-    const int cg = D / c.pos_groups;
-    const int Tpad = T + c.pos_kernel;
-    const int64_t rows1 = (int64_t)N * Ts[1], rows2 = (int64_t)N * Ts[2];
-#define WS(name, bytes, ptr) do { if ((rc = ws_get(h, name, (size_t)(bytes), &ptr))) return rc; } while (0)
-    // split-K workspace (fp32 partial slabs of products too small to fill the chip; see launch_gemm): the partials of one
-    // product never exceed CUs x 256 x 256 floats
-    void* splitk;
-    WS("splitk", SPLITK_BYTES, splitk);
-    WS("len", (size_t)N * 8, d_len);
-    WS("frames", (size_t)N * 4, d_frames);
-    void* d_rowoff;
-    WS("rowoff", (size_t)(3 * N + 1) * 4, d_rowoff);
-    const int* d_frames_enc = (const int*)d_rowoff + 2 * N + 1;
-    WS("partial", (size_t)N * 64 * 3 * 8, d_partial);
-    WS("stats", (size_t)N * 2 * 4, d_stats);
-    WS("actA", (size_t)rows1 * C * 2 * NT + PLANE_SLACK, actA);
-    WS("actB", (size_t)rows2 * C * 2 * NT + PLANE_SLACK, actB);
-    WS("preln", (size_t)rows2 * C * 4, preln);
-    WS("h", (size_t)M * D * 4, hbuf);
-    WS("xp", (size_t)M * D * 2 * NT + PLANE_SLACK, xp);
-    WS("hg", (size_t)N * Tpad * D * 2 * NT, hg);
-    // head dimension and the width of a Q / K / V row: 64 columns, 128 for heads wider than that (the columns beyond dh stay zero:
-    // the buffers are zero-filled when they are created and the QKV scatter writes the dh real columns only)
-    const int dh = D / H, dhp = dh > 64 ? 128 : 64;
-    const size_t qkv_bytes = (size_t)N * H * Tp * dhp * 2 * NT;
-    if ((rc = ws_get(h, "q", qkv_bytes, &qb, true))) return rc;
-    if ((rc = ws_get(h, "k", qkv_bytes, &kb, true))) return rc;
-    if ((rc = ws_get(h, "vt", qkv_bytes, &vtb, true))) return rc;
-    WS("ao", (size_t)M * D * 2 * NT + PLANE_SLACK, ao);
-    WS("ff", (size_t)M * F * 2 * NT + PLANE_SLACK, ff);
-    WS("hfin", (size_t)M * D * 4, hfin);
-    WS("logits", (size_t)M * h->ld_logits * 4, logits);
-    // Packed rows: a ragged batch runs its encoder layers on the valid frames only (rows of utterance n at row_off[n], all
-    // utterances back to back): every kernel of a layer is row-wise except the attention, which takes the offsets.  A row's
-    // arithmetic does not depend on its position, so the valid frames come out as in the padded layout (the same bits when
-    // the products pick the same kernels for the smaller row count, within rounding of the K-chunk order otherwise).  Used
-    // when at least a tenth of the padded rows are padding (not under AMX_FLAG_KEEP_HIDDEN); AMX_FLAG_NO_PACK keeps the padded
-    // layout.
-    const bool any_hidden = keep;  // the debug capture wants every hidden state in the padded layout, padding included
-    const int TpTot = round_up((int)Mp, 64) + 64;  // rows per head of the packed Q / K / V planes
-    bool packed = !(flags & AMX_FLAG_NO_PACK) && !any_hidden && D % 4 == 0 && Mp * 10 <= M * 9 &&
-                  (int64_t)TpTot <= (int64_t)N * Tp;
-    // Packed from the feature projection on ("early"): the last conv layer's LayerNorm pass gathers the valid frames, so the
-    // feature projection, the positional convolution (window kernel: skips the frame blocks beyond an utterance), the final
-    // LayerNorm, the classifier heads and the log-softmax read packed rows too and nothing is packed or unpacked in between.
-    // Needs the window kernel (the grouped-GEMM form of the positional convolution addresses padded rows) and no time-layer
-    // head (its attention walks (utterance, frame) pairs); otherwise the rows are packed after the positional convolution
-    // and unpacked before the final LayerNorm, as in round 2.
-    const bool window_ok = posconv_window_eligible(D, c.pos_groups, c.pos_kernel, N, T, Tpad, (int64_t)N * Tpad * D);
-    bool any_time_layer = false;
-    for (auto& st : h->steps) any_time_layer |= st.time_heads > 0;
-    // (the post-LN encoder has no LayerNorm pass between its last layer and the heads to unpack behind: it packs early or not at all)
-    if (!h->stable && !(window_ok && !any_time_layer)) packed = false;
-    const bool packed_early = packed && window_ok && !any_time_layer;
-    void* hpk = nullptr;
-    if (packed) WS("h_packed", (size_t)Mp * D * 4, hpk);
-    const float* d_audio = audio;
-    float* d_out = out;
-    const int64_t total = layout_total(h, N, T);
-    if (flags & AMX_FLAG_HOST_IO) {
-        void *a, *o;
-        WS("audio_host_io", (size_t)N * L * 4, a);
-        WS("out_host_io", (size_t)total * 4, o);
-        HIPCHK(h, hipMemcpyAsync(a, audio, (size_t)N * L * 4, hipMemcpyHostToDevice, s));
-        d_audio = (const float*)a;
-        d_out = (float*)o;
-    }
-    std::vector<float*> saved(c.layers + 1, nullptr);
-    for (int l = 0; l < c.layers; ++l)
-        if (keep || h->need_hidden[l]) {
-            void* p;
-            std::string nm = "hid" + std::to_string(l);
-            WS(nm.c_str(), (size_t)M * D * 4, p);
-            saved[l] = (float*)p;
-        }
-    saved[c.layers] = (float*)hfin;
-    float* conv_dbg = nullptr;
-    if (keep) {
-        void* p;
-        WS("conv_dbg", (size_t)M * C * 4, p);
-        conv_dbg = (float*)p;
-    }
-
-    HIPCHK(h, hipMemcpyAsync(d_len, pin_len, (size_t)N * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_frames, pin_frames, (size_t)N * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_rowoff, pin_rowoff, (size_t)(3 * N + 1) * 4, hipMemcpyHostToDevice, s));
-    // Ragged batch: the conv stack skips what lies wholly in an utterance's padding (conv0: frame blocks; the row-complete
-    // layers 1..n-2: 128-row tiles).  A valid frame of any layer only reads valid frames of the layer below, and the rows
-    // left unwritten (stale, possibly non-finite) stay inside padded rows until the feature projection zeroes those.
-    // (only from a tenth of padding on -- the threshold of the packed rows: below it the padded frames are simply computed, and
-    // NOTHING of the pass depends on the lengths by value any more -- lengths, frame counts and masks are device buffers the plan
-    // refreshes -- so a recording of this (N, L) geometry serves every batch of that geometry: see the key below)
-    const bool ragged = Mp < M && Mp * 10 <= M * 9 && !keep && !(flags & AMX_FLAG_NO_PACK);
-    // per conv layer i >= 1: the ascending list of its 128-row output tiles that hold a row some utterance owns
-    int* d_tiles = nullptr;
-    size_t tile_first[AMX_MAX_CONV + 1] = {0};
-    if (ragged) {
-        size_t total_tiles = 0;
-        constexpr int64_t TR = GEMM_LN_TILE_ROWS;
-        for (int i = 1; i < c.n_conv; ++i) total_tiles += (size_t)((N * Ts[i + 1] + TR - 1) / TR);
-        if (h->tiles_cap[slot] < total_tiles) {  // the slot is idle: its event was waited for above
-            if (h->h_tiles_pinned[slot]) (void)hipHostFree(h->h_tiles_pinned[slot]);
-            h->h_tiles_pinned[slot] = nullptr;
-            h->tiles_cap[slot] = 0;
-            HIPCHK(h, hipHostMalloc((void**)&h->h_tiles_pinned[slot], (total_tiles + total_tiles / 4 + 64) * 4));
-            h->tiles_cap[slot] = total_tiles + total_tiles / 4 + 64;
-        }
-        int* list = h->h_tiles_pinned[slot];
-        size_t count = 0;
-        for (int i = 1; i < c.n_conv; ++i) {
-            tile_first[i] = count;
-            const int64_t rpb = Ts[i + 1], rows = N * rpb;
-            const int* valid = conv_rows.data() + (size_t)i * N;
-            for (int64_t first = 0; first < rows; first += TR) {
-                const int64_t last = std::min(first + TR, rows) - 1;
-                const int64_t b0 = first / rpb, b1 = last / rpb;
-                if (b0 != b1 || first - b0 * rpb < valid[b0]) list[count++] = (int)(first / TR);
-            }
-        }
-        tile_first[c.n_conv] = count;
-        void* p;
-        WS("conv_tiles", std::max<size_t>(count, 1) * 4, p);
-        d_tiles = (int*)p;
-        HIPCHK(h, hipMemcpyAsync(d_tiles, list, count * 4, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(h, hipEventRecord(h->pin_event[slot], s));
-    h->pin_busy[slot] = true;
-
-    // ---- the rest of the plan: every buffer and host-side table the pass needs exists before anything is enqueued, so that
-    // the enqueue region below issues nothing but memsets, kernels and device copies (which is what a HIP graph may hold) ----
-    void *gn_partial = nullptr, *gn_scale = nullptr, *gn_shift = nullptr;
-    if (h->gn) {
-        WS("gn_partial", conv0_groupnorm_partial_bytes(N, (int)Ts[1], C), gn_partial);
-        WS("gn_scale", (size_t)N * C * 4, gn_scale);
-        WS("gn_shift", (size_t)N * C * 4, gn_shift);
-    }
-    const bool stable = h->stable;
-    const int64_t Mh = packed_early ? Mp : M;  // rows of the final LayerNorm and of the classifier heads
-    // hidden_states[layers]: the final LayerNorm's fp32 rows; post-LN encoder: the stream as the last layer left it (kept in
-    // a buffer of its own only for the debug capture)
-    float* const hfin_rows = (stable || keep) ? (float*)hfin : (float*)(packed ? hpk : hbuf);
-    saved[c.layers] = hfin_rows;
-    const int E = c.embedding_size;
-    void *ebuf = nullptr, *cat = nullptr;
-    int kcat = 0;
-    for (auto& st : h->steps) kcat = std::max(kcat, st.direct_output ? 0 : st.Kpad);
-    const int Eld = round_up(E, kalign(h));  // row stride of the embedding planes (pad columns are never read: K = E)
-    if (E > 0) WS("e", (size_t)M * Eld * 2 * NT + PLANE_SLACK, ebuf);
-    if (kcat > 0) WS("cat", (size_t)M * kcat * 2 * NT + PLANE_SLACK, cat);
-    void *tl_x = nullptr, *tl_p = nullptr, *tl_qkv = nullptr;
-    {
-        int cmax = 0;
-        for (auto& st : h->steps)
-            if (st.time_heads > 0) {
-                cmax = std::max(cmax, st.Cpad);
-                if (st.rows / st.time_heads > 4096)
-                    return fail(h, AMX_EINVAL, "head_dim of a time-layer classifier beyond 4096");
-            }
-        if (cmax > 0) {
-            WS("tl_x", (size_t)M * cmax * 4, tl_x);
-            WS("tl_p", (size_t)M * cmax * 2 * NT + PLANE_SLACK, tl_p);
-            WS("tl_qkv", (size_t)M * cmax * 3 * 4, tl_qkv);
+    int* list = h->h_tiles_pinned[slot];
+    size_t count = 0;
+    for (int i = 1; i < c.n_conv; ++i) {
+        P.tile_first[i] = count;
+        const int64_t rpb = P.Ts[i + 1], rows = N * rpb;
+        const int* valid = valid_rows.data() + (size_t)i * N;
+        for (int64_t first = 0; first < rows; first += TR) {
+            const int64_t last = std::min(first + TR, rows) - 1;
+            const int64_t b0 = first / rpb, b1 = last / rpb;
+            if (b0 != b1 || first - b0 * rpb < valid[b0]) list[count++] = (int)(first / TR);
         }
     }
-    const bool blanks = c.dependency_blanks != 0;
+    P.tile_first[c.n_conv] = count;
+    void* p;
+    if (int rc = ws_get(h, "conv_tiles", std::max<size_t>(count, 1) * 4, &p)) return rc;
+    P.d_tiles = (int*)p;
+    HIPCHK(h, hipMemcpyAsync(P.d_tiles, list, count * 4, hipMemcpyHostToDevice, s));
+    return AMX_OK;
+}
+
+// the concatenation recipe of every classifier with dependencies: source pointers / logit columns of this pass
+static int plan_concat(amx_handle h, const PassPlan& P, hipStream_t s) {
     for (auto& st : h->steps) {
         if (st.direct_output) continue;
-        // concatenation recipe of a classifier with dependencies: source pointers / logit columns of this pass
         for (size_t i = 0; i < st.parts.size(); ++i) {
             int dep = st.part_dep[i];
             if (dep < 0) {
-                st.parts[i].src = dep == AMX_DEP_OUTPUT ? hfin_rows : saved[-2 - dep];
+                st.parts[i].src = dep == AMX_DEP_OUTPUT ? P.hfin_rows : P.saved[-2 - dep];
             } else {
-                st.parts[i].src_col = h->col[dep] + (blanks ? 0 : 1);
+                st.parts[i].src_col = h->col[dep] + (P.blanks ? 0 : 1);
                 // a composed dependency has an inventory-dependent width; the classifier was trained on the training
                 // inventory, so the widths must agree
-                int w = h->width[dep] - (blanks ? 0 : 1);
+                int w = h->width[dep] - (P.blanks ? 0 : 1);
                 if (w != st.parts[i].width)
                     return fail(h, AMX_EINVAL, "inventory size does not match the input width of a dependent classifier");
             }
@@ -1657,108 +1440,232 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
             st.parts_uploaded = st.parts;
         }
     }
-    const bool needs_qkv_zero = !packed && (h->last_N != N || h->last_T != T || h->qkv_dirty);
-    const int64_t Mrows = packed ? Mp : M;  // rows the layers work on
-    const int64_t xp_plane = pln(h, Mrows * D);
-    const int64_t qk_plane = packed ? (int64_t)H * TpTot * dhp : (int64_t)N * H * Tp * dhp;
-    float* const stream = (float*)(packed ? hpk : hbuf);  // the residual stream of the layers [Mrows, D]
-    // ---- the plan as a value ----
-    P.h = h;
-    P.flags = flags;
-    P.N = N;
-    P.L = L;
-    P.d_audio = d_audio;
-    P.d_out = d_out;
-    P.total = total;
-    P.NT = NT;
-    P.prec = prec;
-    P.C = C;
-    P.D = D;
-    P.F = F;
-    P.H = H;
-    P.T = T;
-    P.Tp = Tp;
-    P.TpTot = TpTot;
-    P.Tpad = Tpad;
-    P.cg = cg;
-    P.dh = dh;
-    P.dhp = dhp;
-    P.E = E;
-    P.Eld = Eld;
-    P.M = M;
-    P.Mp = Mp;
-    P.Mrows = Mrows;
-    P.Mh = Mh;
-    P.rows1 = rows1;
-    P.rows2 = rows2;
-    P.xp_plane = xp_plane;
-    P.qk_plane = qk_plane;
-    P.qkv_bytes = qkv_bytes;
-    P.keep = keep;
-    P.masked = masked;
-    P.stable = stable;
-    P.packed = packed;
-    P.packed_early = packed_early;
-    P.ragged = ragged;
-    P.window_ok = window_ok;
-    P.needs_qkv_zero = needs_qkv_zero;
-    P.blanks = blanks;
-    P.d_len = d_len;
-    P.d_frames = d_frames;
-    P.d_rowoff = d_rowoff;
-    P.d_partial = d_partial;
-    P.d_stats = d_stats;
-    P.actA = actA;
-    P.actB = actB;
-    P.preln = preln;
-    P.hbuf = hbuf;
-    P.xp = xp;
-    P.hg = hg;
-    P.qb = qb;
-    P.kb = kb;
-    P.vtb = vtb;
-    P.ao = ao;
-    P.ff = ff;
-    P.hfin = hfin;
-    P.logits = logits;
-    P.hpk = hpk;
-    P.splitk = splitk;
-    P.gn_partial = gn_partial;
-    P.gn_scale = gn_scale;
-    P.gn_shift = gn_shift;
-    P.ebuf = ebuf;
-    P.cat = cat;
-    P.tl_x = tl_x;
-    P.tl_p = tl_p;
-    P.tl_qkv = tl_qkv;
-    P.d_frames_enc = d_frames_enc;
-    P.d_tiles = d_tiles;
-    P.conv_dbg = conv_dbg;
-    P.hfin_rows = hfin_rows;
-    P.stream = stream;
-    for (int i = 0; i <= AMX_MAX_CONV; ++i) { P.Ts[i] = i <= c.n_conv ? Ts[i] : 0; P.tile_first[i] = tile_first[i]; }
-    P.saved = saved;
-    if (packed_early) {
+    return AMX_OK;
+}
+
+// The plan region of a forward pass (see PassPlan): argument and geometry checks, pinned uploads of lengths / frame counts / row
+// offsets / tile lists, every workspace buffer (ws_get may allocate, free and synchronise), the concatenation recipes of dependent
+// classifiers, and the decisions that depend on the lengths.
+static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, int N, int64_t L, float* out, int64_t* out_lengths,
+                     uint32_t flags, hipStream_t s, PassPlan& P) {
+    int rc;
+    const amx_config& c = h->cfg;
+    h->timing = (flags & AMX_FLAG_TIMING) != 0;
+    h->timing_stream = s;
+    P.flags = flags; P.N = N; P.L = L;
+    P.keep = (flags & AMX_FLAG_KEEP_HIDDEN) != 0;
+    P.NT = h->NT; P.prec = h->prec; P.C = c.conv_dim; P.D = c.hidden; P.F = c.ffn; P.H = c.heads;
+    const int NT = P.NT, C = P.C, D = P.D, F = P.F, H = P.H;
+
+    P.T = (int)conv_lengths(c, L, P.Ts);
+    P.M = (int64_t)N * P.T;
+    {
+        const int64_t nmax = max_utterances_for(c, NT, L);
+        if (N > nmax)
+            return fail(h, AMX_EINVAL, "batch too large for the 32-bit offsets of the kernels: at most " + std::to_string(nmax) +
+                                           " utterances of " + std::to_string(L) + " samples per call (amx_max_utterances); split the batch");
+    }
+    P.Tp = round_up(P.T, 64);
+
+    int64_t maxlen = 0;
+    for (int n = 0; n < N; ++n) {
+        if (lengths[n] < 1 || lengths[n] > L) return fail(h, AMX_EINVAL, "lengths must lie in [1, L]");
+        maxlen = std::max(maxlen, lengths[n]);
+    }
+    if (maxlen != L && !(flags & AMX_FLAG_PADDED))
+        return fail(h, AMX_EINVAL, "the batch must be padded to exactly max(lengths) (reference utils.py:62-63, acoustic_model.py:765-767)");
+
+    // ---- pinned host staging of lengths (ring of event-guarded slots: no stream synchronisation on the hot path) ----
+    if (h->pinned_cap < N && (rc = pin_reserve(h, N, s))) return rc;
+    const int slot = h->pin_next;
+    h->pin_next = (h->pin_next + 1) % amx_handle_s::PIN_SLOTS;
+    if (h->pin_busy[slot]) HIPCHK(h, hipEventSynchronize(h->pin_event[slot]));  // its copies ran PIN_SLOTS calls ago
+    int64_t* pin_len = h->h_lengths_pinned[slot];
+    int* pin_frames = h->h_frames_pinned[slot];
+    int* pin_rowoff = h->h_rowoff_pinned[slot];
+    std::vector<int> conv_rows((size_t)c.n_conv * N);  // [conv layer][n]: valid output rows
+    P.Mp = 0;  // valid frames of the batch = rows of the packed layout
+    for (int n = 0; n < N; ++n) {
+        pin_len[n] = lengths[n];
+        int64_t rows_n[AMX_MAX_CONV + 1];
+        const int64_t f = conv_lengths(c, lengths[n], rows_n);
+        for (int i = 0; i < c.n_conv; ++i) conv_rows[(size_t)i * N + n] = (int)rows_n[i + 1];
+        if (f < 1) return fail(h, AMX_EINVAL, "utterance shorter than the receptive field of the feature extractor");
+        pin_frames[n] = (int)f;
+        pin_rowoff[n] = (int)P.Mp;
+        P.Mp += f;
+        if (out_lengths) out_lengths[n] = f;
+    }
+    pin_rowoff[N] = (int)P.Mp;
+    {   // utterances by descending length (ties by index): the order the packed attention dispatches them in
+        int* order = pin_rowoff + N + 1;
+        for (int n = 0; n < N; ++n) order[n] = n;
+        std::stable_sort(order, order + N, [&](int a, int b) { return pin_frames[a] > pin_frames[b]; });
+    }
+    // The frames the ENCODER treats as valid: the utterance's own, or -- a model whose preprocessor has
+    // return_attention_mask = False is called with attention_mask=None (acoustic_model.py:814,842-846) -- every frame of the
+    // padded length: nothing is zeroed, every key is attended to.  `Predictions.lengths` are the utterance's own either way.
+    P.masked = h->masked;
+    for (int n = 0; n < N; ++n) pin_rowoff[2 * N + 1 + n] = P.masked ? pin_frames[n] : P.T;
+    if (!P.masked) P.Mp = P.M;  // no padding as far as the encoder is concerned: nothing to pack, nothing to skip
+
+    // ---- workspace ----
+    P.cg = D / c.pos_groups;
+    P.Tpad = P.T + c.pos_kernel;
+    P.rows1 = (int64_t)N * P.Ts[1];
+    P.rows2 = (int64_t)N * P.Ts[2];
+#define WS(name, bytes, ptr) do { if ((rc = ws_get(h, name, (size_t)(bytes), &ptr))) return rc; } while (0)
+    // split-K workspace (fp32 partial slabs of products too small to fill the chip; see launch_gemm): the partials of one
+    // product never exceed CUs x 256 x 256 floats
+    WS("splitk", SPLITK_BYTES, P.splitk);
+    WS("len", (size_t)N * 8, P.d_len);
+    WS("frames", (size_t)N * 4, P.d_frames);
+    WS("rowoff", (size_t)(3 * N + 1) * 4, P.d_rowoff);
+    P.d_frames_enc = (const int*)P.d_rowoff + 2 * N + 1;
+    WS("partial", (size_t)N * 64 * 3 * 8, P.d_partial);
+    WS("stats", (size_t)N * 2 * 4, P.d_stats);
+    WS("actA", (size_t)P.rows1 * C * 2 * NT + PLANE_SLACK, P.actA);
+    WS("actB", (size_t)P.rows2 * C * 2 * NT + PLANE_SLACK, P.actB);
+    WS("preln", (size_t)P.rows2 * C * 4, P.preln);
+    WS("h", (size_t)P.M * D * 4, P.hbuf);
+    WS("xp", (size_t)P.M * D * 2 * NT + PLANE_SLACK, P.xp);
+    WS("hg", (size_t)N * P.Tpad * D * 2 * NT, P.hg);
+    // head dimension and the width of a Q / K / V row: 64 columns, 128 for heads wider than that (the columns beyond dh stay zero:
+    // the buffers are zero-filled when they are created and the QKV scatter writes the dh real columns only)
+    P.dh = D / H;
+    P.dhp = P.dh > 64 ? 128 : 64;
+    P.qkv_bytes = (size_t)N * H * P.Tp * P.dhp * 2 * NT;
+    if ((rc = ws_get(h, "q", P.qkv_bytes, &P.qb, true))) return rc;
+    if ((rc = ws_get(h, "k", P.qkv_bytes, &P.kb, true))) return rc;
+    if ((rc = ws_get(h, "vt", P.qkv_bytes, &P.vtb, true))) return rc;
+    WS("ao", (size_t)P.M * D * 2 * NT + PLANE_SLACK, P.ao);
+    WS("ff", (size_t)P.M * F * 2 * NT + PLANE_SLACK, P.ff);
+    WS("hfin", (size_t)P.M * D * 4, P.hfin);
+    WS("logits", (size_t)P.M * h->ld_logits * 4, P.logits);
+    // Packed rows: a ragged batch runs its encoder layers on the valid frames only (rows of utterance n at row_off[n], all
+    // utterances back to back): every kernel of a layer is row-wise except the attention, which takes the offsets.  A row's
+    // arithmetic does not depend on its position, so the valid frames come out as in the padded layout (the same bits when
+    // the products pick the same kernels for the smaller row count, within rounding of the K-chunk order otherwise).  Used
+    // when at least a tenth of the padded rows are padding (not under AMX_FLAG_KEEP_HIDDEN: the debug capture wants every hidden
+    // state in the padded layout, padding included); AMX_FLAG_NO_PACK keeps the padded layout.
+    P.TpTot = round_up((int)P.Mp, 64) + 64;  // rows per head of the packed Q / K / V planes
+    P.packed = !(flags & AMX_FLAG_NO_PACK) && !P.keep && D % 4 == 0 && P.Mp * 10 <= P.M * 9 &&
+               (int64_t)P.TpTot <= (int64_t)N * P.Tp;
+    // Packed from the feature projection on ("early"): the last conv layer's LayerNorm pass gathers the valid frames, so the
+    // feature projection, the positional convolution (window kernel: skips the frame blocks beyond an utterance), the final
+    // LayerNorm, the classifier heads and the log-softmax read packed rows too and nothing is packed or unpacked in between.
+    // Needs the window kernel (the grouped-GEMM form of the positional convolution addresses padded rows) and no time-layer
+    // head (its attention walks (utterance, frame) pairs); otherwise the rows are packed after the positional convolution
+    // and unpacked before the final LayerNorm, as in round 2.
+    P.window_ok = posconv_window_eligible(D, c.pos_groups, c.pos_kernel, N, P.T, P.Tpad, (int64_t)N * P.Tpad * D);
+    bool any_time_layer = false;
+    for (auto& st : h->steps) any_time_layer |= st.time_heads > 0;
+    // (the post-LN encoder has no LayerNorm pass between its last layer and the heads to unpack behind: it packs early or not at all)
+    if (!h->stable && !(P.window_ok && !any_time_layer)) P.packed = false;
+    P.packed_early = P.packed && P.window_ok && !any_time_layer;
+    if (P.packed) WS("h_packed", (size_t)P.Mp * D * 4, P.hpk);
+    P.d_audio = audio;
+    P.d_out = out;
+    P.total = layout_total(h, N, P.T);
+    if (flags & AMX_FLAG_HOST_IO) {
+        void *a, *o;
+        WS("audio_host_io", (size_t)N * L * 4, a);
+        WS("out_host_io", (size_t)P.total * 4, o);
+        HIPCHK(h, hipMemcpyAsync(a, audio, (size_t)N * L * 4, hipMemcpyHostToDevice, s));
+        P.d_audio = (const float*)a;
+        P.d_out = (float*)o;
+    }
+    P.saved.assign(c.layers + 1, nullptr);
+    for (int l = 0; l < c.layers; ++l)
+        if (P.keep || h->need_hidden[l]) {
+            void* p;
+            std::string nm = "hid" + std::to_string(l);
+            WS(nm.c_str(), (size_t)P.M * D * 4, p);
+            P.saved[l] = (float*)p;
+        }
+    if (P.keep) {
+        void* p;
+        WS("conv_dbg", (size_t)P.M * C * 4, p);
+        P.conv_dbg = (float*)p;
+    }
+
+    HIPCHK(h, hipMemcpyAsync(P.d_len, pin_len, (size_t)N * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(P.d_frames, pin_frames, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(P.d_rowoff, pin_rowoff, (size_t)(3 * N + 1) * 4, hipMemcpyHostToDevice, s));
+    // Ragged batch: the conv stack skips what lies wholly in an utterance's padding (conv0: frame blocks; the row-complete
+    // layers 1..n-2: 128-row tiles).  A valid frame of any layer only reads valid frames of the layer below, and the rows
+    // left unwritten (stale, possibly non-finite) stay inside padded rows until the feature projection zeroes those.
+    // (only from a tenth of padding on -- the threshold of the packed rows: below it the padded frames are simply computed, and
+    // NOTHING of the pass depends on the lengths by value any more -- lengths, frame counts and masks are device buffers the plan
+    // refreshes -- so a recording of this (N, L) geometry serves every batch of that geometry: see graph_key)
+    P.ragged = P.Mp < P.M && P.Mp * 10 <= P.M * 9 && !P.keep && !(flags & AMX_FLAG_NO_PACK);
+    if (P.ragged && (rc = plan_conv_tiles(h, P, slot, conv_rows, s))) return rc;
+    HIPCHK(h, hipEventRecord(h->pin_event[slot], s));
+    h->pin_busy[slot] = true;
+
+    // ---- the rest of the plan: every buffer and host-side table the pass needs exists before anything is enqueued, so that
+    // enqueue_pass issues nothing but memsets, kernels and device copies (which is what a HIP graph may hold) ----
+    if (h->gn) {
+        WS("gn_partial", conv0_groupnorm_partial_bytes(N, (int)P.Ts[1], C), P.gn_partial);
+        WS("gn_scale", (size_t)N * C * 4, P.gn_scale);
+        WS("gn_shift", (size_t)N * C * 4, P.gn_shift);
+    }
+    P.stable = h->stable;
+    P.Mh = P.packed_early ? P.Mp : P.M;  // rows of the final LayerNorm and of the classifier heads
+    // hidden_states[layers]: the final LayerNorm's fp32 rows; post-LN encoder: the stream as the last layer left it (kept in
+    // a buffer of its own only for the debug capture)
+    P.hfin_rows = (P.stable || P.keep) ? (float*)P.hfin : (float*)(P.packed ? P.hpk : P.hbuf);
+    P.saved[c.layers] = P.hfin_rows;
+    P.E = c.embedding_size;
+    int kcat = 0;
+    for (auto& st : h->steps) kcat = std::max(kcat, st.direct_output ? 0 : st.Kpad);
+    P.Eld = round_up(P.E, kalign(h));  // row stride of the embedding planes (pad columns are never read: K = E)
+    if (P.E > 0) WS("e", (size_t)P.M * P.Eld * 2 * NT + PLANE_SLACK, P.ebuf);
+    if (kcat > 0) WS("cat", (size_t)P.M * kcat * 2 * NT + PLANE_SLACK, P.cat);
+    {
+        int cmax = 0;
+        for (auto& st : h->steps)
+            if (st.time_heads > 0) {
+                cmax = std::max(cmax, st.Cpad);
+                if (st.rows / st.time_heads > 4096)
+                    return fail(h, AMX_EINVAL, "head_dim of a time-layer classifier beyond 4096");
+            }
+        if (cmax > 0) {
+            WS("tl_x", (size_t)P.M * cmax * 4, P.tl_x);
+            WS("tl_p", (size_t)P.M * cmax * 2 * NT + PLANE_SLACK, P.tl_p);
+            WS("tl_qkv", (size_t)P.M * cmax * 3 * 4, P.tl_qkv);
+        }
+    }
+    P.blanks = c.dependency_blanks != 0;
+    if ((rc = plan_concat(h, P, s))) return rc;
+    P.needs_qkv_zero = !P.packed && (h->last_N != N || h->last_T != P.T || h->qkv_dirty);
+    P.Mrows = P.packed ? P.Mp : P.M;  // rows the layers work on
+    P.xp_plane = pln(h, P.Mrows * D);
+    P.qk_plane = P.packed ? (int64_t)H * P.TpTot * P.dhp : (int64_t)N * H * P.Tp * P.dhp;
+    P.stream = (float*)(P.packed ? P.hpk : P.hbuf);
+    if (P.packed_early) {
         P.rowoff_host.assign(pin_rowoff, pin_rowoff + N);
         P.frames_host.assign(pin_frames, pin_frames + N);
     }
     // LayerNorm fold: decided on the products as they will be launched
     P.stream_in_planes = NT == 2;
-    if (stable && c.layers > 0 && D % 64 == 0 && D <= 2048) {
-        WS("ln_rowps", (size_t)Mrows * 16, P.ln_rowps);
-        WS("ln_coef", (size_t)Mrows * 8, P.ln_coef);
-        WS("ln_partial", (size_t)Mrows * (D / 64) * 8, P.ln_partial);
+    if (P.stable && c.layers > 0 && D % 64 == 0 && D <= 2048) {
+        WS("ln_rowps", (size_t)P.Mrows * 16, P.ln_rowps);
+        WS("ln_coef", (size_t)P.Mrows * 8, P.ln_coef);
+        WS("ln_partial", (size_t)P.Mrows * (D / 64) * 8, P.ln_partial);
         const Layer& ly = h->layers[0];
+        const int prec = P.prec;
         // (the producers as enqueue_pass launches them: the out-projection without fp32 rows, FFN2 with and without)
-        P.fold = gemm_ln_fold_ok(prec, P.as_consumer(P.qkv_params(ly), ly.c_qkv)) &&
-                 gemm_ln_fold_ok(prec, P.as_producer(P.oproj_params(ly), false)) &&
-                 gemm_ln_fold_ok(prec, P.as_consumer(P.ffn1_params(ly), ly.c_1)) &&
-                 gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(ly), false)) && gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(ly), true));
+        P.fold = gemm_ln_fold_ok(prec, P.as_consumer(P.qkv_params(h, ly), ly.c_qkv)) &&
+                 gemm_ln_fold_ok(prec, P.as_producer(P.oproj_params(h, ly), false)) &&
+                 gemm_ln_fold_ok(prec, P.as_consumer(P.ffn1_params(h, ly), ly.c_1)) &&
+                 gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(h, ly), false)) &&
+                 gemm_ln_fold_ok(prec, P.as_producer(P.ffn2_params(h, ly), true));
     }
     ++h->pass_counter;
     h->last_fold = P.fold;
-    h->last_packed = packed_early ? 2 : (packed ? 1 : 0);
-    h->last_rows = Mrows;
+    h->last_packed = P.packed_early ? 2 : (P.packed ? 1 : 0);
+    h->last_rows = P.Mrows;
     h->last_graph = 0;
 #undef WS
     return AMX_OK;
@@ -1768,132 +1675,62 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
 // launch_zero), nothing that allocates, uploads or synchronises.
 static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
     const amx_config& c = h->cfg;
-    const auto flags = P.flags;
-    const auto N = P.N;
-    const auto L = P.L;
-    const auto d_audio = P.d_audio;
-    const auto d_out = P.d_out;
-    const auto total = P.total;
-    const auto NT = P.NT;
-    const auto prec = P.prec;
-    const auto C = P.C;
-    const auto D = P.D;
-    const auto F = P.F;
-    const auto H = P.H;
-    const auto T = P.T;
-    const auto Tp = P.Tp;
-    const auto TpTot = P.TpTot;
-    const auto Tpad = P.Tpad;
-    const auto cg = P.cg;
-    const auto dh = P.dh;
-    const auto dhp = P.dhp;
-    const auto E = P.E;
-    const auto Eld = P.Eld;
-    const auto M = P.M;
-    const auto Mp = P.Mp;
-    const auto Mrows = P.Mrows;
-    const auto Mh = P.Mh;
-    const auto rows1 = P.rows1;
-    const auto rows2 = P.rows2;
-    const auto xp_plane = P.xp_plane;
-    const auto qk_plane = P.qk_plane;
-    const auto qkv_bytes = P.qkv_bytes;
-    const auto keep = P.keep;
-    const auto masked = P.masked;
-    const auto stable = P.stable;
-    const auto packed = P.packed;
-    const auto packed_early = P.packed_early;
-    const auto ragged = P.ragged;
-    const auto window_ok = P.window_ok;
-    const auto needs_qkv_zero = P.needs_qkv_zero;
-    const auto blanks = P.blanks;
-    const auto d_len = P.d_len;
-    const auto d_frames = P.d_frames;
-    const auto d_rowoff = P.d_rowoff;
-    const auto d_partial = P.d_partial;
-    const auto d_stats = P.d_stats;
-    const auto actA = P.actA;
-    const auto actB = P.actB;
-    const auto preln = P.preln;
-    void* hbuf = P.hbuf;  // (local: the layers switch it to the packed stream and back)
-    const auto xp = P.xp;
-    const auto hg = P.hg;
-    const auto qb = P.qb;
-    const auto kb = P.kb;
-    const auto vtb = P.vtb;
-    const auto ao = P.ao;
-    const auto ff = P.ff;
-    const auto hfin = P.hfin;
-    const auto logits = P.logits;
-    const auto hpk = P.hpk;
-    const auto splitk = P.splitk;
-    const auto gn_partial = P.gn_partial;
-    const auto gn_scale = P.gn_scale;
-    const auto gn_shift = P.gn_shift;
-    const auto ebuf = P.ebuf;
-    const auto cat = P.cat;
-    const auto tl_x = P.tl_x;
-    const auto tl_p = P.tl_p;
-    const auto tl_qkv = P.tl_qkv;
-    const auto d_frames_enc = P.d_frames_enc;
-    const auto d_tiles = P.d_tiles;
-    const auto conv_dbg = P.conv_dbg;
-    const auto hfin_rows = P.hfin_rows;
-    const auto stream = P.stream;
-    const auto& Ts = P.Ts;
-    const auto& tile_first = P.tile_first;
-    const auto& saved = P.saved;
-    const bool fold = P.fold, stream_in_planes = P.stream_in_planes;
-    void* const ln_rowps = P.ln_rowps; void* const ln_coef = P.ln_coef; void* const ln_partial = P.ln_partial;
-    (void)F; (void)rows2; (void)total; (void)Mh; (void)E; (void)hfin; (void)stream; (void)blanks; (void)ln_coef; (void)stream_in_planes;
-    (void)ff; (void)splitk; (void)hfin_rows; (void)qk_plane; (void)dh; (void)Tp; (void)cg; (void)Eld;
-    auto run_gemm = [&](int precision, GemmParams& g, hipStream_t stream_) { g = P.with_ws(g); launch_gemm(precision, g, stream_); };
+    const int prec = P.prec, N = P.N, C = P.C, D = P.D, T = P.T;
+    const int64_t M = P.M, Mh = P.Mh;
+    void* hbuf = P.hbuf;  // the residual stream: the layers switch it to the packed rows and back
+    // Every GEMM of the pass: split-K workspace, timed under its kernel class (the one launch_gemm picks unless the caller names
+    // one), refusals recorded.  launch_gemm refuses fold products only, and P.fold checked those with these very params.
+    bool refused = false;
+    auto gemm = [&](const GemmParams& g, int cls = -1) {
+        Timed t_(h, cls < 0 ? gemm_class(prec, g) : cls);
+        refused |= !launch_gemm(prec, P.with_ws(g), s);
+    };
     // K/V/Q padding rows [T, Tp) must stay finite: re-zero when the geometry changes
     // (zero fills inside a pass are kernels, never memsets: amx_rowops.hip, launch_zero)
-    if (needs_qkv_zero) {
-        launch_zero(qb, qkv_bytes, s);
-        launch_zero(kb, qkv_bytes, s);
-        launch_zero(vtb, qkv_bytes, s);
+    if (P.needs_qkv_zero) {
+        launch_zero(P.qb, P.qkv_bytes, s);
+        launch_zero(P.kb, P.qkv_bytes, s);
+        launch_zero(P.vtb, P.qkv_bytes, s);
     }
-    if (packed) {
+    if (P.packed) {
         // rows [Mp, TpTot) of every head are read (never used) by the last key tile and query block: keep them finite
-        const size_t row_b = (size_t)dhp * 2, tail = (size_t)(TpTot - Mp) * row_b, pitch = (size_t)TpTot * row_b;
-        for (void* buf : {qb, kb, vtb})  // the planes lie back to back: NT * H blocks of TpTot rows
-            launch_zero_2d((char*)buf + (size_t)Mp * row_b, pitch, tail, (size_t)NT * H, s);
+        const size_t row_b = (size_t)P.dhp * 2, tail = (size_t)(P.TpTot - P.Mp) * row_b, pitch = (size_t)P.TpTot * row_b;
+        for (void* buf : {P.qb, P.kb, P.vtb})  // the planes lie back to back: NT * H blocks of TpTot rows
+            launch_zero_2d((char*)buf + (size_t)P.Mp * row_b, pitch, tail, (size_t)P.NT * P.H, s);
     }
     // amx_check_finite reports on THIS forward pass; the later slices of one over-long batch (AMX_FLAG_CONTINUE) add up
-    if (!(flags & AMX_FLAG_CONTINUE)) launch_zero(h->nonfinite, 4, s);
+    if (!(P.flags & AMX_FLAG_CONTINUE)) launch_zero(h->nonfinite, 4, s);
     // ---- input normalisation statistics + conv layer 0 (fused norm + conv + LN + GELU) ----
-    { Timed t_(h, AMX_KC_OTHER); launch_audio_stats(d_audio, (const int64_t*)d_len, N, L, (double*)d_partial, (float*)d_stats, c.do_normalize, s); }
+    { Timed t_(h, AMX_KC_OTHER); launch_audio_stats(P.d_audio, (const int64_t*)P.d_len, N, P.L, (double*)P.d_partial, (float*)P.d_stats, c.do_normalize, s); }
     if (h->gn) {
         // group-norm variant: GroupNorm statistics over ALL frames of the padded length (upstream normalises the padded batch
         // tensor), then conv + affine + GELU; frame blocks in an utterance's padding may still be skipped in the second pass
         Timed t_(h, AMX_KC_CONV0);
-        launch_conv0_groupnorm(prec, d_audio, (const int64_t*)d_len, (const float*)d_stats, N, L, (int)Ts[1], C, c.conv_kernel[0],
+        launch_conv0_groupnorm(prec, P.d_audio, (const int64_t*)P.d_len, (const float*)P.d_stats, N, P.L, (int)P.Ts[1], C, c.conv_kernel[0],
                                c.conv_stride[0], h->c0_w, h->conv_b[0], h->conv_g[0], h->conv_be[0], 1e-5f, c.do_normalize,
-                               (double*)gn_partial, (float*)gn_scale, (float*)gn_shift, actA, pln(h, rows1 * C), ragged ? 1 : 0, s,
+                               (double*)P.gn_partial, (float*)P.gn_scale, (float*)P.gn_shift, P.actA, pln(h, P.rows1 * C), P.ragged ? 1 : 0, s,
                                conv0_mfma_eligible(C, c.conv_kernel[0], c.conv_stride[0]) ? h->c0_wscale : 0.f);
     } else {
         Timed t_(h, AMX_KC_CONV0);
-        launch_conv0(prec, d_audio, (const int64_t*)d_len, (const float*)d_stats, N, L, (int)Ts[1], C, c.conv_kernel[0],
-                     c.conv_stride[0], h->c0_w, h->conv_b[0], h->conv_g[0], h->conv_be[0], 1e-5f, c.do_normalize, actA,
-                     pln(h, rows1 * C), ragged ? 1 : 0, s, h->c0_stats, h->c0_wscale);
+        launch_conv0(prec, P.d_audio, (const int64_t*)P.d_len, (const float*)P.d_stats, N, P.L, (int)P.Ts[1], C, c.conv_kernel[0],
+                     c.conv_stride[0], h->c0_w, h->conv_b[0], h->conv_g[0], h->conv_be[0], 1e-5f, c.do_normalize, P.actA,
+                     pln(h, P.rows1 * C), P.ragged ? 1 : 0, s, h->c0_stats, h->c0_wscale);
     }
     // ---- conv layers 1..n-1: implicit GEMM over overlapping channels-last windows, then LN + GELU rows ----
-    void* cur = actA;
-    int64_t cur_plane = pln(h, rows1 * C);
-    void* other = actB;
+    void* cur = P.actA;
+    int64_t cur_plane = pln(h, P.rows1 * C);
+    void* other = P.actB;
     for (int i = 1; i < c.n_conv; ++i) {
-        const int64_t rows_out = (int64_t)N * Ts[i + 1];
+        const int64_t rows_out = (int64_t)N * P.Ts[i + 1];
         GemmParams g{};
-        g.A = cur; g.a_plane = cur_plane; g.lda = (int64_t)c.conv_stride[i] * C; g.rows_per_batch = Ts[i + 1];
-        g.a_batch_stride = Ts[i] * C;
+        g.A = cur; g.a_plane = cur_plane; g.lda = (int64_t)c.conv_stride[i] * C; g.rows_per_batch = P.Ts[i + 1];
+        g.a_batch_stride = P.Ts[i] * C;
         g.W = h->conv_w[i]; g.w_plane = pln(h, (int64_t)C * C * c.conv_kernel[i]); g.ldw = (int64_t)C * c.conv_kernel[i];
         g.M = (int)rows_out; g.N = C; g.K = C * c.conv_kernel[i];
         g.scale = h->conv_r[i]; g.bias = h->conv_b[i];
-        if (ragged) {  // honoured by the row-complete kernel only
-            g.tile_list = d_tiles + tile_first[i];
-            g.n_tiles = (int)(tile_first[i + 1] - tile_first[i]);
+        if (P.ragged) {  // honoured by the row-complete kernel only
+            g.tile_list = P.d_tiles + P.tile_first[i];
+            g.n_tiles = (int)(P.tile_first[i + 1] - P.tile_first[i]);
         }
         const bool last = i == c.n_conv - 1;
         const int64_t out_plane = pln(h, rows_out * C);
@@ -1903,15 +1740,15 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
             g.tile_list = nullptr; g.n_tiles = 0;
             if (!last) {
                 g.out_p = other; g.out_plane = out_plane; g.ldp = C;
-                { Timed t_(h, gemm_class(prec, g)); run_gemm(prec, g, s); }
+                gemm(g);
             } else {
                 // last layer: fp32 GELU output, then the feature-projection LayerNorm -> planes (packed_early: valid frames only)
-                g.out_f32 = keep ? conv_dbg : (float*)preln; g.ldo = C;
-                { Timed t_(h, AMX_KC_CONV_TAIL); run_gemm(prec, g, s); }
+                g.out_f32 = P.keep ? P.conv_dbg : (float*)P.preln; g.ldo = C;
+                gemm(g, AMX_KC_CONV_TAIL);
                 Timed t_(h, AMX_KC_CONV_TAIL);
-                if (packed_early)
+                if (P.packed_early)
                     launch_rownorm_to_packed(prec, g.out_f32, C, rows_out, C, nullptr, nullptr, 0, h->fp_g, h->fp_b, 0.f, c.eps, other,
-                                             out_plane, C, (const int*)d_rowoff, (const int*)d_frames, T, s);
+                                             out_plane, C, (const int*)P.d_rowoff, (const int*)P.d_frames, T, s);
                 else
                     launch_rownorm(prec, g.out_f32, C, rows_out, C, nullptr, nullptr, 0, h->fp_g, h->fp_b, 0.f, c.eps, other, out_plane,
                                    C, nullptr, 0, s);
@@ -1932,31 +1769,31 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
                     f.a_taps = c.conv_kernel[i];
                     f.a_tap_stride = C;
                 }
-                { Timed t_(h, AMX_KC_GEMM_LN); run_gemm(prec, f, s); }
+                gemm(f, AMX_KC_GEMM_LN);
                 std::swap(cur, other);
                 cur_plane = out_plane;
                 continue;
             }
         }
-        g.out_f32 = (float*)preln; g.ldo = C;
-        { Timed t_(h, last ? AMX_KC_CONV_TAIL : gemm_class(prec, g)); run_gemm(prec, g, s); }
+        g.out_f32 = (float*)P.preln; g.ldo = C;
+        gemm(g, last ? AMX_KC_CONV_TAIL : gemm_class(prec, g));
         if (!last) {
-            { Timed t_(h, AMX_KC_ROWNORM); launch_rownorm(prec, (const float*)preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, nullptr, nullptr, 1e-5f,
+            { Timed t_(h, AMX_KC_ROWNORM); launch_rownorm(prec, (const float*)P.preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, nullptr, nullptr, 1e-5f,
                            0.f, other, out_plane, C, nullptr, 0, s); }
-        } else if (!keep) {
+        } else if (!P.keep) {
             // last conv layer: LN + GELU, then the feature-projection LayerNorm in the same pass (packed_early: only the valid
             // frames, written back to back)
             Timed t_(h, AMX_KC_CONV_TAIL);
-            if (packed_early)
-                launch_rownorm_to_packed(prec, (const float*)preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, h->fp_g, h->fp_b, 1e-5f,
-                                         c.eps, other, out_plane, C, (const int*)d_rowoff, (const int*)d_frames, T, s);
+            if (P.packed_early)
+                launch_rownorm_to_packed(prec, (const float*)P.preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, h->fp_g, h->fp_b, 1e-5f,
+                                         c.eps, other, out_plane, C, (const int*)P.d_rowoff, (const int*)P.d_frames, T, s);
             else
-                launch_rownorm(prec, (const float*)preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, h->fp_g, h->fp_b, 1e-5f,
+                launch_rownorm(prec, (const float*)P.preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, h->fp_g, h->fp_b, 1e-5f,
                                c.eps, other, out_plane, C, nullptr, 0, s);
         } else {
-            { Timed t_(h, AMX_KC_ROWNORM); launch_rownorm(prec, (const float*)preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, nullptr, nullptr, 1e-5f,
-                           0.f, nullptr, 0, 0, conv_dbg, C, s); }
-            { Timed t_(h, AMX_KC_ROWNORM); launch_rownorm(prec, conv_dbg, C, rows_out, C, h->fp_g, h->fp_b, 0, nullptr, nullptr, c.eps, 0.f, other, out_plane,
+            { Timed t_(h, AMX_KC_ROWNORM); launch_rownorm(prec, (const float*)P.preln, C, rows_out, C, h->conv_g[i], h->conv_be[i], 1, nullptr, nullptr, 1e-5f,
+                           0.f, nullptr, 0, 0, P.conv_dbg, C, s); }
+            { Timed t_(h, AMX_KC_ROWNORM); launch_rownorm(prec, P.conv_dbg, C, rows_out, C, h->fp_g, h->fp_b, 0, nullptr, nullptr, c.eps, 0.f, other, out_plane,
                            C, nullptr, 0, s); }
         }
         std::swap(cur, other);
@@ -1965,50 +1802,50 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
     // ---- feature projection (+ zero padded frames) ----
     {
         GemmParams g{};
-        const int64_t Mfp = packed_early ? Mp : M;  // packed_early: the valid frames only, no row mask needed
+        const int64_t Mfp = P.packed_early ? P.Mp : M;  // packed_early: the valid frames only, no row mask needed
         g.A = cur; g.a_plane = cur_plane; g.lda = C; g.rows_per_batch = Mfp; g.a_batch_stride = 0;
         g.W = h->fp_w; g.w_plane = pln(h, (int64_t)D * C); g.ldw = C;
         g.M = (int)Mfp; g.N = D; g.K = C;
         g.scale = h->fp_r; g.bias = h->fp_bias;
-        if (!packed_early && masked) { g.row_len = (const int*)d_frames; g.rows_T = T; }  // hidden_states[~mask] = 0
-        g.out_f32 = (float*)(packed_early ? hpk : hbuf); g.ldo = D;
-        { Timed t_(h, gemm_class(prec, g)); run_gemm(prec, g, s); }
+        if (!P.packed_early && P.masked) { g.row_len = (const int*)P.d_frames; g.rows_T = T; }  // hidden_states[~mask] = 0
+        g.out_f32 = (float*)(P.packed_early ? P.hpk : hbuf); g.ldo = D;
+        gemm(g);
     }
     // ---- positional conv embedding: h += GELU(grouped conv(h)) ----
     {
-        const int* pk_off = packed_early ? (const int*)d_rowoff : nullptr;
-        const int* pk_len = packed_early ? (const int*)d_frames : nullptr;
-        float* hcur = (float*)(packed_early ? hpk : hbuf);
-        { Timed t_(h, AMX_KC_OTHER); launch_posconv_pack(prec, hcur, N, T, D, c.pos_groups, c.pos_kernel / 2, Tpad, hg,
+        const int cg = P.cg, Tpad = P.Tpad;
+        const int* pk_off = P.packed_early ? (const int*)P.d_rowoff : nullptr;
+        const int* pk_len = P.packed_early ? (const int*)P.d_frames : nullptr;
+        float* hcur = (float*)(P.packed_early ? P.hpk : hbuf);
+        { Timed t_(h, AMX_KC_OTHER); launch_posconv_pack(prec, hcur, N, T, D, c.pos_groups, c.pos_kernel / 2, Tpad, P.hg,
                             (int64_t)N * Tpad * D, pk_off, pk_len, s); }
         // the window kernel where it takes the shape, the grouped implicit GEMM on the tile kernels otherwise
-        if (window_ok) {
+        if (P.window_ok) {
             Timed t_(h, AMX_KC_GEMM_TILE);
-            launch_posconv_window(prec, hg, (int64_t)N * Tpad * D, h->pos_w, (int64_t)D * cg * c.pos_kernel,
+            launch_posconv_window(prec, P.hg, (int64_t)N * Tpad * D, h->pos_w, (int64_t)D * cg * c.pos_kernel,
                                   (int64_t)cg * c.pos_kernel, h->pos_b, h->pos_r, hcur, N, T, Tpad, D, c.pos_groups, c.pos_kernel,
                                   pk_off, pk_len, s);
         } else {
-        GemmParams g{};
-        g.A = hg; g.a_plane = (int64_t)N * Tpad * D; g.lda = cg; g.rows_per_batch = T; g.a_batch_stride = (int64_t)Tpad * cg;
-        g.za = (int64_t)N * Tpad * cg;
-        g.W = h->pos_w; g.w_plane = (int64_t)D * cg * c.pos_kernel; g.ldw = (int64_t)cg * c.pos_kernel;
-        g.zw = (int64_t)cg * cg * c.pos_kernel;
-        g.M = (int)M; g.N = cg; g.K = cg * c.pos_kernel;
-        g.scale = h->pos_r; g.bias = h->pos_b; g.zbias = cg; g.act = 1;
-        g.residual = (const float*)hbuf; g.ldr = D; g.out_f32 = (float*)hbuf; g.ldo = D; g.zout = cg;
-        { Timed t_(h, AMX_KC_GEMM_TILE); launch_gemm_grouped(prec, g, c.pos_groups, s); }
+            GemmParams g{};
+            g.A = P.hg; g.a_plane = (int64_t)N * Tpad * D; g.lda = cg; g.rows_per_batch = T; g.a_batch_stride = (int64_t)Tpad * cg;
+            g.za = (int64_t)N * Tpad * cg;
+            g.W = h->pos_w; g.w_plane = (int64_t)D * cg * c.pos_kernel; g.ldw = (int64_t)cg * c.pos_kernel;
+            g.zw = (int64_t)cg * cg * c.pos_kernel;
+            g.M = (int)M; g.N = cg; g.K = cg * c.pos_kernel;
+            g.scale = h->pos_r; g.bias = h->pos_b; g.zbias = cg; g.act = 1;
+            g.residual = (const float*)hbuf; g.ldr = D; g.out_f32 = (float*)hbuf; g.ldo = D; g.zout = cg;
+            { Timed t_(h, AMX_KC_GEMM_TILE); launch_gemm_grouped(prec, g, c.pos_groups, s); }
         }
     }
     // ---- transformer encoder (pre-LN) ----
     void* const hpad = hbuf;     // the padded residual stream [N * T, D]
-    if (packed) {
-        if (!packed_early) { Timed t_(h, AMX_KC_OTHER); launch_pack_rows((const float*)hpad, (float*)hpk, (const int*)d_rowoff, (const int*)d_frames, N, T, D, false, s); }
-        hbuf = hpk;
+    if (P.packed) {
+        if (!P.packed_early) { Timed t_(h, AMX_KC_OTHER); launch_pack_rows((const float*)hpad, (float*)P.hpk, (const int*)P.d_rowoff, (const int*)P.d_frames, N, T, D, false, s); }
+        hbuf = P.hpk;
     }
     // A residual product that launch_gemm cuts into K chunks (short batches) leaves its fix-up -- slab sum + bias + residual
     // -> h -- to the LayerNorm that follows it: one kernel instead of the fix-up and a LayerNorm pass that re-reads h.
     struct { bool on = false; GemmParams g; int splits = 0; } pending;
-    bool refused = false;  // a fold product launch_gemm had no kernel for (never expected: P.fold checked these very params)
     auto residual_gemm = [&](GemmParams g, bool may_defer) {
         const int splits = may_defer ? gemm_planned_splits(prec, g) : 1;
         if (splits > 1 && fixup_rownorm_eligible(g)) {
@@ -2017,118 +1854,110 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
             pending.g = g;
             pending.splits = splits;
         }
-        { Timed t_(h, gemm_class(prec, g)); refused |= !launch_gemm(prec, g, s); }
+        gemm(g);
     };
     // LayerNorm of the residual stream (rows of hbuf) -> planes (and the fp32 rows, for the final one)
     auto stream_norm = [&](const float* gamma, const float* beta, int64_t rows, int64_t plane, float* out_ln) {
         Timed t_(h, AMX_KC_ROWNORM);
         if (pending.on) {
-            launch_fixup_rownorm(prec, pending.g, pending.splits, gamma, beta, c.eps, xp, plane, D, out_ln, D, s);
+            launch_fixup_rownorm(prec, pending.g, pending.splits, gamma, beta, c.eps, P.xp, plane, D, out_ln, D, s);
             pending.on = false;
         } else {
-            launch_rownorm(prec, (const float*)hbuf, D, rows, D, gamma, beta, 0, nullptr, nullptr, c.eps, 0.f, xp, plane, D, out_ln, D, s);
+            launch_rownorm(prec, (const float*)hbuf, D, rows, D, gamma, beta, 0, nullptr, nullptr, c.eps, 0.f, P.xp, plane, D, out_ln, D, s);
         }
     };
     // post-LN encoder (Wav2Vec2Encoder): h = LayerNorm(h + pos_conv(h)) first; every layer is h = LN1(h + attention(h)),
     // h = LN2(h + FFN(h)); hidden_states[layers] is the last layer's output as it is.  The LayerNorm passes write the fp32
     // rows back in place (the residual stream IS the normalised tensor) next to the planes the products read.
-    float* const ln_inplace = stable ? nullptr : (float*)hbuf;
-    if (!stable) stream_norm(h->fln_g, h->fln_b, Mrows, xp_plane, ln_inplace);
+    float* const ln_inplace = P.stable ? nullptr : (float*)hbuf;
+    if (!P.stable) stream_norm(h->fln_g, h->fln_b, P.Mrows, P.xp_plane, ln_inplace);
     // (pre-LN layers: gamma / beta of both norms live in the QKV / FFN1 weights -- fold_layer_norm at amx_create -- so a row pass
     // normalises with (1, 0))
     // the fold's padded frames (padded layout of a ragged batch, keys the attention masks) are written under a smaller scale: see
     // ln_plane_scale.  Without the attention mask every frame is a key, and none is padding.
-    const int* const fold_frames = packed || !masked ? nullptr : (const int*)d_frames_enc;
+    const int* const fold_frames = P.packed || !P.masked ? nullptr : P.d_frames_enc;
     auto ln_finalize = [&]() {
         Timed t_(h, AMX_KC_ROWNORM);
-        launch_ln_finalize((const float2*)ln_partial, D / 64, Mrows, c.eps, (float4*)ln_rowps, (float2*)ln_coef, fold_frames, T, s);
+        launch_ln_finalize((const float2*)P.ln_partial, D / 64, P.Mrows, c.eps, (float4*)P.ln_rowps, (float2*)P.ln_coef, fold_frames, T, s);
     };
     for (int l = 0; l < c.layers; ++l) {
         const Layer& ly = h->layers[l];
-        if (fold) {
+        if (P.fold) {
             // the first norm of the stack from the stream itself; later ones: the previous FFN2 left planes and statistics
             if (l == 0) {
                 Timed t_(h, AMX_KC_ROWNORM);
-                launch_ln_rowprep(prec, (const float*)hbuf, D, Mrows, D, c.eps, xp, xp_plane, D, (float4*)ln_rowps, (float2*)ln_coef,
+                launch_ln_rowprep(prec, (const float*)hbuf, D, P.Mrows, D, c.eps, P.xp, P.xp_plane, D, (float4*)P.ln_rowps, (float2*)P.ln_coef,
                                   fold_frames, T, s);
             }
-        } else if (stable) {
-            stream_norm(h->unit_g, h->zero_b, Mrows, xp_plane, nullptr);  // (completes the previous layer's FFN2 when that was deferred)
+        } else if (P.stable) {
+            stream_norm(h->unit_g, h->zero_b, P.Mrows, P.xp_plane, nullptr);  // (completes the previous layer's FFN2 when that was deferred)
         }
-        if (saved[l]) {
+        if (P.saved[l]) {
             // a classifier reads hidden state l (OUTPUT_l, acoustic_model.py:478-483): padded layout; with packed rows the padded
             // frames take their pre-encoder rows (finite, as meaningless as any padded frame) and the valid ones are scattered in
             // (packed_early: the classifiers read packed rows, the copy is the packed stream as it is)
-            if (packed_early) {
-                launch_copy(saved[l], hbuf, (size_t)Mp * D * 4, s);  // (a kernel, not a memcpy node: see launch_zero)
+            if (P.packed_early) {
+                launch_copy(P.saved[l], hbuf, (size_t)P.Mp * D * 4, s);  // (a kernel, not a memcpy node: see launch_zero)
             } else {
-                launch_copy(saved[l], packed ? hpad : hbuf, (size_t)M * D * 4, s);
-                if (packed) launch_pack_rows(saved[l], (float*)hbuf, (const int*)d_rowoff, (const int*)d_frames, N, T, D, true, s);
+                launch_copy(P.saved[l], P.packed ? hpad : hbuf, (size_t)M * D * 4, s);
+                if (P.packed) launch_pack_rows(P.saved[l], (float*)hbuf, (const int*)P.d_rowoff, (const int*)P.d_frames, N, T, D, true, s);
             }
         }
-        {
-            GemmParams g = P.qkv_params(ly);
-            if (fold) g = P.as_consumer(g, ly.c_qkv);
-            { Timed t_(h, gemm_class(prec, g)); refused |= !launch_gemm(prec, g, s); }
-        }
+        gemm(P.fold ? P.as_consumer(P.qkv_params(h, ly), ly.c_qkv) : P.qkv_params(h, ly));
         {
             AttnParams a{};
-            a.q = qb; a.k = kb; a.v = vtb;
-            a.qk_plane = qk_plane;
-            a.out = ao; a.out_plane = xp_plane;
-            a.frame_len = d_frames_enc;
-            a.N = N; a.H = H; a.T = T; a.Tp = packed ? TpTot : Tp; a.dh = dh; a.dhp = dhp;
-            a.row_off = packed ? (const int*)d_rowoff : nullptr;
-            a.order = packed ? (const int*)d_rowoff + N + 1 : nullptr;
+            a.q = P.qb; a.k = P.kb; a.v = P.vtb;
+            a.qk_plane = P.qk_plane;
+            a.out = P.ao; a.out_plane = P.xp_plane;
+            a.frame_len = P.d_frames_enc;
+            a.N = N; a.H = P.H; a.T = T; a.Tp = P.packed ? P.TpTot : P.Tp; a.dh = P.dh; a.dhp = P.dhp;
+            a.row_off = P.packed ? (const int*)P.d_rowoff : nullptr;
+            a.order = P.packed ? (const int*)P.d_rowoff + N + 1 : nullptr;
             { Timed t_(h, AMX_KC_ATTENTION); launch_attention(prec, a, s); }
         }
-        if (fold) {
-            residual_gemm(P.as_producer(P.oproj_params(ly), false), false);  // (nothing reads the stream between the two halves of a layer)
+        if (P.fold) {
+            residual_gemm(P.as_producer(P.oproj_params(h, ly), false), false);  // (nothing reads the stream between the two halves of a layer)
             ln_finalize();
         } else {
-            residual_gemm(P.oproj_params(ly), true);
+            residual_gemm(P.oproj_params(h, ly), true);
             // pre-LN: the LayerNorm in front of the FFN (`final_layer_norm`); post-LN: `layer_norm` behind the attention residual
-            if (stable) stream_norm(h->unit_g, h->zero_b, Mrows, xp_plane, nullptr);
-            else stream_norm(ly.ln1_g, ly.ln1_b, Mrows, xp_plane, ln_inplace);
+            if (P.stable) stream_norm(h->unit_g, h->zero_b, P.Mrows, P.xp_plane, nullptr);
+            else stream_norm(ly.ln1_g, ly.ln1_b, P.Mrows, P.xp_plane, ln_inplace);
         }
-        {
-            GemmParams g = P.ffn1_params(ly);
-            if (fold) g = P.as_consumer(g, ly.c_1);
-            { Timed t_(h, gemm_class(prec, g)); refused |= !launch_gemm(prec, g, s); }
-        }
-        if (fold && (l + 1 < c.layers || stream_in_planes)) {
+        gemm(P.fold ? P.as_consumer(P.ffn1_params(h, ly), ly.c_1) : P.ffn1_params(h, ly));
+        if (P.fold && (l + 1 < c.layers || P.stream_in_planes)) {
             // fp32 rows where the next reader needs them: hidden state l + 1 is published, or this is the last layer (final LayerNorm,
             // unpacking); the last layer's planes and statistics have no reader (it is a producer for the residual's sake)
             const bool last = l + 1 == c.layers;
-            residual_gemm(P.as_producer(P.ffn2_params(ly), last || saved[l + 1] != nullptr), false);
+            residual_gemm(P.as_producer(P.ffn2_params(h, ly), last || P.saved[l + 1] != nullptr), false);
             if (!last) ln_finalize();
         } else {
             // (the last layer of a packed batch is followed by the unpacking, not by a LayerNorm of these rows)
-            residual_gemm(P.ffn2_params(ly), !fold && !(packed && !packed_early && l == c.layers - 1));
+            residual_gemm(P.ffn2_params(h, ly), !P.fold && !(P.packed && !P.packed_early && l == c.layers - 1));
         }
-        if (!stable) stream_norm(ly.ln2_g, ly.ln2_b, Mrows, xp_plane, ln_inplace);  // `final_layer_norm` closes the post-LN layer
+        if (!P.stable) stream_norm(ly.ln2_g, ly.ln2_b, P.Mrows, P.xp_plane, ln_inplace);  // `final_layer_norm` closes the post-LN layer
     }
     if (refused) return fail(h, AMX_EINVAL, "internal: an encoder product of the LayerNorm fold had no kernel for its plan and was not launched");
-    if (packed && !packed_early) {
+    if (P.packed && !P.packed_early) {
         // back to the padded layout for the final LayerNorm and the projection (padded frames keep their pre-encoder rows)
-        { Timed t_(h, AMX_KC_OTHER); launch_pack_rows((const float*)hpad, (float*)hpk, (const int*)d_rowoff, (const int*)d_frames, N, T, D, true, s); }
+        { Timed t_(h, AMX_KC_OTHER); launch_pack_rows((const float*)hpad, (float*)P.hpk, (const int*)P.d_rowoff, (const int*)P.d_frames, N, T, D, true, s); }
         hbuf = hpad;
     }
-    if (stable) {
-        stream_norm(h->fln_g, h->fln_b, Mh, pln(h, Mh * D), (float*)hfin);
-    } else if (keep) {
+    if (P.stable) {
+        stream_norm(h->fln_g, h->fln_b, Mh, pln(h, Mh * D), (float*)P.hfin);
+    } else if (P.keep) {
         // post-LN: hidden_states[layers] = the stream as the last layer left it (hfin_rows); its planes are in xp already
-        launch_copy(hfin, hbuf, (size_t)Mh * D * 4, s);
+        launch_copy(P.hfin, hbuf, (size_t)Mh * D * 4, s);
     }
 
     // ---- hierarchical projection ----
     for (auto& st : h->steps) {
-        const void* A = xp;
+        const void* A = P.xp;
         int64_t a_plane = pln(h, Mh * D), lda = D;
         if (!st.direct_output) {
-            { Timed t_(h, AMX_KC_OTHER); launch_concat(prec, st.parts_dev, (int)st.parts.size(), (const float*)logits, h->ld_logits, Mh, cat,
+            { Timed t_(h, AMX_KC_OTHER); launch_concat(prec, st.parts_dev, (int)st.parts.size(), (const float*)P.logits, h->ld_logits, Mh, P.cat,
                           pln(h, Mh * st.Kpad), st.Kpad, st.Kpad, s); }
-            A = cat; a_plane = pln(h, Mh * st.Kpad); lda = st.Kpad;
+            A = P.cat; a_plane = pln(h, Mh * st.Kpad); lda = st.Kpad;
         }
         GemmParams g{};
         g.A = A; g.a_plane = a_plane; g.lda = lda; g.rows_per_batch = Mh;
@@ -2138,46 +1967,137 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         if (st.time_heads > 0) {
             // ProjectingMultiheadAttention.forward (acoustic_model.py:255-268)
             const int Co = st.rows, Cp = st.Cpad;
-            g.out_f32 = (float*)tl_x; g.ldo = Co;
-            { Timed t_(h, gemm_class(prec, g)); run_gemm(prec, g, s); }
-            { Timed t_(h, AMX_KC_OTHER); launch_time_ln_pe(prec, (const float*)tl_x, Mh, Co, T, st.tl_g, st.tl_b, 1e-5f, st.tl_pe, tl_p,
+            g.out_f32 = (float*)P.tl_x; g.ldo = Co;
+            gemm(g);
+            { Timed t_(h, AMX_KC_OTHER); launch_time_ln_pe(prec, (const float*)P.tl_x, Mh, Co, T, st.tl_g, st.tl_b, 1e-5f, st.tl_pe, P.tl_p,
                               pln(h, Mh * Cp), Cp, s); }
             GemmParams gi{};
-            gi.A = tl_p; gi.a_plane = pln(h, Mh * Cp); gi.lda = Cp; gi.rows_per_batch = Mh;
+            gi.A = P.tl_p; gi.a_plane = pln(h, Mh * Cp); gi.lda = Cp; gi.rows_per_batch = Mh;
             gi.W = st.tl_win; gi.w_plane = pln(h, (int64_t)3 * Co * Cp); gi.ldw = Cp;
             gi.M = (int)Mh; gi.N = 3 * Co; gi.K = Cp;
             gi.scale = st.r_tin; gi.bias = st.tl_bin;
-            gi.out_f32 = (float*)tl_qkv; gi.ldo = 3 * Co;
-            { Timed t_(h, gemm_class(prec, gi)); run_gemm(prec, gi, s); }
-            { Timed t_(h, AMX_KC_OTHER); launch_time_attention(prec, (const float*)tl_qkv, (const int*)d_frames, N, T, Co, st.time_heads,
-                                  tl_p, pln(h, Mh * Cp), Cp, s); }
+            gi.out_f32 = (float*)P.tl_qkv; gi.ldo = 3 * Co;
+            gemm(gi);
+            { Timed t_(h, AMX_KC_OTHER); launch_time_attention(prec, (const float*)P.tl_qkv, (const int*)P.d_frames, N, T, Co, st.time_heads,
+                                  P.tl_p, pln(h, Mh * Cp), Cp, s); }
             // out_proj lands where the plain linear classifier would have written
             g = GemmParams{};
-            g.A = tl_p; g.a_plane = pln(h, Mh * Cp); g.lda = Cp; g.rows_per_batch = Mh;
+            g.A = P.tl_p; g.a_plane = pln(h, Mh * Cp); g.lda = Cp; g.rows_per_batch = Mh;
             g.W = st.tl_wout; g.w_plane = pln(h, (int64_t)Co * Cp); g.ldw = Cp;
             g.M = (int)Mh; g.N = Co; g.K = Cp;
             g.scale = st.r_tout; g.bias = st.tl_bout;
         }
         if (st.composed) {
-            g.out_p = ebuf; g.out_plane = pln(h, Mh * Eld); g.ldp = Eld;
-            { Timed t_(h, gemm_class(prec, g)); run_gemm(prec, g, s); }
+            g.out_p = P.ebuf; g.out_plane = pln(h, Mh * P.Eld); g.ldp = P.Eld;
+            gemm(g);
             // logits = (e @ composed) / sqrt(E)   (acoustic_model.py:234)
+            const auto& inv = cur_inv(h);
             GemmParams g2{};
-            g2.A = ebuf; g2.a_plane = pln(h, Mh * Eld); g2.lda = Eld; g2.rows_per_batch = Mh;
-            g2.W = h->composed_w; g2.w_plane = pln(h, (int64_t)h->P1 * Eld); g2.ldw = Eld;
-            g2.M = (int)Mh; g2.N = h->P1; g2.K = E;
-            g2.scale = h->r_composed / sqrtf((float)E);
-            g2.out_f32 = (float*)logits + h->col[st.classes[0]]; g2.ldo = h->ld_logits;
-            { Timed t_(h, gemm_class(prec, g2)); run_gemm(prec, g2, s); }
+            g2.A = P.ebuf; g2.a_plane = pln(h, Mh * P.Eld); g2.lda = P.Eld; g2.rows_per_batch = Mh;
+            g2.W = inv.composed_w; g2.w_plane = pln(h, (int64_t)inv.P1 * P.Eld); g2.ldw = P.Eld;
+            g2.M = (int)Mh; g2.N = inv.P1; g2.K = P.E;
+            g2.scale = inv.r_composed / sqrtf((float)P.E);
+            g2.out_f32 = (float*)P.logits + h->col[st.classes[0]]; g2.ldo = h->ld_logits;
+            gemm(g2);
         } else {
-            g.out_f32 = (float*)logits + h->col[st.classes[0]]; g.ldo = h->ld_logits;
-            { Timed t_(h, gemm_class(prec, g)); run_gemm(prec, g, s); }
+            g.out_f32 = (float*)P.logits + h->col[st.classes[0]]; g.ldo = h->ld_logits;
+            gemm(g);
         }
     }
-    { Timed t_(h, AMX_KC_OTHER); launch_logsoftmax_out(h->out_unique_dev, (int)h->out_unique.size(), (const float*)logits, h->ld_logits, N, T,
-                          (const int*)d_frames, (flags & AMX_FLAG_RAW_LOGITS) ? 0 : 1, d_out, h->nonfinite,
-                          packed_early ? (const int*)d_rowoff : nullptr, s); }
+    { Timed t_(h, AMX_KC_OTHER); launch_logsoftmax_out(cur_inv(h).out_unique_dev, (int)h->out_unique.size(), (const float*)P.logits, h->ld_logits, N, T,
+                          (const int*)P.d_frames, (P.flags & AMX_FLAG_RAW_LOGITS) ? 0 : 1, P.d_out, h->nonfinite,
+                          P.packed_early ? (const int*)P.d_rowoff : nullptr, s); }
     HIPCHK(h, hipGetLastError());
+    return AMX_OK;
+}
+
+// what a recording of a pass is keyed on: its buffers, geometry, flags, inventory, the workspace generation and the stream, and
+// the lengths where they size grids and tile lists
+constexpr size_t KEY_WS_GEN = 8;  // key[KEY_WS_GEN]: the workspace generation (ws_get) the recording's pointers belong to
+static std::vector<int64_t> graph_key(amx_handle h, const PassPlan& P, const int64_t* lengths, hipStream_t s) {
+    std::vector<int64_t> key;
+    key.reserve(10 + (size_t)P.N);
+    key.insert(key.end(), {(int64_t)(intptr_t)P.d_audio, (int64_t)(intptr_t)P.d_out, (int64_t)P.N, P.L, (int64_t)P.flags,
+                           (int64_t)P.needs_qkv_zero, (int64_t)h->inv, (int64_t)cur_inv(h).generation, (int64_t)h->ws_gen});
+    // (the stream is part of the key: an executable graph is launched on one stream at a time -- a handle is meant for one
+    // stream, include/allophant_amx.h, but a caller that moves to another one gets a recording of its own, not a shared one)
+    key.push_back((int64_t)(intptr_t)s);
+    // A recording is keyed on GEOMETRY where it can be (ABI 6): in the padded layout without tile skipping every kernel reads
+    // lengths / frame counts / masks from the device buffers the plan region has just refreshed (no length travels by value in a
+    // kernel node), so batches of one (N, L) with different lengths -- the reference's loop feeds a new batch every iteration,
+    // run.py:742-753 -- replay one recording.  Packed rows and skipped conv tiles size grids and tile lists by the lengths:
+    // those passes keep them in the key.
+    key.push_back(P.packed ? 2 : (P.ragged ? 1 : 0));
+    if (P.packed || P.ragged) key.insert(key.end(), lengths, lengths + P.N);
+    return key;
+}
+
+// The recording cache of amx_forward: replays the graph of a pass whose key was recorded, records one for a key that ran eagerly
+// among the last few passes (and launches it), and otherwise notes the key.  `done`: the pass has been launched.
+static int run_recorded(amx_handle h, const PassPlan& P, const int64_t* lengths, hipStream_t s, bool& done) {
+    std::vector<int64_t> key = graph_key(h, P, lengths, s);
+    if (!h->graphs.empty() && h->graphs.front().key[KEY_WS_GEN] != (int64_t)h->ws_gen) {
+        // a workspace buffer moved since these were recorded (ws_get synchronised the device before freeing it)
+        drop_graphs(h);
+    }
+    for (auto& g : h->graphs)
+        if (g.key == key) {
+            HIPCHK(h, hipGraphLaunch(g.exec, s));
+            g.last_use = ++h->graph_clock;
+            g.last_stream = s;
+            ++h->graph_replays;
+            h->last_graph = 2;
+            done = true;
+            return AMX_OK;
+        }
+    if (std::find(h->graph_seen.begin(), h->graph_seen.end(), key) == h->graph_seen.end()) {
+        if ((int)h->graph_seen.size() >= amx_handle_s::GRAPH_SEEN) h->graph_seen.erase(h->graph_seen.begin());
+        h->graph_seen.push_back(std::move(key));
+        return AMX_OK;
+    }
+    // this key ran eagerly a moment ago: record it.  Capture runs on a private stream (the caller's may be the null stream, which
+    // cannot be captured) in thread-local mode; nothing executes until the launch below.
+    if (!h->capture_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking));
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    if (hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+        (void)hipGetLastError();
+        h->graph_broken = true;
+        return AMX_OK;
+    }
+    const int erc = enqueue_pass(h, P, h->capture_stream);
+    const hipError_t end = hipStreamEndCapture(h->capture_stream, &graph);
+    if (erc) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return erc;
+    }
+    if (end != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipGetLastError();
+        h->graph_broken = true;  // this runtime does not record the pass: stay eager from here on
+        return AMX_OK;
+    }
+    if ((int)h->graphs.size() >= amx_handle_s::GRAPH_CAP) {
+        // evict the least recently used recording once nothing on the stream can still be running it
+        size_t lru = 0;
+        for (size_t i = 1; i < h->graphs.size(); ++i)
+            if (h->graphs[i].last_use < h->graphs[lru].last_use) lru = i;
+        HIPCHK(h, hipStreamSynchronize(h->graphs[lru].last_stream));  // (its last launch may be on another stream than `s`)
+        (void)hipGraphExecDestroy(h->graphs[lru].exec);
+        if (h->graphs[lru].graph) (void)hipGraphDestroy(h->graphs[lru].graph);
+        h->graphs.erase(h->graphs.begin() + (long)lru);
+    }
+    HIPCHK(h, hipGraphLaunch(exec, s));
+    amx_handle_s::GraphEntry entry;
+    entry.key = std::move(key);
+    entry.exec = exec;
+    entry.graph = graph;
+    entry.last_use = ++h->graph_clock;
+    entry.last_stream = s;
+    h->graphs.push_back(std::move(entry));
+    ++h->graph_captures;
+    h->last_graph = 1;
+    done = true;
     return AMX_OK;
 }
 
@@ -2197,114 +2117,27 @@ extern "C" int amx_forward(amx_handle h, const float* audio, const int64_t* leng
     if (rc) return rc;
     PassPlan P;
     if ((rc = plan_pass(h, audio, lengths, N, L, out, out_lengths, flags, s, P))) return rc;
-    const float* const d_audio = P.d_audio;
-    float* const d_out = P.d_out;
-    const bool needs_qkv_zero = P.needs_qkv_zero, packed = P.packed, ragged = P.ragged, packed_early = P.packed_early, keep = P.keep;
-    const int64_t total = P.total;
-    const int T = P.T;
-    auto enqueue = [&](hipStream_t stream) -> int { return enqueue_pass(h, P, stream); };
 
     // ---- run the pass: replay its graph, record one, or enqueue it eagerly ----
     const bool graph_ok = !h->graph_broken && !(flags & (AMX_FLAG_NO_GRAPH | AMX_FLAG_TIMING | AMX_FLAG_KEEP_HIDDEN));
     bool done = false;
-    if (graph_ok) {
-        std::vector<int64_t> key;
-        key.reserve(10 + (size_t)N);
-        key.insert(key.end(), {(int64_t)(intptr_t)d_audio, (int64_t)(intptr_t)d_out, (int64_t)N, L, (int64_t)flags, (int64_t)needs_qkv_zero,
-                               (int64_t)h->inv, (int64_t)h->inventories[h->inv].generation, (int64_t)h->ws_gen});
-        // (the stream is part of the key: an executable graph is launched on one stream at a time -- a handle is meant for one
-        // stream, include/allophant_amx.h, but a caller that moves to another one gets a recording of its own, not a shared one)
-        key.push_back((int64_t)(intptr_t)s);
-        // A recording is keyed on GEOMETRY where it can be (ABI 6): in the padded layout without tile skipping every kernel reads
-        // lengths / frame counts / masks from the device buffers the plan region has just refreshed (no length travels by value in a
-        // kernel node), so batches of one (N, L) with different lengths -- the reference's loop feeds a new batch every iteration,
-        // run.py:742-753 -- replay one recording.  Packed rows and skipped conv tiles size grids and tile lists by the lengths:
-        // those passes keep them in the key.
-        key.push_back(packed ? 2 : (ragged ? 1 : 0));
-        if (packed || ragged) key.insert(key.end(), lengths, lengths + N);
-        if (!h->graphs.empty() && h->graphs.front().key.size() >= 11 && h->graphs.front().key[8] != (int64_t)h->ws_gen) {
-            // a workspace buffer moved since these were recorded (ws_get synchronised the device before freeing it)
-            drop_graphs(h);
-        }
-        for (auto& g : h->graphs)
-            if (g.key == key) {
-                HIPCHK(h, hipGraphLaunch(g.exec, s));
-                g.last_use = ++h->graph_clock;
-                g.last_stream = s;
-                ++h->graph_replays;
-                h->last_graph = 2;
-                done = true;
-                break;
-            }
-        const bool seen_before = std::find(h->graph_seen.begin(), h->graph_seen.end(), key) != h->graph_seen.end();
-        if (!done && seen_before) {
-            // this key ran eagerly a moment ago: record it.  Capture runs on a private stream (the caller's may be the null
-            // stream, which cannot be captured) in thread-local mode; nothing executes until the launch below.
-            if (!h->capture_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int erc = enqueue(h->capture_stream);
-                const hipError_t end = hipStreamEndCapture(h->capture_stream, &graph);
-                if (erc) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    return erc;
-                }
-                if (end == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    if ((int)h->graphs.size() >= amx_handle_s::GRAPH_CAP) {
-                        // evict the least recently used recording once nothing on the stream can still be running it
-                        size_t lru = 0;
-                        for (size_t i = 1; i < h->graphs.size(); ++i)
-                            if (h->graphs[i].last_use < h->graphs[lru].last_use) lru = i;
-                        HIPCHK(h, hipStreamSynchronize(h->graphs[lru].last_stream));  // (its last launch may be on another stream than `s`)
-                        (void)hipGraphExecDestroy(h->graphs[lru].exec);
-                        if (h->graphs[lru].graph) (void)hipGraphDestroy(h->graphs[lru].graph);
-                        h->graphs.erase(h->graphs.begin() + (long)lru);
-                    }
-                    HIPCHK(h, hipGraphLaunch(exec, s));
-                    amx_handle_s::GraphEntry entry;
-                    entry.key = key;
-                    entry.exec = exec;
-                    entry.graph = graph;
-                    entry.last_use = ++h->graph_clock;
-                    entry.last_stream = s;
-                    h->graphs.push_back(std::move(entry));
-                    ++h->graph_captures;
-                    h->last_graph = 1;
-                    done = true;
-                } else {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    (void)hipGetLastError();
-                    h->graph_broken = true;  // this runtime does not record the pass: stay eager from here on
-                }
-            } else {
-                (void)hipGetLastError();
-                h->graph_broken = true;
-            }
-        }
-        if (!done && !seen_before) {
-            if ((int)h->graph_seen.size() >= amx_handle_s::GRAPH_SEEN) h->graph_seen.erase(h->graph_seen.begin());
-            h->graph_seen.push_back(std::move(key));
-        }
-    }
-    if (!done && (rc = enqueue(s))) return rc;
+    if (graph_ok && (rc = run_recorded(h, P, lengths, s, done))) return rc;
+    if (!done && (rc = enqueue_pass(h, P, s))) return rc;
     // the pass's non-finite frame count travels to a pinned slot behind it; the next call reads it (see range_poll)
     if (!(flags & AMX_FLAG_NO_RANGE_CHECK) && (rc = range_record(h, (flags & AMX_FLAG_CONTINUE) != 0, s))) return rc;
     if (flags & AMX_FLAG_HOST_IO) {
-        HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(out, P.d_out, (size_t)P.total * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
     }
-    bool report_now = false;
-    if ((flags & AMX_FLAG_HOST_IO) && !(flags & AMX_FLAG_NO_RANGE_CHECK)) report_now = true;
-    h->last_N = N; h->last_L = L; h->last_T = T; h->last_keep = keep;
-    h->last_packed_rows = packed_early;
-    if (packed_early) {
+    h->last_N = N; h->last_L = L; h->last_T = P.T; h->last_keep = P.keep;
+    h->last_packed_rows = P.packed_early;
+    if (P.packed_early) {
         h->last_rowoff = P.rowoff_host;
         h->last_frames = P.frames_host;
     }
-    h->qkv_dirty = packed;  // a packed call leaves other rows in the Q / K / V planes: the next padded call re-zeroes them
+    h->qkv_dirty = P.packed;  // a packed call leaves other rows in the Q / K / V planes: the next padded call re-zeroes them
     // a host-I/O call has synchronised and handed the outputs over already: its own range report does not wait for the next call
-    if (report_now && (rc = range_poll(h, true))) return rc;
+    if ((flags & AMX_FLAG_HOST_IO) && !(flags & AMX_FLAG_NO_RANGE_CHECK) && (rc = range_poll(h, true))) return rc;
     return AMX_OK;
 }
 
@@ -2352,6 +2185,21 @@ extern "C" int amx_graph_info(amx_handle h, int64_t* captures, int64_t* replays)
     return AMX_OK;
 }
 
+// the frame counts of a decode call: each in [0, T] of the output block, uploaded as int32
+static int upload_frame_lengths(amx_handle h, const int64_t* frame_lengths, int N, int T, hipStream_t s, const int** d_fl) {
+    std::vector<int> fl(N);
+    for (int n = 0; n < N; ++n) {
+        if (frame_lengths[n] < 0 || frame_lengths[n] > T) return fail(h, AMX_EINVAL, "frame length out of range");
+        fl[n] = (int)frame_lengths[n];
+    }
+    void* d;
+    if (int rc = ws_get(h, "ctc_frames", (size_t)N * 4, &d)) return rc;
+    HIPCHK(h, hipMemcpyAsync(d, fl.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));  // fl is pageable host memory
+    *d_fl = (const int*)d;
+    return AMX_OK;
+}
+
 extern "C" int amx_greedy_ctc(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
                               int64_t* tokens, int64_t* timesteps, int32_t* counts, float* scores, void* stream) {
     if (!h || !out || !frame_lengths || !tokens || !timesteps || !counts || !scores) return AMX_EINVAL;
@@ -2360,16 +2208,9 @@ extern "C" int amx_greedy_ctc(amx_handle h, const float* out, const int64_t* fra
     int rc = compute_layout(h, N, L);  // output block geometry is a function of (N, L, inventory) only
     if (rc) return rc;
     const int T = (int)h->layout_T;
-    std::vector<int> fl(N);
-    for (int n = 0; n < N; ++n) {
-        if (frame_lengths[n] < 0 || frame_lengths[n] > T) return fail(h, AMX_EINVAL, "frame length out of range");
-        fl[n] = (int)frame_lengths[n];
-    }
-    void* d_fl;
-    if ((rc = ws_get(h, "ctc_frames", (size_t)N * 4, &d_fl))) return rc;
-    HIPCHK(h, hipMemcpyAsync(d_fl, fl.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));  // fl is pageable host memory
-    launch_greedy_ctc(h->out_all_dev, (int)h->out_all.size(), out, (const int*)d_fl, N, T, tokens, timesteps, counts, scores, s);
+    const int* d_fl;
+    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
+    launch_greedy_ctc(cur_inv(h).out_all_dev, (int)h->out_all.size(), out, d_fl, N, T, tokens, timesteps, counts, scores, s);
     HIPCHK(h, hipGetLastError());
     return AMX_OK;
 }
@@ -2431,16 +2272,9 @@ extern "C" int amx_beam_ctc(amx_handle h, const float* out, const int64_t* frame
     amx_beam_ctc_workspace(beam_width, rows, T, &need);
     if (workspace_bytes < need || (need && !workspace))
         return fail(h, AMX_EINVAL, "beam-search workspace too small: " + std::to_string(need) + " bytes needed");
-    std::vector<int> fl(N);
-    for (int n = 0; n < N; ++n) {
-        if (frame_lengths[n] < 0 || frame_lengths[n] > T) return fail(h, AMX_EINVAL, "frame length out of range");
-        fl[n] = (int)frame_lengths[n];
-    }
-    void* d_fl;
-    if ((rc = ws_get(h, "ctc_frames", (size_t)N * 4, &d_fl))) return rc;
-    HIPCHK(h, hipMemcpyAsync(d_fl, fl.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));  // fl is pageable host memory
-    launch_beam_ctc(h->out_all_dev, (int)h->out_all.size(), out, (const int*)d_fl, N, T, beam_width, n_best,
+    const int* d_fl;
+    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
+    launch_beam_ctc(cur_inv(h).out_all_dev, (int)h->out_all.size(), out, d_fl, N, T, beam_width, n_best,
                     (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores, hyp_counts, s);
     HIPCHK(h, hipGetLastError());
     return AMX_OK;
