@@ -3,6 +3,7 @@
 #include "../../include/allophant_amx.h"
 #include "../../include/allophant_amx_allophones.h"
 #include "../../include/allophant_amx_beam.h"
+#include "../../include/allophant_amx_resample.h"
 #include "amx_common.h"
 
 #include <algorithm>
@@ -2301,6 +2302,36 @@ extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_
                               (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores,
                               hyp_counts, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "beam-search kernel launch failed");
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// sinc resampling
+// =================================================================================================================
+extern "C" int amx_resample_bank(int64_t orig_freq, int64_t new_freq, int32_t lowpass_filter_width, double rolloff,
+                                 amx_resample_geometry* geometry, float* bank, int32_t* phases) {
+    if (!geometry) return fail(nullptr, AMX_EINVAL, "null geometry pointer");
+    amx_resample_geometry g{};
+    const std::string err = resample_bank(orig_freq, new_freq, lowpass_filter_width, rolloff, &g, bank, phases);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    *geometry = g;
+    return AMX_OK;
+}
+
+extern "C" int amx_resample(int device, const float* x, int64_t stride, int64_t L_in, const int64_t* lengths,
+                            const amx_resample_row* rows, const float* bank, const int32_t* phases, int64_t window, int N,
+                            int64_t L_out, float* y, void* stream) {
+    if (N < 0 || L_in < 0 || L_out < 0) return fail(nullptr, AMX_EINVAL, "negative resampling geometry");
+    if (N > 65535) return fail(nullptr, AMX_EINVAL, "at most 65535 utterances per call");
+    if (L_out > ((int64_t)1 << 40)) return fail(nullptr, AMX_EINVAL, "L_out exceeds 2^40 samples");
+    if (window < 0 || window > AMX_RESAMPLE_MAX_WINDOW)
+        return fail(nullptr, AMX_EINVAL, "window must be 0 to " + std::to_string(AMX_RESAMPLE_MAX_WINDOW));
+    if (N > 1 && stride < L_in) return fail(nullptr, AMX_EINVAL, "row stride below L_in");
+    if (N == 0 || L_out == 0) return AMX_OK;
+    if (!x || !lengths || !rows || !y || (window > 0 && (!bank || !phases))) return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_resample(x, stride, L_in, lengths, rows, bank, phases, (int)window, N, L_out, y, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "resampling kernel launch failed");
     return AMX_OK;
 }
 

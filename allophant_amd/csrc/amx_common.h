@@ -2,7 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 #include <type_traits>
+
+struct amx_resample_geometry;  // include/allophant_amx_resample.h
+struct amx_resample_row;
 
 namespace amx {
 
@@ -488,6 +492,15 @@ int allophone_frames(int P1);
 void launch_allophone_map(const float* phone, int64_t stride_t, int64_t stride_n, const int* language_ids, int n_lang, int N,
                           int64_t T, int P1, int Q1, const int* col_ptr, const int* ent_p, const float* ent_w,
                           const float* col_init, float* out, hipStream_t s);
+
+// sinc resampling (amx_resample.hip): torchaudio's sinc_interp_hann resampler, contract in include/allophant_amx_resample.h.
+// resample_bank is host code (the filter bank in float64, rounded to fp32; "" or the reason the arguments are refused);
+// launch_resample covers (row, tile of RS_TILE output samples) and stages up to `window` input floats per tile in LDS.
+constexpr int RS_TILE = 1024;
+std::string resample_bank(int64_t orig, int64_t new_rate, int32_t lpw, double rolloff, amx_resample_geometry* g, float* bank,
+                          int32_t* phases);
+void launch_resample(const float* x, int64_t stride, int64_t L_in, const int64_t* lengths, const amx_resample_row* rows,
+                     const float* bank, const int32_t* phases, int window, int N, int64_t L_out, float* y, hipStream_t s);
 
 // weight packing helpers (device side; run once at amx_create / amx_set_inventory)
 void launch_pack_matrix(int prec, const float* src, int rows, int cols, int64_t src_row_stride, int64_t src_col_stride,

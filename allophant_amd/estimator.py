@@ -10,6 +10,7 @@ Mirrors (reference file:line):
   * ``BeamCTCDecoder``, ``_ctc_decoder``, ``feature_decoders``  allophant/predictions.py:210-254
   * ``Estimator.map_allophones``  allophant/estimator.py:1048-1049 -> AllophoneMapping.map_allophones
                              (allophant/network/acoustic_model.py:142-159)
+  * ``Estimator.sample_rate``  allophant/estimator.py:940; ``Estimator.resample`` applies ``resample.resample_batch``
 
 PyTorch is used only as plumbing (device memory for inputs/outputs, the current HIP stream); all arithmetic happens in the
 HIP kernels behind the C ABI.
@@ -240,6 +241,7 @@ def _spec_to_structs(spec: Dict[str, Any], precision: str):
     return cfg, descs
 
 
+SAMPLE_RATE = 16000  # the audio rate of every reference model (checkpoint.py checks it on restore)
 ALLOPHONE_MATRICES_KEY = "_projection._layers.phoneme._allophone_layer._allophone_matrices"
 _NO_ALLOPHONE_LAYER = "Can't map phones to allophones with a model without an allophone layer"  # acoustic_model.py:546
 
@@ -306,6 +308,21 @@ class Estimator:
     @property
     def device_bytes(self) -> int:
         return int(self._lib.amx_device_bytes(self._handle))
+
+    @property
+    def sample_rate(self) -> int:
+        """The rate ``predict`` expects (reference estimator.py:940; every upstream model is trained at 16 kHz)."""
+        return SAMPLE_RATE
+
+    def resample(self, batch: Batch, sample_rates) -> Batch:
+        """``resample.resample_batch(batch, sample_rates, self.sample_rate)`` on this estimator's device: a padded batch at
+        source rates (one per utterance, mixed freely) -> the 16 kHz batch ``predict`` takes, in one launch.  Upstream
+        resamples each utterance on the host before ``predict`` (README recipe; speech_corpus.py ``Resample(sr, 16000)``)."""
+        from .resample import resample_batch
+
+        if batch.audio_features.device != self._device:
+            batch = batch.to(self._device)
+        return resample_batch(batch, sample_rates, self.sample_rate)
 
     @classmethod
     def restore(cls, checkpoint_or_path, device: str = "cuda:0", precision: str = "f16x3"):

@@ -42,6 +42,10 @@ ALLOPHONE_EXPORTS = ["amx_set_allophones", "amx_map_allophones"]
 BEAM_EXPORTS = ["amx_beam_ctc_workspace", "amx_beam_ctc", "amx_beam_ctc_emissions"]
 BEAM_EXP_EMISSIONS = 1  # AMX_BEAM_EXP_EMISSIONS
 BEAM_MAX_WIDTH = 64
+# the sinc-resampling entry points (include/allophant_amx_resample.h; added to ABI 6, detected by name)
+RESAMPLE_EXPORTS = ["amx_resample_bank", "amx_resample"]
+RESAMPLE_MAX_PHASES = 4096  # AMX_RESAMPLE_MAX_PHASES
+RESAMPLE_MAX_WINDOW = 16384  # AMX_RESAMPLE_MAX_WINDOW
 
 
 def dep_output_layer(i: int) -> int:
@@ -73,6 +77,14 @@ class AmxTensor(C.Structure):
 
 class AmxOutputDesc(C.Structure):
     _fields_ = [("name", C.c_char * AMX_NAME_LEN), ("classes", C.c_int32), ("offset", C.c_int64)]
+
+
+class AmxResampleGeometry(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("o", "m", "width", "taps", "bank_size", "window")]
+
+
+# amx_resample_row: six int64 fields, built by the binding as an int64 [N, 6] tensor in this order
+RESAMPLE_ROW_FIELDS = ("o", "m", "width", "taps", "bank_offset", "phase_offset")
 
 
 _lib: Optional[C.CDLL] = None
@@ -125,6 +137,11 @@ def load() -> C.CDLL:
         lib.amx_beam_ctc_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, i32, i32, C.c_uint32, vp, C.c_size_t,
                                                vp, vp, vp, vp, vp, vp]
         lib.amx_beam_ctc_emissions.restype = i32
+    if hasattr(lib, "amx_resample"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_resample_bank.argtypes = [i64, i64, C.c_int32, C.c_double, C.POINTER(AmxResampleGeometry), vp, vp]
+        lib.amx_resample_bank.restype = i32
+        lib.amx_resample.argtypes = [i32, vp, i64, i64, vp, vp, vp, vp, i64, i32, i64, vp, vp]
+        lib.amx_resample.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
