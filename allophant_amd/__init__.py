@@ -7,7 +7,8 @@ compute path without the built ``liballophant_amx.so`` raises.
 from . import spec, synthetic  # noqa: F401
 
 __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCDecoder", "CTCHypothesis", "BeamCTCDecoder",
-           "BeamDecoded", "feature_decoders"]
+           "BeamDecoded", "feature_decoders", "EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator",
+           "levensthein_statistics", "levensthein_statistics_batch"]
 __version__ = "0.1.0"
 
 
@@ -18,4 +19,9 @@ def __getattr__(name):
         from . import estimator
 
         return getattr(estimator, name)
+    if name in ("EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator", "levensthein_statistics",
+                "levensthein_statistics_batch"):
+        from . import evaluation
+
+        return getattr(evaluation, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

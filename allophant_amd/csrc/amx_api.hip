@@ -4,6 +4,7 @@
 #include "../../include/allophant_amx_allophones.h"
 #include "../../include/allophant_amx_beam.h"
 #include "../../include/allophant_amx_resample.h"
+#include "../../include/allophant_amx_edit.h"
 #include "amx_common.h"
 
 #include <algorithm>
@@ -2332,6 +2333,58 @@ extern "C" int amx_resample(int device, const float* x, int64_t stride, int64_t 
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_resample(x, stride, L_in, lengths, rows, bank, phases, (int)window, N, L_out, y, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "resampling kernel launch failed");
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// edit statistics
+// =================================================================================================================
+static std::string edit_limits(int64_t max_expected, int64_t max_actual) {
+    if (max_expected < 0 || max_expected > AMX_EDIT_MAX_LENGTH || max_actual < 0 || max_actual > AMX_EDIT_MAX_LENGTH)
+        return "expanded lengths must be 0 to " + std::to_string(AMX_EDIT_MAX_LENGTH);
+    return "";
+}
+
+extern "C" int amx_edit_workspace(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (rows < 0 || rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "rows must be 0 to 2^31 - 1");
+    const std::string err = edit_limits(max_expected, max_actual);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    *bytes = edit_workspace_bytes(rows, max_expected, max_actual);
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_statistics(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O,
+                                   int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                   const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                   const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                   const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual, void* workspace,
+                                   size_t workspace_bytes, int32_t* statistics, int32_t* best, uint64_t* totals, void* stream) {
+    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
+    if (K < 1 || K > AMX_EDIT_MAX_CANDIDATES)
+        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
+    const std::string err = edit_limits(max_expected, max_actual);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
+    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
+    const int64_t rows = (int64_t)O * N * K;
+    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N * K must stay below 2^31");
+    if (rows == 0) return AMX_OK;
+    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
+        !workspace || !statistics || !best || !totals)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (workspace_bytes < edit_workspace_bytes(rows, max_expected, max_actual))
+        return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_workspace");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    amx::EditArgs a{};
+    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = stride_k, a.T = T;
+    a.O = O, a.N = N, a.K = K, a.G = G, a.H = H;
+    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
+    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
+    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
+    a.workspace = (int32_t*)workspace, a.statistics = statistics, a.best = best, a.totals = totals;
+    launch_edit_statistics(a, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit statistics launch failed");
     return AMX_OK;
 }
 

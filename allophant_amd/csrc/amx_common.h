@@ -502,6 +502,24 @@ std::string resample_bank(int64_t orig, int64_t new_rate, int32_t lpw, double ro
 void launch_resample(const float* x, int64_t stride, int64_t L_in, const int64_t* lengths, const amx_resample_row* rows,
                      const float* bank, const int32_t* phases, int window, int N, int64_t L_out, float* y, hipStream_t s);
 
+// edit statistics (amx_edit.hip): contract in include/allophant_amx_edit.h.  One wave per scored (output, utterance,
+// candidate) row, then one thread per (output, utterance) for the candidate choice and the totals.  The launcher fills the
+// workspace layout (per row, in int32: expected, actual, two boundary rows of int2 cells, each padded to 16).
+struct EditArgs {
+    const int64_t* tokens;
+    int64_t stride_o, stride_n, stride_k, T;
+    int O, N, K, G, H;
+    const int32_t *counts, *hyp_counts, *label_offsets, *label_ids, *groups;
+    const int32_t *map_offsets, *map_values, *label_maps, *hyp_maps;
+    int cap_a, cap_b;  // max_expected, max_actual
+    int64_t cap_a_pad, cap_b_pad, bnd_pad, span;
+    int32_t* workspace;
+    int32_t *statistics, *best;
+    uint64_t* totals;
+};
+size_t edit_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual);
+void launch_edit_statistics(EditArgs a, hipStream_t s);
+
 // weight packing helpers (device side; run once at amx_create / amx_set_inventory)
 void launch_pack_matrix(int prec, const float* src, int rows, int cols, int64_t src_row_stride, int64_t src_col_stride,
                         float scale, void* dst, int64_t dst_plane, int64_t ldd, int cols_pad, hipStream_t s);

@@ -1,0 +1,525 @@
+"""Phoneme and attribute error rates of decoded batches: upstream's ``run.py evaluate`` (run.py:392-499) on the device.
+
+``Evaluator.add`` scores the hypotheses that ``Estimator.greedy_decode_device`` / ``beam_decode_device`` left in HBM against
+the batch's labels with the ``amx_edit_statistics`` kernel (include/allophant_amx_edit.h): upstream's
+``levensthein_statistics`` per (output, utterance, candidate), the candidate of the lowest fp32 error rate, and per-language
+totals, all without a host synchronisation.  ``Evaluator.results`` fetches the totals once and returns upstream's
+``MultilingualEvaluationResults`` (evaluation.py:33-73), JSON keys included.
+
+The kernel compares ids.  Every output gets an id space built from the strings upstream compares, and two CSR maps into it:
+the label map (a label phoneme -> its attribute contour, after the ``--fix-unicode`` replacements, or the phoneme itself,
+split under ``--split-complex``) and the hypothesis map (a token -> ``inventory[token - 1]``, remapped per language and split,
+or the category ``feature_values(name, token - 1)``; the blank expands to nothing).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import unicodedata
+from dataclasses import dataclass, field
+from typing import Dict, Hashable, IO, List, NamedTuple, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import lib as _lib
+from .phonetic import IPA_LAYERS, AttributeTable, InventoryView, split_complex_segment
+
+__all__ = ["EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "EvaluationMaps", "Evaluator", "LabelBatch", "levensthein_statistics",
+           "levensthein_statistics_batch", "unicode_replacements"]
+
+TOTAL = "total"
+STATISTICS_FIELDS = ("insertions", "deletions", "substitutions", "correct")  # the kernel's order
+
+
+def _f32_ratio(numerator: np.float32, denominator: np.float32) -> float:
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.float32(numerator) / np.float32(denominator))
+
+
+@dataclass(frozen=True)
+class EditStatistics:
+    """Upstream's ``allophant.phonemes.EditStatistics`` (edit_distance.rs:283-360): counts of the first best edit path; rates
+    in fp32 with upstream's order of operations."""
+    insertions: int = 0
+    deletions: int = 0
+    substitutions: int = 0
+    correct: int = 0
+
+    @classmethod
+    def zeros(cls) -> "EditStatistics":
+        return cls(0, 0, 0, 0)
+
+    def word_error_rate(self) -> float:
+        """``(f32(S + D) + f32(I)) / (f32(S + D) + f32(C))``: NaN for all zeros, inf for insertions against nothing."""
+        substituted_or_deleted = np.float32(self.substitutions + self.deletions)
+        return _f32_ratio(substituted_or_deleted + np.float32(self.insertions), substituted_or_deleted + np.float32(self.correct))
+
+    def _expected_count(self) -> np.float32:
+        return np.float32(self.substitutions + self.deletions + self.correct)
+
+    def substitution_rate(self) -> float:
+        return _f32_ratio(np.float32(self.substitutions), self._expected_count())
+
+    def insertion_rate(self) -> float:
+        return _f32_ratio(np.float32(self.insertions), self._expected_count())
+
+    def deletion_rate(self) -> float:
+        return _f32_ratio(np.float32(self.deletions), self._expected_count())
+
+    def __add__(self, other: "EditStatistics") -> "EditStatistics":
+        if not isinstance(other, EditStatistics):
+            return NotImplemented
+        return EditStatistics(*(a + b for a, b in zip(self.astuple(), other.astuple())))
+
+    def astuple(self) -> Tuple[int, int, int, int]:
+        return (self.insertions, self.deletions, self.substitutions, self.correct)
+
+    def to_dict(self) -> Dict[str, int]:
+        return dict(zip(STATISTICS_FIELDS, self.astuple()))
+
+    @classmethod
+    def from_dict(cls, value: Dict[str, int]) -> "EditStatistics":
+        if set(value) != set(STATISTICS_FIELDS):  # EditStatisticsField._deserialize
+            raise ValueError("EditStatistics field mismatch, either missing or superfluous fields present")
+        return cls(*(int(value[k]) for k in STATISTICS_FIELDS))
+
+    def __str__(self) -> str:
+        return (f"EditStatistics(insertions={self.insertions}, deletions={self.deletions}, "
+                f"substitutions={self.substitutions}, correct={self.correct})")
+
+
+@dataclass
+class EvaluationResults:
+    """Upstream's ``EvaluationResults``: per output name its error rate and statistics."""
+    properties: List[str]
+    error_rates: Dict[str, float]
+    error_statistics: Dict[str, EditStatistics]
+
+    @classmethod
+    def from_statistics(cls, properties: Sequence[str], statistics: Dict[str, EditStatistics]) -> "EvaluationResults":
+        return cls(list(properties), {name: s.word_error_rate() for name, s in statistics.items()}, dict(statistics))
+
+    def to_dict(self) -> Dict:
+        return {"properties": list(self.properties), "error_rates": dict(self.error_rates),
+                "error_statistics": {name: s.to_dict() for name, s in self.error_statistics.items()}}
+
+    @classmethod
+    def from_dict(cls, value: Dict) -> "EvaluationResults":
+        return cls(list(value["properties"]), {k: float(v) for k, v in value["error_rates"].items()},
+                   {k: EditStatistics.from_dict(v) for k, v in value["error_statistics"].items()})
+
+    def __format__(self, format_spec: str) -> str:
+        return "\n".join(f"{name}: | {self.error_statistics[name]} | {self.error_rates[name] * 100:{format_spec + 'f'}}"
+                         for name in self.properties)
+
+    def __str__(self) -> str:
+        return f"{self:.4}"
+
+
+def _package_version() -> str:
+    from . import __version__
+
+    return __version__
+
+
+@dataclass
+class MultilingualEvaluationResults:
+    """Upstream's ``MultilingualEvaluationResults``: per language (and ``"total"``) an ``EvaluationResults``."""
+    evaluation_arguments: str
+    results: Dict[str, EvaluationResults]
+    package_version: str = field(default_factory=_package_version)
+
+    @classmethod
+    def from_statistics(cls, evaluation_arguments: str, properties: Sequence[str],
+                        statistics: Dict[str, Dict[str, EditStatistics]]) -> "MultilingualEvaluationResults":
+        """``evaluate`` (run.py:475-493): every language's results, then ``"total"``, the integer sum over the languages."""
+        results: Dict[str, EvaluationResults] = {}
+        totals: Dict[str, EditStatistics] = {}
+        for language, language_statistics in statistics.items():
+            for name, s in language_statistics.items():
+                totals[name] = totals.get(name, EditStatistics.zeros()) + s
+            results[language] = EvaluationResults.from_statistics(properties, language_statistics)
+        results[TOTAL] = EvaluationResults.from_statistics(properties, totals)
+        return cls(evaluation_arguments, results)
+
+    def with_totals(self) -> "MultilingualEvaluationResults":
+        """These results with ``"total"`` rebuilt from the languages."""
+        languages = {k: v for k, v in self.results.items() if k != TOTAL}
+        properties = next(iter(self.results.values())).properties if self.results else []
+        rebuilt = MultilingualEvaluationResults.from_statistics(
+            self.evaluation_arguments, properties, {k: v.error_statistics for k, v in languages.items()})
+        rebuilt.package_version = self.package_version
+        return rebuilt
+
+    def to_dict(self) -> Dict:
+        return {"evaluation_arguments": self.evaluation_arguments,
+                "results": {k: v.to_dict() for k, v in self.results.items()}, "package_version": self.package_version}
+
+    @classmethod
+    def from_dict(cls, value: Dict) -> "MultilingualEvaluationResults":
+        return cls(value["evaluation_arguments"], {k: EvaluationResults.from_dict(v) for k, v in value["results"].items()},
+                   value.get("package_version", _package_version()))
+
+    def dumps(self) -> str:
+        return json.dumps(self.to_dict())
+
+    def dump(self, file: IO[str]) -> None:
+        file.write(self.dumps())
+
+    @classmethod
+    def loads(cls, text: str) -> "MultilingualEvaluationResults":
+        return cls.from_dict(json.loads(text))
+
+    @classmethod
+    def load(cls, file: IO[str]) -> "MultilingualEvaluationResults":
+        return cls.loads(file.read())
+
+    def __format__(self, format_spec: str) -> str:
+        lines = [f"Command: {self.evaluation_arguments}\nVersion: {self.package_version}"]
+        lines += [f"{language}:\n{results:{format_spec}}" for language, results in self.results.items()]
+        return "\n".join(lines)
+
+    def __str__(self) -> str:
+        return f"{self:.4}"
+
+
+def unicode_replacements(table: AttributeTable, symbols: Sequence[str]) -> Dict[str, str]:
+    """``--fix-unicode``: ``missing_inventory_mappings`` (phonetic_features.py:488-510) without segmentation -- a label
+    symbol missing from the table maps to its NFC form when the table has that."""
+    known = set(table.full_phonemes)
+    mapping = {}
+    for symbol in symbols:
+        if symbol in known:
+            continue
+        combined = unicodedata.normalize("NFC", symbol)
+        if combined not in known:
+            raise ValueError(f"No suitable mapping found for segment {symbol!r}")
+        mapping[symbol] = combined
+    return mapping
+
+
+class _MapBuilder:
+    """Concatenated CSR maps (``map_offsets`` / ``map_values``) and their descriptors (first, entries)."""
+
+    def __init__(self):
+        self.offsets: List[int] = []
+        self.values: List[int] = []
+
+    def add(self, entries: Sequence[Sequence[int]]) -> Tuple[int, int]:
+        first = len(self.offsets)
+        for entry in entries:
+            self.offsets.append(len(self.values))
+            self.values.extend(entry)
+        self.offsets.append(len(self.values))
+        return first, len(entries)
+
+
+def _ids(space: Dict[Hashable, int], symbols: Sequence[Hashable]) -> List[int]:
+    return [space.setdefault(s, len(space)) for s in symbols]
+
+
+def _library():
+    handle = _lib.load()
+    if not hasattr(handle, "amx_edit_statistics"):
+        raise RuntimeError("liballophant_amx.so lacks amx_edit_statistics: rebuild the library")
+    return handle
+
+
+def _device(device) -> torch.device:
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("edit statistics run on the MI355X: there is no CPU path")
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _ptr(t: Optional[Tensor], offset: int = 0):
+    """Device address of element ``offset`` of ``t`` (an empty tail still gets a non-null address)."""
+    return C.c_void_p(t.data_ptr() + offset * t.element_size()) if t is not None else None
+
+
+def _run(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int, G: int,
+         maps: Tensor, n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int, max_actual: int,
+         workspace: Optional[Tensor], totals: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """One ``amx_edit_statistics`` call.  ``labels`` is the uploaded int32 block [offsets N + 1 | groups N | label ids],
+    ``maps`` the uploaded int32 block [map offsets | map values]; returns (statistics, best, workspace)."""
+    handle = _library()
+    O, N_, K, T = tokens.shape
+    rows = O * N_ * K
+    size = C.c_size_t()
+    _lib.check(handle, None, handle.amx_edit_workspace(rows, max_expected, max_actual, C.byref(size)))
+    if workspace is None or workspace.numel() < size.value:
+        workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=device)
+    statistics = torch.empty(O, N_, K, 4, dtype=torch.int32, device=device)
+    best = torch.empty(O, N_, dtype=torch.int32, device=device)
+    if tokens.stride(3) != 1:
+        tokens = tokens.contiguous()
+    stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        code = handle.amx_edit_statistics(
+            device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), tokens.stride(2), O, N_, K, T, _ptr(counts),
+            _ptr(hyp_counts), _ptr(labels), _ptr(labels, 2 * N + 1), _ptr(labels, N + 1), G, _ptr(maps), _ptr(maps, n_offsets),
+            _ptr(label_maps), _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel(), _ptr(statistics),
+            _ptr(best), _ptr(totals), C.c_void_p(stream))
+    _lib.check(handle, None, code)
+    return statistics, best, workspace
+
+
+def _upload(blocks: Sequence[np.ndarray], device: torch.device) -> Tuple[Tensor, List[int]]:
+    """Concatenates int32 blocks into one pinned buffer and copies it with one non-blocking copy; returns the device tensor
+    and each block's start."""
+    starts, total = [], 0
+    for b in blocks:
+        starts.append(total)
+        total += len(b)
+    host = torch.empty(max(1, total), dtype=torch.int32, pin_memory=True)
+    view = host.numpy()
+    for start, b in zip(starts, blocks):
+        view[start:start + len(b)] = b
+    return host.to(device, non_blocking=True), starts
+
+
+class LabelBatch(NamedTuple):
+    """A batch's labels on the device: ``data`` int32 [offsets N + 1 | language indices N | label ids], and the longest
+    label of any output once expanded (host-computed: it sizes the workspace)."""
+    data: Tensor
+    N: int
+    max_expected: int
+
+
+class EvaluationMaps:
+    """The host half of ``Evaluator``: per output an id space (``spaces[o]``: string -> id) built from the strings upstream
+    compares, the label map and the hypothesis maps into it, as concatenated CSR arrays (``offsets``, ``values``) with
+    descriptors ``label_maps`` [O, 2] and ``hyp_maps`` [H, O, 2] (first, entries).  ``label_ids`` numbers the label symbols:
+    every phoneme of the table and every replaced form.  Arguments as ``Evaluator``."""
+
+    def __init__(self, table: AttributeTable, names: Sequence[str], inventory: Union[InventoryView, Sequence[str]],
+                 languages: Sequence[str], split_complex: bool = False,
+                 source_maps: Optional[Dict[str, Dict[str, str]]] = None, replacements: Optional[Dict[str, str]] = None):
+        self.names = list(names)
+        self.languages = list(languages)
+        if not self.names or not self.languages:
+            raise ValueError("evaluation needs at least one output and one language")
+        inventory = list(inventory.inventory if isinstance(inventory, InventoryView) else inventory)
+        replacements = dict(replacements or {})
+        if source_maps is not None:
+            missing = [lang for lang in self.languages if lang not in source_maps]
+            if missing:
+                raise ValueError(f"no source map for the languages {missing}")
+        known = set(table.full_phonemes)
+        self.label_ids: Dict[str, int] = {}
+        _ids(self.label_ids, table.full_phonemes)
+        _ids(self.label_ids, list(replacements))
+        label_symbols = list(self.label_ids)
+
+        def split(symbols: Sequence[str]) -> List[str]:
+            return [p for s in symbols for p in split_complex_segment(s)] if split_complex else list(symbols)
+
+        builder = _MapBuilder()
+        self.H = len(self.languages) if source_maps is not None else 1
+        self.label_maps = np.zeros((len(self.names), 2), dtype=np.int32)
+        self.hyp_maps = np.zeros((self.H, len(self.names), 2), dtype=np.int32)
+        self.label_lengths = np.zeros((len(self.names), len(label_symbols)), dtype=np.int64)
+        self.spaces: List[Dict[str, int]] = []
+        fanout = 0
+        for o, name in enumerate(self.names):
+            space: Dict[str, int] = {}
+            self.spaces.append(space)
+            if name in IPA_LAYERS:
+                # run.py:399-411: the label itself (no replacement), split under --split-complex
+                entries = [_ids(space, split([p])) for p in label_symbols]
+            else:
+                if name not in table.full_feature_names:
+                    raise ValueError(f"Missing feature in attributes: {name!r}")
+                entries = []
+                for p in label_symbols:
+                    target = replacements.get(p, p)
+                    if target not in known:
+                        raise ValueError(f"replacement {p!r} -> {target!r} names no phoneme of the attribute table")
+                    entries.append(_ids(space, table.feature_contour(target, name)))
+            self.label_lengths[o] = [len(e) for e in entries]
+            self.label_maps[o] = builder.add(entries)
+            for h in range(self.H):
+                if name not in IPA_LAYERS:
+                    if h == 0:  # attribute maps do not depend on the language: feature_values(name, token - 1)
+                        entries = [[]] + [_ids(space, [c]) for c in table.feature_categories(name)]
+                        fanout = max(fanout, 1)
+                        self.hyp_maps[0, o] = builder.add(entries)
+                    else:
+                        self.hyp_maps[h, o] = self.hyp_maps[0, o]
+                    continue
+                source = None if source_maps is None else source_maps[self.languages[h]]
+                if source is not None:
+                    missing = [p for p in inventory if p not in source]
+                    if missing:
+                        raise ValueError(f"source map of {self.languages[h]!r} lacks {missing}")
+                # inventory[token - 1], remapped, then split; the blank (token 0) expands to nothing
+                entries = [[]] + [_ids(space, split([source[p] if source is not None else p])) for p in inventory]
+                fanout = max(fanout, max(len(e) for e in entries))
+                self.hyp_maps[h, o] = builder.add(entries)
+        self.hyp_fanout = max(1, fanout)
+        self.offsets = np.asarray(builder.offsets, dtype=np.int32)
+        self.values = np.asarray(builder.values, dtype=np.int32)
+
+    def _expand(self, descriptor, ids: Sequence[int], o: int) -> List[str]:
+        first, entries = (int(v) for v in descriptor)
+        names = {i: s for s, i in self.spaces[o].items()}
+        out = []
+        for e in ids:
+            if not 0 <= e < entries:
+                raise IndexError(f"id {e} outside a map of {entries} entries")
+            out += [names[int(v)] for v in self.values[self.offsets[first + e]:self.offsets[first + e + 1]]]
+        return out
+
+    def expand_label(self, o: int, label: Sequence[str]) -> List[str]:
+        """What the kernel compares as expected, as strings (host expansion through the label map of output ``o``)."""
+        return self._expand(self.label_maps[o], [self.label_ids[s] for s in label], o)
+
+    def expand_tokens(self, o: int, language: int, tokens: Sequence[int]) -> List[str]:
+        """What the kernel compares as actual, as strings (host expansion of decoded token ids)."""
+        return self._expand(self.hyp_maps[language if self.H > 1 else 0, o], [int(t) for t in tokens], o)
+
+
+class Evaluator:
+    """Accumulates upstream's ``evaluate`` statistics over decoded batches on the device.
+
+    ``table``: the attribute table (its full feature columns give the label contours); ``names``: the outputs to score (a
+    subset of the decoded ones, e.g. ``Predictions.outputs`` keys); ``inventory``: the phoneme inventory (or ``InventoryView``)
+    the predictions were made under -- the ``phone`` / ``phoneme`` tokens index it; ``languages``: the totals slots, in
+    order.  Options as upstream's ``evaluate``: ``split_complex`` (``--split-complex``), ``source_maps`` (language -> phoneme
+    -> phoneme: remapping, which ``--no-remap`` turns off) and ``replacements`` (label phoneme -> table phoneme, applied before
+    the attribute lookup: ``--fix-unicode``, see ``unicode_replacements``)."""
+
+    def __init__(self, table: AttributeTable, names: Sequence[str], inventory: Union[InventoryView, Sequence[str]],
+                 languages: Sequence[str], split_complex: bool = False,
+                 source_maps: Optional[Dict[str, Dict[str, str]]] = None, replacements: Optional[Dict[str, str]] = None,
+                 device=None):
+        self.device = _device(device)
+        self.maps = EvaluationMaps(table, names, inventory, languages, split_complex, source_maps, replacements)
+        self.names, self.languages = self.maps.names, self.maps.languages
+        self._n_offsets = len(self.maps.offsets)
+        self._maps = torch.from_numpy(np.concatenate([self.maps.offsets, self.maps.values])).to(self.device)
+        self._label_maps = torch.from_numpy(self.maps.label_maps.reshape(-1)).to(self.device)
+        self._hyp_maps = torch.from_numpy(self.maps.hyp_maps.reshape(-1)).to(self.device)
+        self.totals = torch.zeros(len(self.languages), len(self.names), 4, dtype=torch.int64, device=self.device)
+        self._workspace: Optional[Tensor] = None
+        self._rows: Optional[Tuple[Tensor, Tensor]] = None
+
+    def reset(self) -> None:
+        self.totals.zero_()
+
+    def encode_labels(self, labels: Sequence[Sequence[str]], languages: Sequence[Union[str, int]]) -> "LabelBatch":
+        """Encodes a batch's labels (per utterance its phoneme strings) and languages (codes of ``languages`` or their
+        indices) on the host, one dictionary lookup per symbol, and uploads them with one non-blocking copy from pinned
+        memory.  ``add`` does this itself; call it ahead to capture ``add`` in a graph with the labels as a static input."""
+        if len(labels) != len(languages):
+            raise ValueError(f"{len(labels)} labels for {len(languages)} languages")
+        N = len(labels)
+        offsets = np.zeros(N + 1, dtype=np.int32)
+        groups = np.empty(N, dtype=np.int32)
+        ids: List[int] = []
+        for n, (label, language) in enumerate(zip(labels, languages)):
+            try:
+                ids.extend(self.maps.label_ids[s] for s in label)
+            except KeyError as e:
+                raise ValueError(f"label symbol {e.args[0]!r} of utterance {n} is not in the attribute table") from None
+            offsets[n + 1] = len(ids)
+            groups[n] = language if isinstance(language, (int, np.integer)) else self.languages.index(language)
+        ids_np = np.asarray(ids, dtype=np.int32)
+        # the longest expanded label of any output: host data, so no device round trip
+        cumulative = np.zeros((len(self.names), len(ids_np) + 1), dtype=np.int64)
+        np.cumsum(self.maps.label_lengths[:, ids_np], axis=1, out=cumulative[:, 1:])
+        max_expected = int((cumulative[:, offsets[1:]] - cumulative[:, offsets[:-1]]).max(initial=0))
+        if max_expected > _lib.EDIT_MAX_LENGTH:
+            raise ValueError(f"an expanded label has {max_expected} symbols; the limit is {_lib.EDIT_MAX_LENGTH}")
+        data, _ = _upload([offsets, groups, ids_np], self.device)
+        return LabelBatch(data, N, max_expected)
+
+    def add(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
+            languages: Optional[Sequence[Union[str, int]]] = None) -> None:
+        """Scores ``decoded`` (``Decoded`` or ``BeamDecoded``, device-resident) against ``labels`` (per utterance its phoneme
+        strings, with ``languages``; or a ``LabelBatch`` from ``encode_labels``) and adds each (output, utterance)'s best
+        candidate to the totals of its language.  Stream-ordered: nothing waits for the device."""
+        rows = [decoded.names.index(name) for name in self.names]
+        tokens, counts = decoded.tokens, decoded.counts
+        hyp_counts = getattr(decoded, "hyp_counts", None)
+        if tokens.device != self.device:
+            raise ValueError(f"decoded results live on {tokens.device}, the evaluator on {self.device}")
+        if tokens.dim() == 3:  # greedy: one candidate
+            tokens, counts = tokens.unsqueeze(2), counts.unsqueeze(2)
+        if rows != list(range(len(decoded.names))):
+            index = torch.tensor(rows, dtype=torch.long, device=self.device)
+            tokens, counts = tokens.index_select(0, index), counts.index_select(0, index)
+            hyp_counts = None if hyp_counts is None else hyp_counts.index_select(0, index)
+        counts = counts.to(torch.int32).contiguous()
+        hyp_counts = None if hyp_counts is None else hyp_counts.to(torch.int32).contiguous()
+        O, N, K, T = tokens.shape
+        if not isinstance(labels, LabelBatch):
+            if languages is None:
+                raise ValueError("labels given as strings need their languages")
+            labels = self.encode_labels(labels, languages)
+        if N != labels.N:
+            raise ValueError(f"{N} decoded utterances for {labels.N} labels")
+        max_actual = min(T * self.maps.hyp_fanout, _lib.EDIT_MAX_LENGTH)
+        statistics, best, self._workspace = _run(
+            self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
+            self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._workspace, self.totals)
+        self._rows = (statistics, best)
+
+    def rows(self) -> Tuple[Tensor, Tensor]:
+        """Of the last ``add``: ``statistics`` int32 [O, N, K, 4] (insertions, deletions, substitutions, correct; -1 for a
+        candidate past ``hyp_counts``, -2 for a row with an out-of-range token) and ``best`` int32 [O, N] (the chosen
+        candidate, -1 for none, -2 for a flagged row), device tensors."""
+        if self._rows is None:
+            raise ValueError("nothing added yet")
+        return self._rows
+
+    def statistics(self) -> Dict[str, Dict[str, EditStatistics]]:
+        """language -> output -> accumulated ``EditStatistics`` (one host synchronisation)."""
+        totals = self.totals.cpu().tolist()
+        return {language: {name: EditStatistics(*totals[g][o]) for o, name in enumerate(self.names)}
+                for g, language in enumerate(self.languages)}
+
+    def results(self, evaluation_arguments: str = "") -> MultilingualEvaluationResults:
+        """Upstream's ``evaluate`` output: every language, then ``"total"`` (one host synchronisation)."""
+        return MultilingualEvaluationResults.from_statistics(evaluation_arguments, self.names, self.statistics())
+
+
+def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                 device=None) -> List[EditStatistics]:
+    """``levensthein_statistics(expected[i], actual[i])`` for every pair, on the device (symbols compare by equality)."""
+    if len(expected) != len(actual):
+        raise ValueError("expected and actual differ in length")
+    device = _device(device)
+    N = len(expected)
+    if N == 0:
+        return []
+    space: Dict[Hashable, int] = {}
+    label_ids = [_ids(space, e) for e in expected]
+    hyp_ids = [_ids(space, a) for a in actual]
+    longest = max(max(map(len, label_ids)), max(map(len, hyp_ids)))
+    if longest > _lib.EDIT_MAX_LENGTH:
+        raise ValueError(f"a sequence has {longest} symbols; the limit is {_lib.EDIT_MAX_LENGTH}")
+    V = max(1, len(space))
+    offsets = np.zeros(N + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(e) for e in label_ids])
+    flat = np.asarray([i for e in label_ids for i in e], dtype=np.int32)
+    block = np.concatenate([offsets, np.zeros(N, dtype=np.int32), flat])
+    T = max(1, max(map(len, hyp_ids)))
+    tokens = np.zeros((1, N, 1, T), dtype=np.int64)
+    for n, a in enumerate(hyp_ids):
+        tokens[0, n, 0, :len(a)] = a
+    counts = np.asarray([len(a) for a in hyp_ids], dtype=np.int32).reshape(1, N, 1)
+    identity = np.concatenate([np.arange(V + 1, dtype=np.int32), np.arange(V, dtype=np.int32)])  # entry e -> [e]
+    descriptor = torch.tensor([0, V], dtype=torch.int32, device=device)
+    totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=device)
+    statistics, _, _ = _run(device, torch.from_numpy(tokens).to(device), torch.from_numpy(counts).to(device), None,
+                            torch.from_numpy(block).to(device), N, 1, torch.from_numpy(identity).to(device), V + 1, descriptor,
+                            descriptor, 1, max(map(len, label_ids)), T, None, totals)
+    return [EditStatistics(*row) for row in statistics.reshape(N, 4).cpu().tolist()]
+
+
+def levensthein_statistics(expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> EditStatistics:
+    """Upstream's ``phonemes.levensthein_statistics(string_a=expected, string_b=actual)`` on the device."""
+    return levensthein_statistics_batch([expected], [actual], device)[0]

@@ -46,6 +46,10 @@ BEAM_MAX_WIDTH = 64
 RESAMPLE_EXPORTS = ["amx_resample_bank", "amx_resample"]
 RESAMPLE_MAX_PHASES = 4096  # AMX_RESAMPLE_MAX_PHASES
 RESAMPLE_MAX_WINDOW = 16384  # AMX_RESAMPLE_MAX_WINDOW
+# the edit-statistics entry points (include/allophant_amx_edit.h; added to ABI 6, detected by name)
+EDIT_EXPORTS = ["amx_edit_workspace", "amx_edit_statistics"]
+EDIT_MAX_LENGTH = 65535  # AMX_EDIT_MAX_LENGTH
+EDIT_MAX_CANDIDATES = 64  # AMX_EDIT_MAX_CANDIDATES
 
 
 def dep_output_layer(i: int) -> int:
@@ -142,6 +146,12 @@ def load() -> C.CDLL:
         lib.amx_resample_bank.restype = i32
         lib.amx_resample.argtypes = [i32, vp, i64, i64, vp, vp, vp, vp, i64, i32, i64, vp, vp]
         lib.amx_resample.restype = i32
+    if hasattr(lib, "amx_edit_statistics"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_edit_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_edit_workspace.restype = i32
+        lib.amx_edit_statistics.argtypes = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
+                                            i32, i64, i64, vp, C.c_size_t, vp, vp, vp, vp]
+        lib.amx_edit_statistics.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]

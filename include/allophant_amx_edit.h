@@ -1,0 +1,66 @@
+/* Edit-distance evaluation entry points of liballophant_amx (companion of allophant_amx.h, same library, same ABI version). */
+#ifndef ALLOPHANT_AMX_EDIT_H
+#define ALLOPHANT_AMX_EDIT_H
+#include "allophant_amx.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Upstream's `run.py evaluate` on decoded hypotheses: `levensthein_statistics(expected, actual)` (uniform costs, the full
+ * matrix and its back-trace, edit_distance.rs:372-481) per (output, utterance, candidate), the candidate of the lowest fp32
+ * `word_error_rate` per (output, utterance) (the first strictly lower one wins, run.py:447-464), and its statistics added to
+ * per-group totals.  Symbols added to ABI 6 without a struct change (detect them with dlsym).  The contract is restated in
+ * DESIGN 9 and, as Python, in tests/edit_util.py.
+ *
+ * Statistics are int32 (insertions, deletions, substitutions, correct), in that order everywhere.
+ *
+ * Sequences are compared as ids.  Each output o has a LABEL map and, per hypothesis-map set h, a HYPOTHESIS map.  A map is a
+ * CSR over int32 ids: its descriptor (first, entries) names entries e in [0, entries), and entry e expands to
+ *     map_values[map_offsets[first + e] .. map_offsets[first + e + 1])
+ * Expected = the concatenated expansions of the utterance's label ids through output o's label map; actual = those of the
+ * candidate's tokens through the hypothesis map of set h = (H == 1 ? 0 : groups[n]).  (The Python binding builds both maps
+ * from strings: contours, complex-segment splitting, remapping, label replacements and the blank offset all live in them.)
+ *
+ * Limits (AMX_EINVAL otherwise): 1 <= K <= AMX_EDIT_MAX_CANDIDATES, 0 <= max_expected, max_actual <= AMX_EDIT_MAX_LENGTH,
+ * O, N, T >= 0, O * N * K < 2^31, G >= 1, H == 1 or H == G.
+ *
+ * The caller supplies the workspace (amx_edit_workspace gives its size): per scored row, max_expected + max_actual int32 for
+ * the expanded sequences and 4 (max_actual + 1) int32 for two boundary rows of the DP.  It always lives in device memory:
+ * the boundary rows of a 65535-long hypothesis do not fit in LDS, and one path serves every length. */
+#define AMX_EDIT_MAX_LENGTH 65535   /* expanded symbols per side */
+#define AMX_EDIT_MAX_CANDIDATES 64  /* K: the beam's width limit */
+
+/* Pure host function (no device, no HIP call): workspace bytes for `rows` = O * N * K scored rows. */
+int amx_edit_workspace(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes);
+
+/* Scores every candidate on `device`.  All pointers are DEVICE pointers:
+ *   tokens        int64 [O, N, K, T] with element strides (stride_o, stride_n, stride_k, 1): candidate k of row (o, n)
+ *                 holds counts[o, n, k] tokens (e.g. `Decoded.tokens` as [O, N, 1, T], `BeamDecoded.tokens`)
+ *   counts        int32 [O, N, K] contiguous
+ *   hyp_counts    int32 [O, N] candidates present per row (`BeamDecoded.hyp_counts`), or NULL for K everywhere; clamped to [0, K]
+ *   label_offsets int32 [N + 1], label_ids int32: utterance n's label is label_ids[label_offsets[n] .. label_offsets[n + 1])
+ *   groups        int32 [N]: the totals slot (the language) of each utterance, in [0, G)
+ *   label_maps    int32 [O, 2], hyp_maps int32 [H, O, 2]: map descriptors (first, entries)
+ *   workspace     workspace_bytes >= amx_edit_workspace(O * N * K, max_expected, max_actual)
+ * and writes
+ *   statistics    int32 [O, N, K, 4]: scored candidates their statistics; candidates at or past the row's hyp_counts -1 x 4;
+ *                 a row with a token or label id outside its map, a count outside [0, T], a bad group or an expansion longer
+ *                 than max_expected / max_actual -2 x 4 (nothing out of range is read)
+ *   best          int32 [O, N]: the chosen candidate; -1 if none has a finite rate below +inf (an empty label gives 0/0 or
+ *                 x/0: upstream skips such rows); -2 if any candidate of the row is flagged (-2 statistics)
+ *   totals        uint64 [G, O, 4]: best >= 0 adds its four counts to totals[groups[n], o] (integer atomics: the sums are
+ *                 the same in any order).  Accumulated, never cleared.
+ * Two launches (score, then select-and-add), stream-ordered on `stream`: no allocation and no host synchronisation (the
+ * call can be captured in a graph). */
+int amx_edit_statistics(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O, int N,
+                        int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets,
+                        const int32_t* label_ids, const int32_t* groups, int G, const int32_t* map_offsets,
+                        const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
+                        int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes, int32_t* statistics,
+                        int32_t* best, uint64_t* totals, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ALLOPHANT_AMX_EDIT_H */
