@@ -2388,6 +2388,54 @@ extern "C" int amx_edit_statistics(int device, const int64_t* tokens, int64_t st
     return AMX_OK;
 }
 
+extern "C" int amx_edit_operations_workspace(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (rows < 0 || rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "rows must be 0 to 2^31 - 1");
+    const std::string err = edit_limits(max_expected, max_actual);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (!edit_operations_workspace_bytes(rows, max_expected, max_actual, bytes))
+        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_operations(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int O, int N, int64_t T,
+                                   const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets,
+                                   const int32_t* label_ids, const int32_t* groups, int G, const int32_t* map_offsets,
+                                   const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
+                                   int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes,
+                                   int64_t max_ops, int32_t* operations, int32_t* operation_counts, void* stream) {
+    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
+    const std::string err = edit_limits(max_expected, max_actual);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (max_ops < std::max(max_expected, max_actual) || max_ops > INT32_MAX)
+        return fail(nullptr, AMX_EINVAL, "max_ops must be max(max_expected, max_actual) to 2^31 - 1");
+    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
+    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
+    const int64_t rows = (int64_t)O * N;
+    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N must stay below 2^31");
+    size_t needed = 0;
+    if (!edit_operations_workspace_bytes(rows, max_expected, max_actual, &needed))
+        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
+    if (rows == 0) return AMX_OK;
+    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
+        !workspace || !operations || !operation_counts)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (workspace_bytes < needed) return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_operations_workspace");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    amx::EditOpsArgs x{};
+    amx::EditArgs& a = x.e;
+    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = 0, a.T = T;
+    a.O = O, a.N = N, a.K = 1, a.G = G, a.H = H;
+    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
+    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
+    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
+    a.workspace = (int32_t*)workspace;
+    x.max_ops = max_ops, x.operations = operations, x.operation_counts = operation_counts;
+    launch_edit_operations(x, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit operations launch failed");
+    return AMX_OK;
+}
+
 // =================================================================================================================
 // allophone layer
 // =================================================================================================================

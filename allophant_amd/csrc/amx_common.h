@@ -519,6 +519,19 @@ struct EditArgs {
 };
 size_t edit_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual);
 void launch_edit_statistics(EditArgs a, hipStream_t s);
+int64_t edit_pad(int64_t v);  // rounded up to a multiple of 16
+
+// edit operations (amx_edit_ops.hip): one wave per (output, utterance) row, candidate 0 (e.K == 1; the statistics outputs
+// unused).  A row's workspace is the statistics row's, then the path codes: per strip of 64 expected symbols, code_stride
+// words of 16 bytes (one per wave step).
+struct EditOpsArgs {
+    EditArgs e;
+    int64_t max_ops, code_stride, codes_at;  // codes_at: int32 offset of the codes in a row's workspace
+    int32_t *operations, *operation_counts;
+};
+// false when the size is not representable in size_t
+bool edit_operations_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes);
+void launch_edit_operations(EditOpsArgs x, hipStream_t s);
 
 // weight packing helpers (device side; run once at amx_create / amx_set_inventory)
 void launch_pack_matrix(int prec, const float* src, int rows, int cols, int64_t src_row_stride, int64_t src_col_stride,

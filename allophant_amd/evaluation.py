@@ -10,6 +10,10 @@ The kernel compares ids.  Every output gets an id space built from the strings u
 the label map (a label phoneme -> its attribute contour, after the ``--fix-unicode`` replacements, or the phoneme itself,
 split under ``--split-complex``) and the hypothesis map (a token -> ``inventory[token - 1]``, remapped per language and split,
 or the category ``feature_values(name, token - 1)``; the blank expands to nothing).
+
+``Evaluator.operations`` / ``Evaluator.edits`` are upstream's ``run.py edits`` (run.py:502-528) on the same ids: the
+``amx_edit_operations`` kernel walks ``levensthein_operations``'s path for the first candidate of every (output, utterance), and
+``edits`` turns the records into ``UtteranceEdits`` (predictions.py:58-83) with one host synchronisation.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ import ctypes as C
 import json
 import unicodedata
 from dataclasses import dataclass, field
+from enum import IntEnum
 from typing import Dict, Hashable, IO, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -27,7 +32,8 @@ from . import lib as _lib
 from .phonetic import IPA_LAYERS, AttributeTable, InventoryView, split_complex_segment
 
 __all__ = ["EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "EvaluationMaps", "Evaluator", "LabelBatch", "levensthein_statistics",
-           "levensthein_statistics_batch", "unicode_replacements"]
+           "levensthein_statistics_batch", "unicode_replacements", "Action", "UtteranceEdits", "levensthein_operations",
+           "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions"]
 
 TOTAL = "total"
 STATISTICS_FIELDS = ("insertions", "deletions", "substitutions", "correct")  # the kernel's order
@@ -185,6 +191,68 @@ class MultilingualEvaluationResults:
         return f"{self:.4}"
 
 
+class Action(IntEnum):
+    """Upstream's ``allophant.phonemes.Action`` (phonemes.pyi): the recorded edit operations."""
+    INSERTION = 1
+    DELETION = 2
+    SUBSTITUTION = 3
+
+    @staticmethod
+    def from_int(integer: int) -> "Action":
+        return Action(integer)
+
+
+Operation = Tuple[Action, int, int]  # (action, i, j): the coordinates after the move
+Substitution = Tuple[Action, str, str]  # (action, expected symbol or "", actual symbol or "")
+
+
+@dataclass
+class UtteranceEdits:
+    """Upstream's ``UtteranceEdits`` (predictions.py:70-83): per output the expected symbols and the edit operations that turn
+    them into the first candidate.  ``to_dict`` / ``to_json`` give mashumaro's shape: fields in this order, ``Action`` as its
+    int, tuples as lists, ``json.dumps`` defaults (non-ASCII escaped)."""
+    language: str
+    utterance_id: str
+    expected: Dict[str, List[str]]
+    edit_operations: Dict[str, List[Substitution]]
+
+    def to_dict(self) -> Dict:
+        return {"language": self.language, "utterance_id": self.utterance_id,
+                "expected": {name: list(symbols) for name, symbols in self.expected.items()},
+                "edit_operations": {name: [[int(action), a, b] for action, a, b in operations]
+                                    for name, operations in self.edit_operations.items()}}
+
+    @classmethod
+    def from_dict(cls, value: Dict) -> "UtteranceEdits":
+        return cls(str(value["language"]), str(value["utterance_id"]),
+                   {name: [str(s) for s in symbols] for name, symbols in value["expected"].items()},
+                   {name: [(Action.from_int(action), str(a), str(b)) for action, a, b in operations]
+                    for name, operations in value["edit_operations"].items()})
+
+    def to_json(self) -> str:
+        return json.dumps(self.to_dict())
+
+    @classmethod
+    def from_json(cls, text: str) -> "UtteranceEdits":
+        return cls.from_dict(json.loads(text))
+
+
+def to_substitutions(expected: Sequence[str], actual: Sequence[str], operations: Sequence[Tuple[int, int, int]]
+                     ) -> List[Substitution]:
+    """Upstream's ``phonemes.to_substitutions`` (edit_distance.rs:105-119), on the host: each (action, i, j) as (action,
+    expected[i] or "", actual[j] or "")."""
+    result = []
+    for action, i, j in operations:
+        action = Action(action)
+        if action == Action.DELETION:
+            result.append((action, expected[i], ""))
+        elif action == Action.INSERTION:
+            result.append((action, "", actual[j]))
+        else:
+            result.append((action, expected[i], actual[j]))
+    return result
+
+
 def unicode_replacements(table: AttributeTable, symbols: Sequence[str]) -> Dict[str, str]:
     """``--fix-unicode``: ``missing_inventory_mappings`` (phonetic_features.py:488-510) without segmentation -- a label
     symbol missing from the table maps to its NFC form when the table has that."""
@@ -264,6 +332,33 @@ def _run(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optio
             _ptr(best), _ptr(totals), C.c_void_p(stream))
     _lib.check(handle, None, code)
     return statistics, best, workspace
+
+
+def _run_operations(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int,
+                    G: int, maps: Tensor, n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int,
+                    max_actual: int, workspace: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """One ``amx_edit_operations`` call on candidate 0: ``tokens`` [O, N, T], ``counts`` int32 [O, N]; arguments otherwise as
+    ``_run``.  Returns (operations int32 [O, N, max_ops, 5], operation counts int32 [O, N], workspace)."""
+    handle = _library()
+    O, N_, T = tokens.shape
+    size = C.c_size_t()
+    _lib.check(handle, None, handle.amx_edit_operations_workspace(O * N_, max_expected, max_actual, C.byref(size)))
+    if workspace is None or workspace.numel() < size.value:
+        workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=device)
+    max_ops = max(1, max_expected, max_actual)
+    operations = torch.empty(O, N_, max_ops, 5, dtype=torch.int32, device=device)
+    operation_counts = torch.empty(O, N_, dtype=torch.int32, device=device)
+    if tokens.stride(2) != 1:
+        tokens = tokens.contiguous()
+    stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        code = handle.amx_edit_operations(
+            device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), O, N_, T, _ptr(counts), _ptr(hyp_counts),
+            _ptr(labels), _ptr(labels, 2 * N + 1), _ptr(labels, N + 1), G, _ptr(maps), _ptr(maps, n_offsets), _ptr(label_maps),
+            _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel(), max_ops, _ptr(operations),
+            _ptr(operation_counts), C.c_void_p(stream))
+    _lib.check(handle, None, code)
+    return operations, operation_counts, workspace
 
 
 def _upload(blocks: Sequence[np.ndarray], device: torch.device) -> Tuple[Tensor, List[int]]:
@@ -404,6 +499,7 @@ class Evaluator:
         self._hyp_maps = torch.from_numpy(self.maps.hyp_maps.reshape(-1)).to(self.device)
         self.totals = torch.zeros(len(self.languages), len(self.names), 4, dtype=torch.int64, device=self.device)
         self._workspace: Optional[Tensor] = None
+        self._ops_workspace: Optional[Tensor] = None
         self._rows: Optional[Tuple[Tensor, Tensor]] = None
 
     def reset(self) -> None:
@@ -467,6 +563,75 @@ class Evaluator:
             self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._workspace, self.totals)
         self._rows = (statistics, best)
 
+    def operations(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
+                   languages: Optional[Sequence[Union[str, int]]] = None) -> Tuple[Tensor, Tensor]:
+        """Upstream's ``levensthein_operations`` of the first candidate (for a ``BeamDecoded`` the best hypothesis) against
+        the label, for every output of ``names`` and every utterance; arguments as ``add``.  Returns device tensors
+        ``operations`` int32 [O, N, max_ops, 5] and ``counts`` int32 [O, N]: row (o, n) holds ``counts[o, n]`` records
+        (action, i, j, expected id or -1, actual id or -1) in upstream's order, ids in ``maps.spaces[o]``; ``counts`` is -1
+        for a row with no candidate and -2 for a row with an out-of-range token.  Stream-ordered: nothing waits for the
+        device (capturable in a graph with a ``LabelBatch`` after one call outside the capture has sized the workspace)."""
+        rows = [decoded.names.index(name) for name in self.names]
+        tokens, counts = decoded.tokens, decoded.counts
+        hyp_counts = getattr(decoded, "hyp_counts", None)
+        if tokens.device != self.device:
+            raise ValueError(f"decoded results live on {tokens.device}, the evaluator on {self.device}")
+        if tokens.dim() == 4:  # beam: candidate 0, the highest-scoring hypothesis
+            tokens, counts = tokens[:, :, 0], counts[:, :, 0]
+        if rows != list(range(len(decoded.names))):
+            index = torch.tensor(rows, dtype=torch.long, device=self.device)
+            tokens, counts = tokens.index_select(0, index), counts.index_select(0, index)
+            hyp_counts = None if hyp_counts is None else hyp_counts.index_select(0, index)
+        counts = counts.to(torch.int32).contiguous()
+        hyp_counts = None if hyp_counts is None else hyp_counts.to(torch.int32).contiguous()
+        O, N, T = tokens.shape
+        if not isinstance(labels, LabelBatch):
+            if languages is None:
+                raise ValueError("labels given as strings need their languages")
+            labels = self.encode_labels(labels, languages)
+        if N != labels.N:
+            raise ValueError(f"{N} decoded utterances for {labels.N} labels")
+        max_actual = min(T * self.maps.hyp_fanout, _lib.EDIT_MAX_LENGTH)
+        operations, operation_counts, self._ops_workspace = _run_operations(
+            self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
+            self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._ops_workspace)
+        return operations, operation_counts
+
+    def edits(self, decoded, labels: Sequence[Sequence[str]], languages: Sequence[Union[str, int]],
+              utterance_ids: Sequence[str]) -> List[UtteranceEdits]:
+        """Upstream's ``_compute_edits`` (run.py:502-521) on a decoded batch: per utterance an ``UtteranceEdits`` with, per
+        output of ``names`` in that order, the expected symbols and the substitutions of the first candidate.  One host
+        synchronisation.  A row with an out-of-range token or without a candidate raises ``ValueError``."""
+        if not len(labels) == len(languages) == len(utterance_ids):
+            raise ValueError(f"{len(labels)} labels, {len(languages)} languages and {len(utterance_ids)} utterance ids")
+        operations, counts = self.operations(decoded, labels, languages)
+        host_operations = torch.empty(operations.shape, dtype=torch.int32, pin_memory=True)
+        host_counts = torch.empty(counts.shape, dtype=torch.int32, pin_memory=True)
+        host_operations.copy_(operations, non_blocking=True)
+        host_counts.copy_(counts, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        records, lengths = host_operations.numpy(), host_counts.numpy()
+        symbols = [["" for _ in range(len(space))] for space in self.maps.spaces]
+        for o, space in enumerate(self.maps.spaces):
+            for symbol, i in space.items():
+                symbols[o][i] = symbol
+        edits = []
+        for n, (label, language, utterance_id) in enumerate(zip(labels, languages, utterance_ids)):
+            expected, substitutions = {}, {}
+            for o, name in enumerate(self.names):
+                count = int(lengths[o, n])
+                if count < 0:
+                    reason = "has no candidate" if count == -1 else "holds a token outside its map"
+                    raise ValueError(f"output {name!r} of utterance {n} ({utterance_id!r}) {reason}")
+                expected[name] = self.maps.expand_label(o, label)
+                names = symbols[o]
+                substitutions[name] = [(Action(action), names[a] if a >= 0 else "", names[b] if b >= 0 else "")
+                                       for action, _, _, a, b in records[o, n, :count].tolist()]
+            if not isinstance(language, str):
+                language = self.languages[int(language)]
+            edits.append(UtteranceEdits(language, str(utterance_id), expected, substitutions))
+        return edits
+
     def rows(self) -> Tuple[Tensor, Tensor]:
         """Of the last ``add``: ``statistics`` int32 [O, N, K, 4] (insertions, deletions, substitutions, correct; -1 for a
         candidate past ``hyp_counts``, -2 for a row with an out-of-range token) and ``best`` int32 [O, N] (the chosen
@@ -486,15 +651,20 @@ class Evaluator:
         return MultilingualEvaluationResults.from_statistics(evaluation_arguments, self.names, self.statistics())
 
 
-def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
-                                 device=None) -> List[EditStatistics]:
-    """``levensthein_statistics(expected[i], actual[i])`` for every pair, on the device (symbols compare by equality)."""
-    if len(expected) != len(actual):
-        raise ValueError("expected and actual differ in length")
-    device = _device(device)
+class _Pairs(NamedTuple):
+    """Sequence pairs as one batch of the kernels: one id space, every id its own map entry."""
+    tokens: Tensor  # int64 [1, N, 1, T]
+    counts: Tensor  # int32 [1, N, 1]
+    labels: Tensor  # the LabelBatch block
+    maps: Tensor  # identity map: offsets V + 1 | values V
+    descriptor: Tensor  # (0, V)
+    V: int
+    max_expected: int
+    T: int
+
+
+def _pairs(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]], device: torch.device) -> _Pairs:
     N = len(expected)
-    if N == 0:
-        return []
     space: Dict[Hashable, int] = {}
     label_ids = [_ids(space, e) for e in expected]
     hyp_ids = [_ids(space, a) for a in actual]
@@ -513,13 +683,55 @@ def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual:
     counts = np.asarray([len(a) for a in hyp_ids], dtype=np.int32).reshape(1, N, 1)
     identity = np.concatenate([np.arange(V + 1, dtype=np.int32), np.arange(V, dtype=np.int32)])  # entry e -> [e]
     descriptor = torch.tensor([0, V], dtype=torch.int32, device=device)
+    return _Pairs(torch.from_numpy(tokens).to(device), torch.from_numpy(counts).to(device), torch.from_numpy(block).to(device),
+                  torch.from_numpy(identity).to(device), descriptor, V, max(map(len, label_ids)), T)
+
+
+def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                 device=None) -> List[EditStatistics]:
+    """``levensthein_statistics(expected[i], actual[i])`` for every pair, on the device (symbols compare by equality)."""
+    if len(expected) != len(actual):
+        raise ValueError("expected and actual differ in length")
+    device = _device(device)
+    N = len(expected)
+    if N == 0:
+        return []
+    p = _pairs(expected, actual, device)
     totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=device)
-    statistics, _, _ = _run(device, torch.from_numpy(tokens).to(device), torch.from_numpy(counts).to(device), None,
-                            torch.from_numpy(block).to(device), N, 1, torch.from_numpy(identity).to(device), V + 1, descriptor,
-                            descriptor, 1, max(map(len, label_ids)), T, None, totals)
+    statistics, _, _ = _run(device, p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
+                            p.max_expected, p.T, None, totals)
     return [EditStatistics(*row) for row in statistics.reshape(N, 4).cpu().tolist()]
 
 
 def levensthein_statistics(expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> EditStatistics:
     """Upstream's ``phonemes.levensthein_statistics(string_a=expected, string_b=actual)`` on the device."""
     return levensthein_statistics_batch([expected], [actual], device)[0]
+
+
+def levensthein_operations_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                 device=None) -> List[Tuple[List[Operation], float]]:
+    """``levensthein_operations(expected[i], actual[i])`` for every pair, on the device (symbols compare by equality)."""
+    if len(expected) != len(actual):
+        raise ValueError("expected and actual differ in length")
+    device = _device(device)
+    N = len(expected)
+    if N == 0:
+        return []
+    p = _pairs(expected, actual, device)
+    operations, counts, _ = _run_operations(device, p.tokens[:, :, 0], p.counts[:, :, 0], None, p.labels, N, 1, p.maps,
+                                            p.V + 1, p.descriptor, p.descriptor, 1, p.max_expected, p.T, None)
+    records, lengths = operations[0].cpu().numpy(), counts[0].cpu().tolist()
+    return [([(Action(action), i, j) for action, i, j in records[n, :lengths[n], :3].tolist()], float(lengths[n]))
+            for n in range(N)]
+
+
+def levensthein_operations(expected: Sequence[Hashable], actual: Sequence[Hashable], device=None
+                           ) -> Tuple[List[Operation], float]:
+    """Upstream's ``phonemes.levensthein_operations(string_a=expected, string_b=actual)`` on the device: the first best path's
+    operations (action, i, j) in order, and the cost."""
+    return levensthein_operations_batch([expected], [actual], device)[0]
+
+
+def levensthein_substitutions(expected: Sequence[str], actual: Sequence[str], device=None) -> List[Substitution]:
+    """Upstream's ``predictions.levensthein_substitutions``: ``to_substitutions`` of ``levensthein_operations``."""
+    return to_substitutions(expected, actual, levensthein_operations(expected, actual, device)[0])

@@ -47,7 +47,7 @@ RESAMPLE_EXPORTS = ["amx_resample_bank", "amx_resample"]
 RESAMPLE_MAX_PHASES = 4096  # AMX_RESAMPLE_MAX_PHASES
 RESAMPLE_MAX_WINDOW = 16384  # AMX_RESAMPLE_MAX_WINDOW
 # the edit-statistics entry points (include/allophant_amx_edit.h; added to ABI 6, detected by name)
-EDIT_EXPORTS = ["amx_edit_workspace", "amx_edit_statistics"]
+EDIT_EXPORTS = ["amx_edit_workspace", "amx_edit_statistics", "amx_edit_operations_workspace", "amx_edit_operations"]
 EDIT_MAX_LENGTH = 65535  # AMX_EDIT_MAX_LENGTH
 EDIT_MAX_CANDIDATES = 64  # AMX_EDIT_MAX_CANDIDATES
 
@@ -152,6 +152,12 @@ def load() -> C.CDLL:
         lib.amx_edit_statistics.argtypes = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
                                             i32, i64, i64, vp, C.c_size_t, vp, vp, vp, vp]
         lib.amx_edit_statistics.restype = i32
+    if hasattr(lib, "amx_edit_operations"):
+        lib.amx_edit_operations_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_edit_operations_workspace.restype = i32
+        lib.amx_edit_operations.argtypes = [i32, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64,
+                                            i64, vp, C.c_size_t, i64, vp, vp, vp]
+        lib.amx_edit_operations.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]

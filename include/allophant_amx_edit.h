@@ -60,6 +60,45 @@ int amx_edit_statistics(int device, const int64_t* tokens, int64_t stride_o, int
                         int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes, int32_t* statistics,
                         int32_t* best, uint64_t* totals, void* stream);
 
+/* Upstream's `run.py edits` on decoded hypotheses: `levensthein_operations(expected, actual)` (uniform costs, the walk of
+ * edit_distance.rs:101-279, the same path as the statistics) and `to_substitutions` per (output, utterance), for candidate 0
+ * only.  Added to ABI 6 like the statistics.  The contract is restated in DESIGN 9 and, as Python, in tests/edit_ops_util.py.
+ *
+ * An operation is the record int32 (action, i, j, expected id, actual id): the action (below), the coordinates after the move
+ * (i indexes expected for a deletion or substitution, j indexes actual for an insertion or substitution; the other one is
+ * where the walk stood) and the symbol ids expected[i] / actual[j] it names, -1 where to_substitutions writes "".  A row's
+ * records are in upstream's order (the back-trace reversed), one per unit of cost: their count is the edit distance, at most
+ * max(m, n).  Maps and limits as amx_edit_statistics with K = 1; also max(max_expected, max_actual) <= max_ops < 2^31.
+ *
+ * The workspace (amx_edit_operations_workspace gives its size) holds, per row, the statistics row's buffers and the path:
+ * 16 bytes per wave step of the DP, ceil(max_expected / 64) strips x (max_actual + 64, padded to 16) steps. */
+#define AMX_EDIT_INSERTION 1
+#define AMX_EDIT_DELETION 2
+#define AMX_EDIT_SUBSTITUTION 3
+
+/* Pure host function (no device, no HIP call): workspace bytes for `rows` = O * N rows; AMX_EINVAL when not representable. */
+int amx_edit_operations_workspace(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes);
+
+/* The operations of candidate 0 on `device`.  All pointers are DEVICE pointers:
+ *   tokens        int64 [O, N, T] with element strides (stride_o, stride_n, 1): row (o, n) holds counts[o, n] tokens
+ *                 (`Decoded.tokens`, or the k = 0 view of `BeamDecoded.tokens`)
+ *   counts        int32 [O, N] contiguous
+ *   hyp_counts    int32 [O, N] candidates present per row, or NULL: a row with 0 (or fewer) has no candidate
+ *   label_offsets, label_ids, groups, map_offsets, map_values, label_maps, hyp_maps, H: as amx_edit_statistics
+ *   workspace     workspace_bytes >= amx_edit_operations_workspace(O * N, max_expected, max_actual)
+ * and writes
+ *   operations        int32 [O, N, max_ops, 5]: records [0, operation_counts[o, n]) of each row; nothing past them
+ *   operation_counts  int32 [O, N]: the cost (the number of records); -1 for a row with no candidate; -2 for a row flagged
+ *                     as amx_edit_statistics flags it (an id outside its map, a count outside [0, T], a bad group, an
+ *                     expansion longer than max_expected / max_actual; nothing out of range is read)
+ * One launch, stream-ordered on `stream`: no allocation and no host synchronisation (the call can be captured in a graph). */
+int amx_edit_operations(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int O, int N, int64_t T,
+                        const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets, const int32_t* label_ids,
+                        const int32_t* groups, int G, const int32_t* map_offsets, const int32_t* map_values,
+                        const int32_t* label_maps, const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual,
+                        void* workspace, size_t workspace_bytes, int64_t max_ops, int32_t* operations,
+                        int32_t* operation_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
