@@ -985,12 +985,7 @@ void launch_attn_any(const AttnParams& p, hipStream_t stream) {
 }
 
 void launch_attention(int prec, const AttnParams& p, hipStream_t stream) {
-    switch (prec) {
-        case PREC_BF16: launch_attn_any<bf16, 1>(p, stream); break;
-        case PREC_F16: launch_attn_any<f16, 1>(p, stream); break;
-        case PREC_BF16X3: launch_attn_any<bf16, 2>(p, stream); break;
-        default: launch_attn_any<f16, 2>(p, stream); break;
-    }
+    AMX_DISPATCH(prec, (launch_attn_any<T16, NT>(p, stream)));
 }
 
 }  // namespace amx

@@ -27,6 +27,14 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 //         (x = hi + lo, hi = rn16(x), lo = rn16(x - hi)), fp32 accumulate: ~2^-21 (f16) / 2^-16 (bf16) relative.
 enum Precision { PREC_BF16 = 0, PREC_F16 = 1, PREC_BF16X3 = 2, PREC_F16X3 = 3 };
 inline int prec_planes(int p) { return p >= 2 ? 2 : 1; }
+// runs CALL once with T16 (the 16-bit type) and NT (planes per operand) of the precision mode `prec`
+#define AMX_DISPATCH(prec, CALL)                                   \
+    switch (prec) {                                                \
+        case PREC_BF16: { typedef bf16 T16; constexpr int NT = 1; CALL; } break;   \
+        case PREC_F16: { typedef f16 T16; constexpr int NT = 1; CALL; } break;     \
+        case PREC_BF16X3: { typedef bf16 T16; constexpr int NT = 2; CALL; } break; \
+        default: { typedef f16 T16; constexpr int NT = 2; CALL; } break;           \
+    }
 
 // Interleaved planes (the layout of every GEMM operand in the two-plane modes, except the positional-convolution image):
 // the hi and lo values of 32 consecutive K elements share one 128-byte line, [hi x 32 | lo x 32], so that the operand DMA of
@@ -321,10 +329,14 @@ struct GemmParams {
 };
 
 extern bool g_force_generic_gemm;
-// false: nothing was launched -- a LayerNorm-fold product (ln_partial / row_coef) on a plan without its epilogue; every
-// plan gemm_ln_fold_ok admits launches
+// What launch_gemm does with a product -- kernel, tile, K chunks, whether anything is launched -- is decided in one place,
+// gemm_route (amx_gemm.hip); launch_gemm launches that route and the queries below read it, so a plan made with the queries and the
+// launch that follows cannot disagree.
+// false: nothing was launched -- a product whose epilogue the kernel of its route does not have: a LayerNorm-fold product
+// (ln_partial / row_coef) off the ping-pong kernel or a producer on its 192-column tiles (every plan gemm_ln_fold_ok admits
+// launches), a fused LayerNorm (ln_gamma) on a shape gemm_fuses_ln refuses
 bool launch_gemm(int prec, const GemmParams& p, hipStream_t stream);
-// true when launch_gemm routes this product to the 256x256 ping-pong kernel (else: generic tile kernel)
+// true when launch_gemm routes this product (its ln_gamma aside) to the 256x256 ping-pong kernel (else: generic tile kernel)
 bool gemm_uses_pp(int prec, const GemmParams& p);
 // true when a product with ln_gamma / ln_beta set can run on the row-complete kernel with fused LayerNorm + GELU
 bool gemm_fuses_ln(int prec, const GemmParams& p);

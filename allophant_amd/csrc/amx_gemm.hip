@@ -25,7 +25,7 @@ namespace {
 #include "amx_gemm_ln.inc"    // gemm_ln_kernel
 
 // ---------------------------------------------------------------------------------------------------------------
-// host side: eligibility, the plan (tile height / K chunks / kernel) of a product, launches
+// host side: eligibility, the route of a product (gemm_route: kernel, tile, K chunks), launches
 // ---------------------------------------------------------------------------------------------------------------
 int device_cus() {
     static int per_device[MAX_DEVICES] = {};
@@ -41,6 +41,11 @@ int device_cus() {
     return cus;
 }
 
+// operand DMA addresses a tile by 32-bit byte offsets from its first row: the spans (elements) must fit
+bool spans_fit(int64_t a_span, int64_t w_span) {
+    return !(a_span < 0 || w_span < 0 || a_span * 2 >= (int64_t)0xFFFFFF00 || w_span * 2 >= (int64_t)0xFFFFFF00);
+}
+
 bool ln_eligible(int NT, const GemmParams& p) {
     if (g_force_generic_gemm) return false;
     if (!p.ln_gamma || !p.ln_beta || p.act != 1 || !p.out_p || p.out_f32 || p.residual || p.row_len || p.mode != 0) return false;
@@ -53,7 +58,7 @@ bool ln_eligible(int NT, const GemmParams& p) {
         if ((a_il && (p.lda % 32 || p.a_batch_stride % 32)) || (w_il && p.ldw % 32)) return false;
         const int64_t a_span = (a_il ? 2 : 1) * ((p.M > p.rows_per_batch ? p.a_batch_stride : 0) + 256 * p.lda + p.K) + (NT > 1 ? p.a_plane : 0);
         const int64_t w_span = (w_il ? 2 : 1) * (512 * p.ldw + p.K) + (NT > 1 ? p.w_plane : 0);
-        if (a_span < 0 || w_span < 0 || a_span * 2 >= (int64_t)0xFFFFFF00 || w_span * 2 >= (int64_t)0xFFFFFF00) return false;
+        if (!spans_fit(a_span, w_span)) return false;
     }
     if (p.bias && ((uintptr_t)p.bias & 15)) return false;
     if (((uintptr_t)p.ln_gamma & 15) || ((uintptr_t)p.ln_beta & 15)) return false;
@@ -68,7 +73,7 @@ bool ln_uses_il(int NT, const GemmParams& p) {
 }
 
 template <typename T, int NT>
-void launch_gemm_ln(const GemmParams& p, hipStream_t stream) {
+void launch_gemm_ln(const GemmParams& p, bool il, hipStream_t stream) {
     static OncePerDevice attr;
     if (attr.first())
         (void)hipFuncSetAttribute((const void*)gemm_ln_kernel<T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, ppw::LDS_BYTES);
@@ -78,7 +83,7 @@ void launch_gemm_ln(const GemmParams& p, hipStream_t stream) {
     dim3 grid(tiles < cus ? tiles : cus, 1, 1);
     {
         // whole-line operand DMA, one segment pair per K slice (two planes: interleaved operands only)
-        if (ln_uses_il(NT, p)) {
+        if (il) {
             static OncePerDevice attr_il;
             if (attr_il.first())
                 (void)hipFuncSetAttribute((const void*)gemm_ln_il_kernel<T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, ppi::LDS_BYTES);
@@ -106,7 +111,7 @@ bool pp_eligible(int NT, const GemmParams& p) {
         // (interleaved planes: every logical offset doubles and the lo value is 64 bytes behind)
         const int64_t a_span = NT * ((p.M > p.rows_per_batch ? p.a_batch_stride : 0) + 256 * p.lda + p.K) + 64;
         const int64_t w_span = NT * (256 * p.ldw + p.K) + 64;
-        if (a_span < 0 || w_span < 0 || a_span * 2 >= (int64_t)0xFFFFFF00 || w_span * 2 >= (int64_t)0xFFFFFF00) return false;
+        if (!spans_fit(a_span, w_span)) return false;
     }
     if (p.bias && ((uintptr_t)p.bias & 15)) return false;
     if (p.out_f32 && (p.ldo % 4 || ((uintptr_t)p.out_f32 & 15))) return false;
@@ -166,46 +171,35 @@ void launch_fixup(const GemmParams& p, int splits, hipStream_t stream) {
                        (int64_t)p.M * p.N);
 }
 
-// LayerNorm fold (GemmParams.row_coef / ln_partial; callers checked gemm_ln_fold_ok): its own kernel instances, one piece, no K chunks
+// the kernel-side view when the K chunks ride on grid.z (LDS-DMA tiles, register-staged tiles): operand pointers advance by the
+// chunk length, the fp32 output by one slab
+GemmParams split_view_z(const GemmParams& p, int splits) {
+    GemmParams q = split_view(p, splits);
+    q.za = q.zw = q.K;
+    q.zout = q.split_out;
+    q.zbias = q.zoutp = 0;
+    return q;
+}
+
+// One ping-pong launch.  FOLD: 0 plain, 1 / 2 the LayerNorm fold's consumer / producer epilogue (GemmParams.row_coef / ln_partial):
+// its own kernel instances, always in one piece.
 template <typename T, int NT, int MI, int NI, int FOLD>
-void launch_pp_fold(const GemmParams& p, hipStream_t stream) {
+void launch_pp_tiles(const GemmParams& p, int splits, hipStream_t stream) {
     static OncePerDevice attr;
     constexpr int lds = pp::lds_bytes(NT, MI, NI);
     if (attr.first())
         (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<T, NT, MI, NI, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    const int tiles = ((p.N + NI * 64 - 1) / (NI * 64)) * ((p.M + MI * 32 - 1) / (MI * 32));
-    const int cus = device_cus();
-    hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI, FOLD>), dim3(tiles < cus ? tiles : cus, 1, 1), dim3(512), lds, stream, p);
-}
-
-// false: nothing was launched -- a fold producer (p.ln_partial) planned on 192-column tiles, which have no producer epilogue
-// (gemm_ln_fold_ok refuses that plan; the caller reports the refusal instead of going on without the residual product)
-template <typename T, int NT, int MI, int NI = 4>
-bool launch_pp_tiles(const GemmParams& p, int splits, hipStream_t stream) {
-    if (p.ln_partial) {
-        if constexpr (NI != 4) return false;
-        launch_pp_fold<T, NT, MI, 4, 2>(p, stream);
-        return true;
-    }
-    if (p.row_coef) {
-        launch_pp_fold<T, NT, MI, NI, 1>(p, stream);
-        return true;
-    }
-    static OncePerDevice attr;
-    constexpr int lds = pp::lds_bytes(NT, MI, NI);
-    if (attr.first())
-        (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<T, NT, MI, NI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (FOLD) splits = 1;
     const int tiles = ((p.N + NI * 64 - 1) / (NI * 64)) * ((p.M + MI * 32 - 1) / (MI * 32));
     const int cus = device_cus();
     const int units = tiles * splits;
     dim3 grid(units < cus ? units : cus, 1, 1);  // persistent: one 112-160-KiB-LDS workgroup per CU
     if (splits > 1) {
-        hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI>), grid, dim3(512), lds, stream, split_view(p, splits));
+        hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI, FOLD>), grid, dim3(512), lds, stream, split_view(p, splits));
         if (!p.defer_fixup) launch_fixup<T, NT>(p, splits, stream);
     } else {
-        hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI>), grid, dim3(512), lds, stream, p);
+        hipLaunchKernelGGL((gemm_pp_kernel<T, NT, MI, NI, FOLD>), grid, dim3(512), lds, stream, p);
     }
-    return true;
 }
 
 // Tile height (256 or 128 rows) and number of K chunks of a ping-pong product, by a cost model in units of one 32-deep MFMA
@@ -250,17 +244,6 @@ void pp_plan(int NT, const GemmParams& p, int* mi_out, int* splits_out, int* ni_
         }
 }
 
-// (the caller has checked pp_eligible) false: nothing was launched, see launch_pp_tiles
-template <typename T, int NT>
-bool launch_gemm_pp(const GemmParams& p, hipStream_t stream) {
-    int mi, splits, ni;
-    pp_plan(NT, p, &mi, &splits, &ni);
-    if (mi == 8 && ni == 4) return launch_pp_tiles<T, NT, 8, 4>(p, splits, stream);
-    if (mi == 8) return launch_pp_tiles<T, NT, 8, 3>(p, splits, stream);
-    if (ni == 4) return launch_pp_tiles<T, NT, 4, 4>(p, splits, stream);
-    return launch_pp_tiles<T, NT, 4, 3>(p, splits, stream);
-}
-
 bool dma_tile_eligible(int NT, const GemmParams& p) {
     if (p.K % BK != 0) return false;
     if (p.lda % 8 || p.ldw % 8 || p.a_plane % 8 || p.w_plane % 8 || p.a_batch_stride % 8 || p.za % 8 || p.zw % 8) return false;
@@ -272,8 +255,7 @@ bool dma_tile_eligible(int NT, const GemmParams& p) {
     if ((a_il && (p.lda % 32 || p.a_batch_stride % 32 || p.za % 32)) || (w_il && (p.ldw % 32 || p.zw % 32))) return false;
     const int64_t a_span = (a_il ? 2 : 1) * (batches_per_tile * p.a_batch_stride + 128 * p.lda + p.K) + (NT > 1 ? p.a_plane : 0);
     const int64_t w_span = (w_il ? 2 : 1) * (64 * p.ldw + p.K) + (NT > 1 ? p.w_plane : 0);
-    if (a_span < 0 || w_span < 0 || a_span * 2 >= (int64_t)0xFFFFFF00 || w_span * 2 >= (int64_t)0xFFFFFF00) return false;
-    return true;
+    return spans_fit(a_span, w_span);
 }
 
 // the LDS-DMA kernel holds one workgroup per CU (144 KiB ring): it serves the short products, big grids keep the
@@ -328,64 +310,88 @@ int dma_preferred_shape(int NT, const GemmParams& p) {
     return 0;
 }
 
-template <typename T, int NT>
-bool launch_gemm_t(const GemmParams& p, hipStream_t stream) {
-    if (!dma_preferred_shape(NT, p) && pp_eligible(NT, p)) return launch_gemm_pp<T, NT>(p, stream);
-    if (p.ln_partial || p.row_coef) return false;  // the fold's epilogues exist in the ping-pong kernel only
-    const int shape = dma_tile_shape(NT, p, 1);  // preferred, or the ping-pong kernel rejected the product
-    if (shape) {
+// What launch_gemm does with a product: THE statement of the routing.  The queries of amx_common.h read it, launch_gemm
+// launches what it says.
+enum class GemmKernel { LN, LN_IL, PP, DMA, TILE };  // row-complete LN kernel, its whole-line variant, ping-pong, LDS-DMA tiles, register-staged tiles
+
+struct GemmRoute {
+    GemmKernel kernel = GemmKernel::TILE;
+    int mi = 0, ni = 0;    // PP: tile height / width in fragments (8 | 4: 256 | 128 rows, 4 | 3: 256 | 192 columns)
+    int fold = 0;          // LayerNorm fold: 0 plain, 1 consumer (row_coef), 2 producer (ln_partial)
+    int shape = 0;         // DMA: 1 = 128 x 64, 2 = 64 x 32
+    int bn = 0;            // TILE: 64 | 128 columns
+    int splits = 1;        // K chunks (1: none).  Fold products launch in one piece whatever this says: gemm_ln_fold_ok refuses them
+    bool launches = true;  // false: nothing will be launched -- a product whose epilogue the kernel of its route does not have
+};
+
+// p: after with_vec_flag.  Depends on nothing but p, device_cus() and g_force_generic_gemm.
+GemmRoute gemm_route(int NT, const GemmParams& p) {
+    GemmRoute r;
+    r.fold = p.ln_partial ? 2 : p.row_coef ? 1 : 0;
+    if (p.ln_gamma) {
+        // fused LayerNorm + GELU: only the row-complete kernels implement it (callers check gemm_fuses_ln first)
+        r.kernel = ln_uses_il(NT, p) ? GemmKernel::LN_IL : GemmKernel::LN;
+        r.launches = ln_eligible(NT, p);
+        return r;
+    }
+    if (!dma_preferred_shape(NT, p) && pp_eligible(NT, p)) {
+        r.kernel = GemmKernel::PP;
+        pp_plan(NT, p, &r.mi, &r.splits, &r.ni);
+        r.launches = !(r.fold == 2 && r.ni != 4);  // 192-column tiles have no producer epilogue
+        return r;
+    }
+    r.launches = !r.fold;  // the fold's epilogues exist in the ping-pong kernel only
+    r.shape = dma_tile_shape(NT, p, 1);  // preferred, or the ping-pong kernel rejected the product
+    if (r.shape) {
         // the ring hides the memory latency, so the K loop is only cut where it is long (K = 4096) and the grid small
-        const int bm = shape == 2 ? 64 : 128, bn = shape == 2 ? 32 : 64;
+        r.kernel = GemmKernel::DMA;
+        const int bm = r.shape == 2 ? 64 : 128, bn = r.shape == 2 ? 32 : 64;
         const int tiles = ((p.N + bn - 1) / bn) * ((p.M + bm - 1) / bm);
-        const int splits = p.K >= 4096 ? choose_splits(p, tiles, device_cus() / 2, BK, 16 * BK) : 1;
-        GemmParams q = p;
-        if (splits > 1) {
-            q = split_view(p, splits);
-            q.za = q.zw = q.K;
-            q.zout = q.split_out;
-            q.zbias = q.zoutp = 0;
-        }
-        launch_gemm_dma_shape<T, NT>(shape, q, splits, stream);
-        if (splits > 1 && !p.defer_fixup) launch_fixup<T, NT>(p, splits, stream);
-        return true;
+        r.splits = p.K >= 4096 ? choose_splits(p, tiles, device_cus() / 2, BK, 16 * BK) : 1;
+        return r;
     }
     // narrow outputs (grouped pos-conv, small classifier heads) use the 128x64 tile
-    const bool narrow = p.N <= 64;
-    const int BM = 128, BN = narrow ? 64 : 128;
-    const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
+    r.bn = p.N <= 64 ? 64 : 128;
+    const int tiles = ((p.N + r.bn - 1) / r.bn) * ((p.M + 127) / 128);
     // short products whose shape the LDS-DMA kernel rejects: the K loop of a register-staged tile is latency-bound, so cut it
-    const int splits = choose_splits(p, tiles, device_cus() / 4, BK, 2 * BK);
-    GemmParams q = p;
-    if (splits > 1) {
-        q = split_view(p, splits);
-        q.za = q.zw = q.K;              // grid.z = K chunk: operand pointers advance by the chunk length,
-        q.zout = q.split_out;           // the fp32 output by one slab
-        q.zbias = q.zoutp = 0;
-    }
-    dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, splits);
-    const size_t lds = (size_t)NT * (BM + BN) * 128;
-    if (narrow) hipLaunchKernelGGL((gemm_kernel<T, NT, 128, 64, 4, 1>), grid, dim3(256), lds, stream, q);
-    else hipLaunchKernelGGL((gemm_kernel<T, NT, 128, 128, 2, 2>), grid, dim3(256), lds, stream, q);
-    if (splits > 1 && !p.defer_fixup) launch_fixup<T, NT>(p, splits, stream);
-    return true;
+    r.splits = choose_splits(p, tiles, device_cus() / 4, BK, 2 * BK);
+    return r;
 }
 
-// the K chunks launch_gemm_t will use: the same decisions, without the launches
-int planned_splits(int NT, const GemmParams& p) {
-    if (!dma_preferred_shape(NT, p) && pp_eligible(NT, p)) {
-        int mi, splits, ni;
-        pp_plan(NT, p, &mi, &splits, &ni);
-        return splits;
+// the ping-pong instance of (r.mi, r.ni, r.fold); producers exist on 256-column tiles only
+template <typename T, int NT, int MI, int NI>
+void launch_pp_fold(const GemmRoute& r, const GemmParams& p, hipStream_t stream) {
+    if (r.fold == 0) launch_pp_tiles<T, NT, MI, NI, 0>(p, r.splits, stream);
+    else if (r.fold == 1) launch_pp_tiles<T, NT, MI, NI, 1>(p, r.splits, stream);
+    else if constexpr (NI == 4) launch_pp_tiles<T, NT, MI, NI, 2>(p, r.splits, stream);
+}
+
+template <typename T, int NT>
+void launch_pp(const GemmRoute& r, const GemmParams& p, hipStream_t stream) {
+    if (r.mi == 8 && r.ni == 4) launch_pp_fold<T, NT, 8, 4>(r, p, stream);
+    else if (r.mi == 8) launch_pp_fold<T, NT, 8, 3>(r, p, stream);
+    else if (r.ni == 4) launch_pp_fold<T, NT, 4, 4>(r, p, stream);
+    else launch_pp_fold<T, NT, 4, 3>(r, p, stream);
+}
+
+// launches what the route says (r.launches checked by the caller)
+template <typename T, int NT>
+void launch_route(const GemmRoute& r, const GemmParams& p, hipStream_t stream) {
+    const GemmParams q = r.splits > 1 ? split_view_z(p, r.splits) : p;  // (DMA, TILE: K chunks on grid.z)
+    switch (r.kernel) {
+        case GemmKernel::LN:
+        case GemmKernel::LN_IL: launch_gemm_ln<T, NT>(p, r.kernel == GemmKernel::LN_IL, stream); return;
+        case GemmKernel::PP: launch_pp<T, NT>(r, p, stream); return;
+        case GemmKernel::DMA: launch_gemm_dma_shape<T, NT>(r.shape, q, r.splits, stream); break;
+        case GemmKernel::TILE: {
+            dim3 grid((p.N + r.bn - 1) / r.bn, (p.M + 127) / 128, r.splits);
+            const size_t lds = (size_t)NT * (128 + r.bn) * 128;
+            if (r.bn == 64) hipLaunchKernelGGL((gemm_kernel<T, NT, 128, 64, 4, 1>), grid, dim3(256), lds, stream, q);
+            else hipLaunchKernelGGL((gemm_kernel<T, NT, 128, 128, 2, 2>), grid, dim3(256), lds, stream, q);
+            break;
+        }
     }
-    const int shape = dma_tile_shape(NT, p, 1);
-    if (shape) {
-        const int bm = shape == 2 ? 64 : 128, bn = shape == 2 ? 32 : 64;
-        const int tiles = ((p.N + bn - 1) / bn) * ((p.M + bm - 1) / bm);
-        return p.K >= 4096 ? choose_splits(p, tiles, device_cus() / 2, BK, 16 * BK) : 1;
-    }
-    const int BN = p.N <= 64 ? 64 : 128;
-    const int tiles = ((p.N + BN - 1) / BN) * ((p.M + 127) / 128);
-    return choose_splits(p, tiles, device_cus() / 4, BK, 2 * BK);
+    if (r.splits > 1 && !p.defer_fixup) launch_fixup<T, NT>(p, r.splits, stream);
 }
 
 template <typename T, int NT>
@@ -420,31 +426,35 @@ static GemmParams with_vec_flag(const GemmParams& in) {
     return p;
 }
 
-bool gemm_fuses_ln(int prec, const GemmParams& p_in) { return ln_eligible(prec_planes(prec), with_vec_flag(p_in)); }
+static GemmRoute route_of(int prec, const GemmParams& p) { return gemm_route(prec_planes(prec), with_vec_flag(p)); }
 
-int gemm_ln_tap_minor_slice(int prec, const GemmParams& p_in) {
-    const int NT = prec_planes(prec);
-    const GemmParams p = with_vec_flag(p_in);
-    if (!ln_eligible(NT, p) || !ln_uses_il(NT, p)) return 0;
-    return NT == 2 ? 32 : 64;
+bool gemm_fuses_ln(int prec, const GemmParams& p) {
+    const GemmRoute r = route_of(prec, p);
+    return (r.kernel == GemmKernel::LN || r.kernel == GemmKernel::LN_IL) && r.launches;
 }
 
-bool gemm_uses_pp(int prec, const GemmParams& p_in) {
-    const GemmParams p = with_vec_flag(p_in);
-    const int NT = prec_planes(prec);
-    return pp_eligible(NT, p) && !dma_preferred_shape(NT, p);  // the routing of launch_gemm_t
+int gemm_ln_tap_minor_slice(int prec, const GemmParams& p) {
+    const GemmRoute r = route_of(prec, p);
+    return r.kernel == GemmKernel::LN_IL && r.launches ? (prec_planes(prec) == 2 ? 32 : 64) : 0;
 }
+
+// gemm_uses_pp and gemm_ln_fold_ok answer for the product itself, whatever LayerNorm is fused behind it: a convolution whose
+// LayerNorm does not fuse is launched, and timed, as that product
+static GemmRoute product_route_of(int prec, GemmParams p) {
+    p.ln_gamma = nullptr;
+    return route_of(prec, p);
+}
+
+bool gemm_uses_pp(int prec, const GemmParams& p) { return product_route_of(prec, p).kernel == GemmKernel::PP; }
 
 bool gemm_ln_fold_ok(int prec, const GemmParams& p_in) {
     const GemmParams p = with_vec_flag(p_in);
     const int NT = prec_planes(prec);
-    if (!p.vec_ok || !pp_eligible(NT, p) || dma_preferred_shape(NT, p)) return false;
-    int mi, splits, ni;
-    pp_plan(NT, p, &mi, &splits, &ni);
-    if (splits != 1) return false;
+    const GemmRoute r = product_route_of(prec, p_in);
+    if (!p.vec_ok || r.kernel != GemmKernel::PP || r.splits != 1) return false;
     if (p.ln_partial) {
         // producer: fp32 stream + residual, planes of the new rows, whole 64-column blocks, 256-column tiles
-        if (ni != 4 || p.N % 64 || p.N > 2048 || !p.out_p || !p.ln_rowps || p.act || p.mode || p.row_len || p.row_coef) return false;
+        if (r.ni != 4 || p.N % 64 || p.N > 2048 || !p.out_p || !p.ln_rowps || p.act || p.mode || p.row_len || p.row_coef) return false;
         // the stream: fp32 rows in and out, or (two planes) the planes themselves as the residual and fp32 out only on request
         if (p.ln_res_planes ? NT != 2 : (!p.out_f32 || !p.residual)) return false;
         if (NT == 2 && (p.out_plane != PLANE_IL || p.ldp % 32)) return false;
@@ -457,11 +467,7 @@ bool gemm_ln_fold_ok(int prec, const GemmParams& p_in) {
     return true;
 }
 
-int gemm_planned_splits(int prec, const GemmParams& p_in) {
-    const GemmParams p = with_vec_flag(p_in);
-    if (p.ln_gamma) return 1;
-    return planned_splits(prec_planes(prec), p);
-}
+int gemm_planned_splits(int prec, const GemmParams& p) { return route_of(prec, p).splits; }
 
 bool fixup_rownorm_eligible(const GemmParams& p) {
     return p.splitk_ws && p.out_f32 && !p.out_p && p.act == 0 && p.mode == 0 && !p.row_len && !p.ln_gamma && p.N % 4 == 0 &&
@@ -471,42 +477,20 @@ bool fixup_rownorm_eligible(const GemmParams& p) {
 
 void launch_fixup_rownorm(int prec, const GemmParams& p, int splits, const float* gamma, const float* beta, float eps, void* out_p,
                           int64_t out_plane, int64_t ldp, float* out_ln, int64_t ldo_ln, hipStream_t stream) {
-    switch (prec) {
-        case PREC_BF16: launch_fixup_rownorm_t<bf16, 1>(p, splits, gamma, beta, eps, out_p, out_plane, ldp, out_ln, ldo_ln, stream); break;
-        case PREC_F16: launch_fixup_rownorm_t<f16, 1>(p, splits, gamma, beta, eps, out_p, out_plane, ldp, out_ln, ldo_ln, stream); break;
-        case PREC_BF16X3: launch_fixup_rownorm_t<bf16, 2>(p, splits, gamma, beta, eps, out_p, out_plane, ldp, out_ln, ldo_ln, stream); break;
-        default: launch_fixup_rownorm_t<f16, 2>(p, splits, gamma, beta, eps, out_p, out_plane, ldp, out_ln, ldo_ln, stream); break;
-    }
+    AMX_DISPATCH(prec, (launch_fixup_rownorm_t<T16, NT>(p, splits, gamma, beta, eps, out_p, out_plane, ldp, out_ln, ldo_ln, stream)));
 }
 
 bool launch_gemm(int prec, const GemmParams& p_in, hipStream_t stream) {
     const GemmParams p = with_vec_flag(p_in);
-    if (p.ln_gamma) {
-        // fused LayerNorm + GELU: only the row-complete kernel implements it (callers check gemm_fuses_ln first)
-        switch (prec) {
-            case PREC_BF16: launch_gemm_ln<bf16, 1>(p, stream); break;
-            case PREC_F16: launch_gemm_ln<f16, 1>(p, stream); break;
-            case PREC_BF16X3: launch_gemm_ln<bf16, 2>(p, stream); break;
-            default: launch_gemm_ln<f16, 2>(p, stream); break;
-        }
-        return true;
-    }
-    switch (prec) {
-        case PREC_BF16: return launch_gemm_t<bf16, 1>(p, stream);
-        case PREC_F16: return launch_gemm_t<f16, 1>(p, stream);
-        case PREC_BF16X3: return launch_gemm_t<bf16, 2>(p, stream);
-        default: return launch_gemm_t<f16, 2>(p, stream);
-    }
+    const GemmRoute r = gemm_route(prec_planes(prec), p);
+    if (!r.launches) return false;
+    AMX_DISPATCH(prec, (launch_route<T16, NT>(r, p, stream)));
+    return true;
 }
 
 void launch_gemm_grouped(int prec, const GemmParams& p_in, int groups, hipStream_t stream) {
     const GemmParams p = with_vec_flag(p_in);
-    switch (prec) {
-        case PREC_BF16: launch_gemm_z<bf16, 1>(p, groups, stream); break;
-        case PREC_F16: launch_gemm_z<f16, 1>(p, groups, stream); break;
-        case PREC_BF16X3: launch_gemm_z<bf16, 2>(p, groups, stream); break;
-        default: launch_gemm_z<f16, 2>(p, groups, stream); break;
-    }
+    AMX_DISPATCH(prec, (launch_gemm_z<T16, NT>(p, groups, stream)));
 }
 
 }  // namespace amx

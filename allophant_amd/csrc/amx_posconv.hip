@@ -207,12 +207,8 @@ bool posconv_window_eligible(int D, int G, int taps, int N, int Tn, int Tpad, in
 void launch_posconv_window(int prec, const void* image, int64_t image_plane, const void* weights, int64_t w_plane, int64_t ldw,
                            const float* bias, float scale, float* h, int N, int Tn, int Tpad, int D, int G, int taps, const int* row_off,
                            const int* frame_len, hipStream_t s) {
-    switch (prec) {
-        case PREC_BF16: launch_posconv_t<bf16, 1>(image, image_plane, weights, w_plane, ldw, bias, scale, h, N, Tn, Tpad, D, G, taps, row_off, frame_len, s); break;
-        case PREC_F16: launch_posconv_t<f16, 1>(image, image_plane, weights, w_plane, ldw, bias, scale, h, N, Tn, Tpad, D, G, taps, row_off, frame_len, s); break;
-        case PREC_BF16X3: launch_posconv_t<bf16, 2>(image, image_plane, weights, w_plane, ldw, bias, scale, h, N, Tn, Tpad, D, G, taps, row_off, frame_len, s); break;
-        default: launch_posconv_t<f16, 2>(image, image_plane, weights, w_plane, ldw, bias, scale, h, N, Tn, Tpad, D, G, taps, row_off, frame_len, s); break;
-    }
+    AMX_DISPATCH(prec, (launch_posconv_t<T16, NT>(image, image_plane, weights, w_plane, ldw, bias, scale, h, N, Tn, Tpad, D, G, taps, row_off,
+                                                  frame_len, s)));
 }
 
 }  // namespace amx

@@ -1543,14 +1543,6 @@ inline int grid_for(int64_t n, int block = 256, int cap = 8192) {
 
 }  // namespace
 
-#define AMX_DISPATCH(prec, CALL)                                   \
-    switch (prec) {                                                \
-        case PREC_BF16: { typedef bf16 T16; constexpr int NT = 1; CALL; } break;   \
-        case PREC_F16: { typedef f16 T16; constexpr int NT = 1; CALL; } break;     \
-        case PREC_BF16X3: { typedef bf16 T16; constexpr int NT = 2; CALL; } break; \
-        default: { typedef f16 T16; constexpr int NT = 2; CALL; } break;           \
-    }
-
 void launch_audio_stats(const float* audio, const int64_t* lengths, int N, int64_t L, double* partial, float* mean_rstd,
                         int do_normalize, hipStream_t s) {
     if (do_normalize) hipLaunchKernelGGL(audio_stats_kernel, dim3(STAT_CHUNKS, N), dim3(256), 0, s, audio, lengths, L, partial);

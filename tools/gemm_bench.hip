@@ -96,24 +96,12 @@ static bool g_compare_nosplit = false;
 static float* g_splitk_ws = nullptr;
 static const int64_t SPLITK_ELEMS = (int64_t)18 << 20;
 
-// a ping-pong product on the given tile width (NI = 4: 256 columns, 3: 192 columns) with the plan's tile height and K chunks
-template <typename T, int NT>
-static void launch_pp_width_t(const GemmParams& p, int ni, hipStream_t s) {
-    int mi, splits, plan_ni;
-    pp_plan(NT, p, &mi, &splits, &plan_ni);
-    if (mi == 8 && ni == 4) launch_pp_tiles<T, NT, 8, 4>(p, splits, s);
-    else if (mi == 8) launch_pp_tiles<T, NT, 8, 3>(p, splits, s);
-    else if (ni == 4) launch_pp_tiles<T, NT, 4, 4>(p, splits, s);
-    else launch_pp_tiles<T, NT, 4, 3>(p, splits, s);
-}
+// a ping-pong product on the given tile width (NI = 4: 256 columns, 3: 192 columns): its own route with the width replaced
 static void launch_pp_width(int prec, const GemmParams& g, int ni, hipStream_t s) {
     const GemmParams p = with_vec_flag(g);
-    switch (prec) {
-        case PREC_BF16: launch_pp_width_t<bf16, 1>(p, ni, s); break;
-        case PREC_F16: launch_pp_width_t<f16, 1>(p, ni, s); break;
-        case PREC_BF16X3: launch_pp_width_t<bf16, 2>(p, ni, s); break;
-        default: launch_pp_width_t<f16, 2>(p, ni, s); break;
-    }
+    GemmRoute r = gemm_route(prec_planes(prec), p);
+    r.ni = ni;
+    AMX_DISPATCH(prec, (launch_route<T16, NT>(r, p, s)));
 }
 
 // ni: 0 = launch_gemm's own choice; 4 / 3 = a product that takes the ping-pong kernel runs on that tile width (*pp_out: it did)
