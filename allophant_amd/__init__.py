@@ -9,7 +9,8 @@ from . import spec, synthetic  # noqa: F401
 __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCDecoder", "CTCHypothesis", "BeamCTCDecoder",
            "BeamDecoded", "feature_decoders", "EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator",
            "levensthein_statistics", "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations",
-           "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions"]
+           "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
+           "levensthein_matrix"]
 __version__ = "0.1.0"
 
 
@@ -22,7 +23,7 @@ def __getattr__(name):
         return getattr(estimator, name)
     if name in ("EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator", "levensthein_statistics",
                 "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations", "levensthein_operations_batch",
-                "levensthein_substitutions", "to_substitutions"):
+                "levensthein_substitutions", "to_substitutions", "PropertyWeighting", "levensthein_matrix"):
         from . import evaluation
 
         return getattr(evaluation, name)

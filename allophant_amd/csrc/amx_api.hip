@@ -2436,6 +2436,144 @@ extern "C" int amx_edit_operations(int device, const int64_t* tokens, int64_t st
     return AMX_OK;
 }
 
+// feature-weighted edit distance
+static std::string edit_cost_limits(float insertion_cost, float deletion_cost) {
+    if (!std::isfinite(insertion_cost) || !std::isfinite(deletion_cost) || insertion_cost <= 0.f || deletion_cost <= 0.f)
+        return "insertion and deletion costs must be finite and above 0";
+    return "";
+}
+
+extern "C" int amx_edit_cost_table_bytes(int64_t V, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (V < 1 || V > AMX_EDIT_MAX_SYMBOLS)
+        return fail(nullptr, AMX_EINVAL, "a cost table covers 1 to " + std::to_string(AMX_EDIT_MAX_SYMBOLS) + " symbols");
+    *bytes = (size_t)V * (size_t)V;
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_cost_table(int device, const uint8_t* codes, int64_t V, int64_t F, uint8_t* table, void* stream) {
+    if (V < 1 || V > AMX_EDIT_MAX_SYMBOLS)
+        return fail(nullptr, AMX_EINVAL, "a cost table covers 1 to " + std::to_string(AMX_EDIT_MAX_SYMBOLS) + " symbols");
+    if (F < 0 || F > AMX_EDIT_MAX_FEATURES)
+        return fail(nullptr, AMX_EINVAL, "feature rows hold 0 to " + std::to_string(AMX_EDIT_MAX_FEATURES) + " columns");
+    if (!table || (F > 0 && !codes)) return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_edit_cost_table(codes, (int)V, (int)F, table, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "cost table launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_weighted_statistics(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k,
+                                            int O, int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                            const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                            const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                            const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual,
+                                            void* workspace, size_t workspace_bytes, float insertion_cost, float deletion_cost,
+                                            const int64_t* cost_tables, const uint8_t* cost_table_data, int32_t* statistics,
+                                            int32_t* best, uint64_t* totals, float* costs, void* stream) {
+    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
+    if (K < 1 || K > AMX_EDIT_MAX_CANDIDATES)
+        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
+    std::string err = edit_limits(max_expected, max_actual);
+    if (err.empty()) err = edit_cost_limits(insertion_cost, deletion_cost);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
+    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
+    const int64_t rows = (int64_t)O * N * K;
+    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N * K must stay below 2^31");
+    if (rows == 0) return AMX_OK;
+    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
+        !workspace || !statistics || !best || !totals || !cost_tables || !costs)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (workspace_bytes < edit_workspace_bytes(rows, max_expected, max_actual))
+        return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_workspace");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    amx::EditWeightedArgs w{};
+    amx::EditArgs& a = w.x.e;
+    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = stride_k, a.T = T;
+    a.O = O, a.N = N, a.K = K, a.G = G, a.H = H;
+    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
+    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
+    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
+    a.workspace = (int32_t*)workspace, a.statistics = statistics, a.best = best, a.totals = totals;
+    w.insertion_cost = insertion_cost, w.deletion_cost = deletion_cost;
+    w.tables = cost_tables, w.table_data = cost_table_data, w.costs = costs;
+    launch_edit_weighted_statistics(w, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "weighted edit statistics launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_weighted_operations(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int O, int N,
+                                            int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                            const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                            const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                            const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual,
+                                            void* workspace, size_t workspace_bytes, float insertion_cost, float deletion_cost,
+                                            const int64_t* cost_tables, const uint8_t* cost_table_data, int64_t max_ops,
+                                            int32_t* operations, int32_t* operation_counts, float* costs, void* stream) {
+    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
+    std::string err = edit_limits(max_expected, max_actual);
+    if (err.empty()) err = edit_cost_limits(insertion_cost, deletion_cost);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (max_ops < max_expected + max_actual || max_ops > INT32_MAX)
+        return fail(nullptr, AMX_EINVAL, "max_ops must be max_expected + max_actual to 2^31 - 1");
+    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
+    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
+    const int64_t rows = (int64_t)O * N;
+    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N must stay below 2^31");
+    size_t needed = 0;
+    if (!edit_operations_workspace_bytes(rows, max_expected, max_actual, &needed))
+        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
+    if (rows == 0) return AMX_OK;
+    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
+        !workspace || !operations || !operation_counts || !cost_tables || !costs)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (workspace_bytes < needed) return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_operations_workspace");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    amx::EditWeightedArgs w{};
+    amx::EditArgs& a = w.x.e;
+    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = 0, a.T = T;
+    a.O = O, a.N = N, a.K = 1, a.G = G, a.H = H;
+    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
+    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
+    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
+    a.workspace = (int32_t*)workspace;
+    w.x.max_ops = max_ops, w.x.operations = operations, w.x.operation_counts = operation_counts;
+    w.insertion_cost = insertion_cost, w.deletion_cost = deletion_cost;
+    w.tables = cost_tables, w.table_data = cost_table_data, w.costs = costs;
+    launch_edit_weighted_operations(w, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "weighted edit operations launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_matrix(int device, const int32_t* expected_offsets, const int32_t* expected_ids,
+                               const int32_t* actual_offsets, const int32_t* actual_ids, int64_t rows, int64_t max_expected,
+                               int64_t max_actual, float insertion_cost, float deletion_cost, const uint8_t* cost_table, int64_t V,
+                               void* workspace, size_t workspace_bytes, float* matrix, int32_t* status, void* stream) {
+    if (rows < 0 || rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "rows must be 0 to 2^31 - 1");
+    std::string err = edit_limits(max_expected, max_actual);
+    if (err.empty()) err = edit_cost_limits(insertion_cost, deletion_cost);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (V < 0 || V > AMX_EDIT_MAX_SYMBOLS)
+        return fail(nullptr, AMX_EINVAL, "a cost table covers at most " + std::to_string(AMX_EDIT_MAX_SYMBOLS) + " symbols");
+    if (rows == 0) return AMX_OK;
+    if (!expected_offsets || !expected_ids || !actual_offsets || !actual_ids || !workspace || !matrix || !status ||
+        (V > 0 && !cost_table))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (workspace_bytes < edit_workspace_bytes(rows, max_expected, max_actual))
+        return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_workspace");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    amx::EditMatrixArgs a{};
+    a.expected_offsets = expected_offsets, a.expected_ids = expected_ids;
+    a.actual_offsets = actual_offsets, a.actual_ids = actual_ids;
+    a.rows = (int)rows, a.cap_a = (int)max_expected, a.cap_b = (int)max_actual, a.V = (int)V, a.table = cost_table;
+    a.insertion_cost = insertion_cost, a.deletion_cost = deletion_cost;
+    a.workspace = (int2*)workspace, a.matrix = matrix, a.status = status;
+    launch_edit_matrix(a, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit matrix launch failed");
+    return AMX_OK;
+}
+
 // =================================================================================================================
 // allophone layer
 // =================================================================================================================

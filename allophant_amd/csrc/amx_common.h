@@ -545,6 +545,33 @@ struct EditOpsArgs {
 bool edit_operations_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes);
 void launch_edit_operations(EditOpsArgs x, hipStream_t s);
 
+// feature-weighted edit distance (amx_edit_weighted.hip): upstream's PropertyWeighting, contract in
+// include/allophant_amx_edit.h.  The rows, maps and workspace layouts are those of the uniform calls (x.e, x); costs are fp32
+// and a substitution costs tables[o]'s byte (expected id, actual id): (first, V) names a uint8 [V, V] table at
+// table_data + first, V == 0 none (a != b).
+struct EditWeightedArgs {
+    EditOpsArgs x;
+    float insertion_cost, deletion_cost;
+    const int64_t* tables;      // [O, 2]
+    const uint8_t* table_data;
+    float* costs;               // statistics: [O, N, K]; operations: [O, N]
+};
+void launch_edit_cost_table(const uint8_t* codes, int V, int F, uint8_t* table, hipStream_t s);
+void launch_edit_weighted_statistics(EditWeightedArgs w, hipStream_t s);
+void launch_edit_weighted_operations(EditWeightedArgs w, hipStream_t s);
+// pairs handed over directly: row r compares expected_ids[expected_offsets[r] .. [r + 1]) with the same of `actual`
+struct EditMatrixArgs {
+    const int32_t *expected_offsets, *expected_ids, *actual_offsets, *actual_ids;
+    int rows, cap_a, cap_b, V;  // V == 0: no table
+    const uint8_t* table;
+    float insertion_cost, deletion_cost;
+    int64_t bnd_pad;            // int2 cells per boundary row
+    int2* workspace;            // two boundary rows per row
+    float* matrix;              // [rows, cap_a + 1, cap_b + 1]
+    int32_t* status;            // [rows]: 0, or -2 for a flagged row
+};
+void launch_edit_matrix(EditMatrixArgs a, hipStream_t s);
+
 // weight packing helpers (device side; run once at amx_create / amx_set_inventory)
 void launch_pack_matrix(int prec, const float* src, int rows, int cols, int64_t src_row_stride, int64_t src_col_stride,
                         float scale, void* dst, int64_t dst_plane, int64_t ldd, int cols_pad, hipStream_t s);

@@ -16,8 +16,6 @@ namespace {
 
 #include "amx_edit_dp.inc"
 
-constexpr int SELECT_THREADS = 256;
-
 __global__ __launch_bounds__(WAVE) void edit_rows_kernel(EditArgs a) {
     const int64_t r = blockIdx.x;  // (o * N + n) * K + k
     const int lane = threadIdx.x;
@@ -60,33 +58,8 @@ __global__ __launch_bounds__(WAVE) void edit_rows_kernel(EditArgs a) {
     if (lane < 4) st[lane] = lane == 0 ? I : lane == 1 ? D : lane == 2 ? S : C;
 }
 
-// One thread per (output, utterance): the first candidate of strictly lowest fp32 word_error_rate, then its counts added.
-__global__ __launch_bounds__(SELECT_THREADS) void edit_select_kernel(EditArgs a) {
-    const int64_t on = (int64_t)blockIdx.x * SELECT_THREADS + threadIdx.x;
-    if (on >= (int64_t)a.O * a.N) return;
-    const int n = (int)(on % a.N), o = (int)(on / a.N);
-    const int present = a.hyp_counts ? min(max(a.hyp_counts[on], 0), a.K) : a.K;
-    const int g = a.groups[n];
-    int best = g < 0 || g >= a.G ? -2 : -1;
-    float lowest = __builtin_huge_valf();
-    for (int k = 0; k < present && best != -2; ++k) {
-        const int32_t* st = a.statistics + (on * a.K + k) * 4;
-        if (st[0] < 0) {
-            best = -2;
-            break;
-        }
-        // edit_distance.rs word_error_rate: (f32(S + D) + f32(I)) / (f32(S + D) + f32(C)), correctly rounded
-        const float sd = (float)(st[2] + st[1]);
-        const float rate = (sd + (float)st[0]) / (sd + (float)st[3]);
-        if (rate < lowest) lowest = rate, best = k;
-    }
-    a.best[on] = best;
-    if (best >= 0) {
-        const int32_t* st = a.statistics + (on * a.K + best) * 4;
-        unsigned long long* total = reinterpret_cast<unsigned long long*>(a.totals) + ((int64_t)g * a.O + o) * 4;
-        for (int q = 0; q < 4; ++q) atomicAdd(total + q, (unsigned long long)st[q]);
-    }
-}
+// One thread per (output, utterance): select_candidate of amx_edit_dp.inc.
+__global__ __launch_bounds__(SELECT_THREADS) void edit_select_kernel(EditArgs a) { select_candidate(a); }
 
 }  // namespace
 

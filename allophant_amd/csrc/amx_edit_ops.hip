@@ -23,22 +23,6 @@ namespace {
 
 #include "amx_edit_dp.inc"
 
-// The sweep's hook for the operations: per strip s and step t, bit l of (diagonal lo, hi, second lo, hi) is lane l's move.
-struct PathCodes {
-    uint4* codes;    // this row's words: strip s, step t at codes[s * stride + t]
-    int64_t stride;  // words per strip
-    uint4 word;      // staged: lane c holds step 64 q + c of the current 64 steps
-    __device__ void step(int s, int t, bool last, bool diag, bool second, int lane) {
-        const unsigned long long d = __ballot(diag), q = __ballot(second);
-        const int c = t & (WAVE - 1);
-        if (lane == c) word = make_uint4((uint32_t)d, (uint32_t)(d >> 32), (uint32_t)q, (uint32_t)(q >> 32));
-        if (c == WAVE - 1 || last) {
-            const int col = (t & ~(WAVE - 1)) + lane;
-            if (col <= t) codes[s * stride + col] = word;
-        }
-    }
-};
-
 __device__ __forceinline__ void flag_row(const EditOpsArgs& x, int64_t r, int value, int lane) {
     if (lane == 0) x.operation_counts[r] = value;
 }
@@ -69,49 +53,7 @@ __global__ __launch_bounds__(WAVE) void edit_ops_kernel(EditOpsArgs x) {
     PathCodes path{codes, x.code_stride, make_uint4(0, 0, 0, 0)};
     const int cost = carried_dp(A, m, B, nb, bnd0, bnd1, lane, path).x;  // its last strip ends with a fence: the codes are visible
 
-    int32_t* out = x.operations + r * x.max_ops * 5;
-    int i = m, j = nb, k = 0, written = 0;
-    int win_s = -1, win_t = 0;  // the loaded window: strip win_s, steps [win_t, win_t + 64)
-    uint4 w = make_uint4(0, 0, 0, 0);
-    int rec_act = 0, rec_i = 0, rec_j = 0;  // lane q stages operation written + q
-    while (k < cost && (i > 0 || j > 0)) {  // (the origin is never reached first; the guard keeps every index in range)
-        int act = 0;  // 0: a match, recorded as nothing
-        if (i == 0) {
-            act = AMX_EDIT_INSERTION, --j;
-        } else if (j == 0) {
-            act = AMX_EDIT_DELETION, --i;
-        } else {
-            const int s = (i - 1) / WAVE, l = (i - 1) % WAVE, t = j + l;
-            if (s != win_s || t < win_t) {
-                win_s = s, win_t = max(0, t - (WAVE - 1));
-                w = codes[s * x.code_stride + win_t + lane];  // win_t + 63 <= max(t, 63) < code_stride
-            }
-            const int q = t - win_t, bit = l & 31;
-            const bool diag = ((uint32_t)lane_value(l < 32 ? w.x : w.y, q) >> bit) & 1;
-            const bool second = ((uint32_t)lane_value(l < 32 ? w.z : w.w, q) >> bit) & 1;
-            if (diag) {
-                --i, --j;
-                if (second) act = AMX_EDIT_SUBSTITUTION;
-            } else if (second) {
-                act = AMX_EDIT_DELETION, --i;
-            } else {
-                act = AMX_EDIT_INSERTION, --j;
-            }
-        }
-        if (act == 0) continue;
-        if (lane == k - written) rec_act = act, rec_i = i, rec_j = j;  // the coordinates after the move
-        ++k;
-        if (k - written == WAVE || k == cost) {
-            const int q = written + lane;
-            if (q < k) {
-                int32_t* rec = out + (int64_t)(cost - 1 - q) * 5;
-                rec[0] = rec_act, rec[1] = rec_i, rec[2] = rec_j;
-                rec[3] = rec_act != AMX_EDIT_INSERTION ? A[rec_i] : -1;
-                rec[4] = rec_act != AMX_EDIT_DELETION ? B[rec_j] : -1;
-            }
-            written = k;
-        }
-    }
+    walk_operations(codes, x.code_stride, A, m, B, nb, cost, x.operations + r * x.max_ops * 5, lane);
     if (lane == 0) x.operation_counts[r] = cost;
 }
 

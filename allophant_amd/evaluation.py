@@ -14,6 +14,10 @@ or the category ``feature_values(name, token - 1)``; the blank expands to nothin
 ``Evaluator.operations`` / ``Evaluator.edits`` are upstream's ``run.py edits`` (run.py:502-528) on the same ids: the
 ``amx_edit_operations`` kernel walks ``levensthein_operations``'s path for the first candidate of every (output, utterance), and
 ``edits`` turns the records into ``UtteranceEdits`` (predictions.py:58-83) with one host synchronisation.
+
+``PropertyWeighting`` is upstream's class of that name (edit_distance.rs:498-599): fp32 insertion and deletion costs and, as the
+substitution cost, the number of features in which two phonemes' rows of a property table differ, through the
+``amx_edit_weighted_*`` / ``amx_edit_matrix`` kernels.  ``Evaluator(weighting=...)`` scores the IPA outputs under it.
 """
 from __future__ import annotations
 
@@ -33,7 +37,8 @@ from .phonetic import IPA_LAYERS, AttributeTable, InventoryView, split_complex_s
 
 __all__ = ["EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "EvaluationMaps", "Evaluator", "LabelBatch", "levensthein_statistics",
            "levensthein_statistics_batch", "unicode_replacements", "Action", "UtteranceEdits", "levensthein_operations",
-           "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions"]
+           "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
+           "levensthein_matrix"]
 
 TOTAL = "total"
 STATISTICS_FIELDS = ("insertions", "deletions", "substitutions", "correct")  # the kernel's order
@@ -295,6 +300,22 @@ def _library():
     return handle
 
 
+def _weighted_library():
+    handle = _library()
+    if not hasattr(handle, "amx_edit_weighted_statistics"):
+        raise RuntimeError("liballophant_amx.so lacks amx_edit_weighted_statistics: rebuild the library")
+    return handle
+
+
+class _Weights(NamedTuple):
+    """The cost arguments of the weighted kernels: per output a descriptor (first, V) into ``data``, the concatenated
+    pairwise cost tables (V == 0: no table, ``a != b``)."""
+    insertion_cost: float
+    deletion_cost: float
+    descriptors: Tensor  # int64 [O, 2]
+    data: Optional[Tensor]  # uint8
+
+
 def _device(device) -> torch.device:
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda" or not torch.cuda.is_available():
@@ -309,10 +330,12 @@ def _ptr(t: Optional[Tensor], offset: int = 0):
 
 def _run(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int, G: int,
          maps: Tensor, n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int, max_actual: int,
-         workspace: Optional[Tensor], totals: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-    """One ``amx_edit_statistics`` call.  ``labels`` is the uploaded int32 block [offsets N + 1 | groups N | label ids],
-    ``maps`` the uploaded int32 block [map offsets | map values]; returns (statistics, best, workspace)."""
-    handle = _library()
+         workspace: Optional[Tensor], totals: Tensor, weights: Optional["_Weights"] = None
+         ) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
+    """One ``amx_edit_statistics`` call, or with ``weights`` one ``amx_edit_weighted_statistics`` call.  ``labels`` is the
+    uploaded int32 block [offsets N + 1 | groups N | label ids], ``maps`` the uploaded int32 block [map offsets | map values];
+    returns (statistics, best, workspace, costs float32 [O, N, K] or None; NaN where nothing was scored)."""
+    handle = _library() if weights is None else _weighted_library()
     O, N_, K, T = tokens.shape
     rows = O * N_ * K
     size = C.c_size_t()
@@ -324,41 +347,55 @@ def _run(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optio
     if tokens.stride(3) != 1:
         tokens = tokens.contiguous()
     stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.device(device):
-        code = handle.amx_edit_statistics(
-            device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), tokens.stride(2), O, N_, K, T, _ptr(counts),
+    head = (device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), tokens.stride(2), O, N_, K, T, _ptr(counts),
             _ptr(hyp_counts), _ptr(labels), _ptr(labels, 2 * N + 1), _ptr(labels, N + 1), G, _ptr(maps), _ptr(maps, n_offsets),
-            _ptr(label_maps), _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel(), _ptr(statistics),
-            _ptr(best), _ptr(totals), C.c_void_p(stream))
+            _ptr(label_maps), _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel())
+    costs = None
+    with torch.cuda.device(device):
+        if weights is None:
+            code = handle.amx_edit_statistics(*head, _ptr(statistics), _ptr(best), _ptr(totals), C.c_void_p(stream))
+        else:
+            costs = torch.full((O, N_, K), float("nan"), dtype=torch.float32, device=device)
+            code = handle.amx_edit_weighted_statistics(
+                *head, weights.insertion_cost, weights.deletion_cost, _ptr(weights.descriptors), _ptr(weights.data),
+                _ptr(statistics), _ptr(best), _ptr(totals), _ptr(costs), C.c_void_p(stream))
     _lib.check(handle, None, code)
-    return statistics, best, workspace
+    return statistics, best, workspace, costs
 
 
 def _run_operations(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int,
                     G: int, maps: Tensor, n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int,
-                    max_actual: int, workspace: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
-    """One ``amx_edit_operations`` call on candidate 0: ``tokens`` [O, N, T], ``counts`` int32 [O, N]; arguments otherwise as
-    ``_run``.  Returns (operations int32 [O, N, max_ops, 5], operation counts int32 [O, N], workspace)."""
-    handle = _library()
+                    max_actual: int, workspace: Optional[Tensor], weights: Optional["_Weights"] = None
+                    ) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
+    """One ``amx_edit_operations`` (with ``weights``: ``amx_edit_weighted_operations``) call on candidate 0: ``tokens``
+    [O, N, T], ``counts`` int32 [O, N]; arguments otherwise as ``_run``.  Returns (operations int32 [O, N, max_ops, 5],
+    operation counts int32 [O, N], workspace, costs float32 [O, N] or None; NaN where there is no path)."""
+    handle = _library() if weights is None else _weighted_library()
     O, N_, T = tokens.shape
     size = C.c_size_t()
     _lib.check(handle, None, handle.amx_edit_operations_workspace(O * N_, max_expected, max_actual, C.byref(size)))
     if workspace is None or workspace.numel() < size.value:
         workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=device)
-    max_ops = max(1, max_expected, max_actual)
+    max_ops = max(1, max_expected, max_actual) if weights is None else max(1, max_expected + max_actual)
     operations = torch.empty(O, N_, max_ops, 5, dtype=torch.int32, device=device)
     operation_counts = torch.empty(O, N_, dtype=torch.int32, device=device)
     if tokens.stride(2) != 1:
         tokens = tokens.contiguous()
     stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.device(device):
-        code = handle.amx_edit_operations(
-            device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), O, N_, T, _ptr(counts), _ptr(hyp_counts),
+    head = (device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), O, N_, T, _ptr(counts), _ptr(hyp_counts),
             _ptr(labels), _ptr(labels, 2 * N + 1), _ptr(labels, N + 1), G, _ptr(maps), _ptr(maps, n_offsets), _ptr(label_maps),
-            _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel(), max_ops, _ptr(operations),
-            _ptr(operation_counts), C.c_void_p(stream))
+            _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel())
+    costs = None
+    with torch.cuda.device(device):
+        if weights is None:
+            code = handle.amx_edit_operations(*head, max_ops, _ptr(operations), _ptr(operation_counts), C.c_void_p(stream))
+        else:
+            costs = torch.full((O, N_), float("nan"), dtype=torch.float32, device=device)
+            code = handle.amx_edit_weighted_operations(
+                *head, weights.insertion_cost, weights.deletion_cost, _ptr(weights.descriptors), _ptr(weights.data), max_ops,
+                _ptr(operations), _ptr(operation_counts), _ptr(costs), C.c_void_p(stream))
     _lib.check(handle, None, code)
-    return operations, operation_counts, workspace
+    return operations, operation_counts, workspace, costs
 
 
 def _upload(blocks: Sequence[np.ndarray], device: torch.device) -> Tuple[Tensor, List[int]]:
@@ -484,14 +521,21 @@ class Evaluator:
     the predictions were made under -- the ``phone`` / ``phoneme`` tokens index it; ``languages``: the totals slots, in
     order.  Options as upstream's ``evaluate``: ``split_complex`` (``--split-complex``), ``source_maps`` (language -> phoneme
     -> phoneme: remapping, which ``--no-remap`` turns off) and ``replacements`` (label phoneme -> table phoneme, applied before
-    the attribute lookup: ``--fix-unicode``, see ``unicode_replacements``)."""
+    the attribute lookup: ``--fix-unicode``, see ``unicode_replacements``).
+
+    ``weighting``: a ``PropertyWeighting``; the IPA outputs (``phone``, ``phoneme``) are then scored, chosen and listed under
+    its costs (``add``, ``operations``, ``edits``), while attribute outputs keep unit costs.  Every symbol of an IPA output's
+    id space (label phonemes, inventory, remapped and split forms) must be in its table: ``ValueError`` otherwise."""
 
     def __init__(self, table: AttributeTable, names: Sequence[str], inventory: Union[InventoryView, Sequence[str]],
                  languages: Sequence[str], split_complex: bool = False,
                  source_maps: Optional[Dict[str, Dict[str, str]]] = None, replacements: Optional[Dict[str, str]] = None,
-                 device=None):
+                 device=None, weighting: Optional["PropertyWeighting"] = None):
         self.device = _device(device)
         self.maps = EvaluationMaps(table, names, inventory, languages, split_complex, source_maps, replacements)
+        self.weighting = weighting
+        if weighting is not None:
+            self._init_weighting(weighting)
         self.names, self.languages = self.maps.names, self.maps.languages
         self._n_offsets = len(self.maps.offsets)
         self._maps = torch.from_numpy(np.concatenate([self.maps.offsets, self.maps.values])).to(self.device)
@@ -501,6 +545,74 @@ class Evaluator:
         self._workspace: Optional[Tensor] = None
         self._ops_workspace: Optional[Tensor] = None
         self._rows: Optional[Tuple[Tensor, Tensor]] = None
+        self._costs: Optional[Tensor] = None
+        self._operation_costs: Optional[Tensor] = None
+
+    def _init_weighting(self, weighting: "PropertyWeighting") -> None:
+        """Splits the outputs into the IPA ones, scored under ``weighting`` with one cost table per id space, and the
+        attribute ones, scored by the uniform kernels; each part gets its own descriptors."""
+        weighted = [o for o, name in enumerate(self.maps.names) if name in IPA_LAYERS]
+        uniform = [o for o, name in enumerate(self.maps.names) if name not in IPA_LAYERS]
+        missing = sorted({s for o in weighted for s in self.maps.spaces[o] if not weighting.has(s)})
+        if missing:
+            raise ValueError(f"the property table lacks the symbols {missing}")
+        tables = [weighting.cost_table(list(self.maps.spaces[o]), self.device) for o in weighted]
+        descriptors, first = [], 0
+        for o, t in zip(weighted, tables):
+            descriptors.append((first, len(self.maps.spaces[o])))
+            first += t.numel()
+        data = torch.cat(tables) if first else None
+        self._parts = []
+        for outputs, weights in ((uniform, None), (weighted, _Weights(weighting.insertion_cost, weighting.deletion_cost,
+                                 torch.tensor(descriptors, dtype=torch.int64, device=self.device).reshape(-1, 2), data))):
+            if outputs:
+                index = torch.tensor(outputs, dtype=torch.long, device=self.device)
+                label_maps = torch.from_numpy(np.ascontiguousarray(self.maps.label_maps[outputs]).reshape(-1)).to(self.device)
+                hyp_maps = torch.from_numpy(np.ascontiguousarray(self.maps.hyp_maps[:, outputs]).reshape(-1)).to(self.device)
+                self._parts.append((index, label_maps, hyp_maps, weights))
+        self._part_workspaces: Dict[Tuple[int, bool], Optional[Tensor]] = {}
+
+    def _add_weighted(self, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: "LabelBatch",
+                      max_actual: int) -> Tuple[Tuple[Tensor, Tensor], Tensor]:
+        O, N, K, _ = tokens.shape
+        G = len(self.languages)
+        statistics = torch.empty(O, N, K, 4, dtype=torch.int32, device=self.device)
+        best = torch.empty(O, N, dtype=torch.int32, device=self.device)
+        costs = torch.empty(O, N, K, dtype=torch.float32, device=self.device)
+        for p, (index, label_maps, hyp_maps, weights) in enumerate(self._parts):
+            totals = torch.zeros(G, len(index), 4, dtype=torch.int64, device=self.device)
+            part_statistics, part_best, self._part_workspaces[p, False], part_costs = _run(
+                self.device, tokens.index_select(0, index), counts.index_select(0, index),
+                None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
+                self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual,
+                self._part_workspaces.get((p, False)), totals, weights)
+            statistics.index_copy_(0, index, part_statistics)
+            best.index_copy_(0, index, part_best)
+            costs.index_copy_(0, index, _unit_costs(part_statistics) if part_costs is None else part_costs)
+            self.totals.index_add_(1, index, totals)
+        return (statistics, best), costs
+
+    def _operations_weighted(self, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: "LabelBatch",
+                             max_actual: int) -> Tuple[Tensor, Tensor]:
+        O, N, _ = tokens.shape
+        G = len(self.languages)
+        max_ops = max(1, labels.max_expected + max_actual)
+        operations = torch.empty(O, N, max_ops, 5, dtype=torch.int32, device=self.device)
+        operation_counts = torch.empty(O, N, dtype=torch.int32, device=self.device)
+        costs = torch.empty(O, N, dtype=torch.float32, device=self.device)
+        for p, (index, label_maps, hyp_maps, weights) in enumerate(self._parts):
+            part_operations, part_counts, self._part_workspaces[p, True], part_costs = _run_operations(
+                self.device, tokens.index_select(0, index), counts.index_select(0, index),
+                None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
+                self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual,
+                self._part_workspaces.get((p, True)), weights)
+            operations[:, :, :part_operations.shape[2]].index_copy_(0, index, part_operations)
+            operation_counts.index_copy_(0, index, part_counts)
+            if part_costs is None:  # unit costs: one per record
+                part_costs = torch.where(part_counts >= 0, part_counts.float(), torch.full_like(part_counts, float("nan"), dtype=torch.float32))
+            costs.index_copy_(0, index, part_costs)
+        self._operation_costs = costs
+        return operations, operation_counts
 
     def reset(self) -> None:
         self.totals.zero_()
@@ -558,10 +670,13 @@ class Evaluator:
         if N != labels.N:
             raise ValueError(f"{N} decoded utterances for {labels.N} labels")
         max_actual = min(T * self.maps.hyp_fanout, _lib.EDIT_MAX_LENGTH)
-        statistics, best, self._workspace = _run(
+        if self.weighting is not None:
+            self._rows, self._costs = self._add_weighted(tokens, counts, hyp_counts, labels, max_actual)
+            return
+        statistics, best, self._workspace, _ = _run(
             self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
             self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._workspace, self.totals)
-        self._rows = (statistics, best)
+        self._rows, self._costs = (statistics, best), None
 
     def operations(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
                    languages: Optional[Sequence[Union[str, int]]] = None) -> Tuple[Tensor, Tensor]:
@@ -592,7 +707,9 @@ class Evaluator:
         if N != labels.N:
             raise ValueError(f"{N} decoded utterances for {labels.N} labels")
         max_actual = min(T * self.maps.hyp_fanout, _lib.EDIT_MAX_LENGTH)
-        operations, operation_counts, self._ops_workspace = _run_operations(
+        if self.weighting is not None:
+            return self._operations_weighted(tokens, counts, hyp_counts, labels, max_actual)
+        operations, operation_counts, self._ops_workspace, _ = _run_operations(
             self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
             self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._ops_workspace)
         return operations, operation_counts
@@ -640,6 +757,14 @@ class Evaluator:
             raise ValueError("nothing added yet")
         return self._rows
 
+    def costs(self) -> Tensor:
+        """Of the last ``add``, beside ``rows()``: float32 [O, N, K], every scored candidate's cost ``M[m][n]`` -- under the
+        ``weighting`` for the IPA outputs, the number of operations for outputs scored with unit costs; NaN where ``rows()``
+        holds -1 / -2.  A device tensor."""
+        if self._rows is None:
+            raise ValueError("nothing added yet")
+        return _unit_costs(self._rows[0]) if self._costs is None else self._costs
+
     def statistics(self) -> Dict[str, Dict[str, EditStatistics]]:
         """language -> output -> accumulated ``EditStatistics`` (one host synchronisation)."""
         totals = self.totals.cpu().tolist()
@@ -649,6 +774,12 @@ class Evaluator:
     def results(self, evaluation_arguments: str = "") -> MultilingualEvaluationResults:
         """Upstream's ``evaluate`` output: every language, then ``"total"`` (one host synchronisation)."""
         return MultilingualEvaluationResults.from_statistics(evaluation_arguments, self.names, self.statistics())
+
+
+def _unit_costs(statistics: Tensor) -> Tensor:
+    """Under unit costs a path costs one per operation: I + D + S of [..., 4] statistics, NaN for rows flagged -1 / -2."""
+    operations = statistics[..., :3].sum(-1).float()
+    return torch.where(statistics[..., 0] >= 0, operations, torch.full_like(operations, float("nan")))
 
 
 class _Pairs(NamedTuple):
@@ -661,6 +792,7 @@ class _Pairs(NamedTuple):
     V: int
     max_expected: int
     T: int
+    symbols: List[Hashable]  # the id space: symbol of id v
 
 
 def _pairs(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]], device: torch.device) -> _Pairs:
@@ -684,7 +816,7 @@ def _pairs(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Has
     identity = np.concatenate([np.arange(V + 1, dtype=np.int32), np.arange(V, dtype=np.int32)])  # entry e -> [e]
     descriptor = torch.tensor([0, V], dtype=torch.int32, device=device)
     return _Pairs(torch.from_numpy(tokens).to(device), torch.from_numpy(counts).to(device), torch.from_numpy(block).to(device),
-                  torch.from_numpy(identity).to(device), descriptor, V, max(map(len, label_ids)), T)
+                  torch.from_numpy(identity).to(device), descriptor, V, max(map(len, label_ids)), T, list(space))
 
 
 def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
@@ -698,8 +830,8 @@ def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual:
         return []
     p = _pairs(expected, actual, device)
     totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=device)
-    statistics, _, _ = _run(device, p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
-                            p.max_expected, p.T, None, totals)
+    statistics, _, _, _ = _run(device, p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
+                               p.max_expected, p.T, None, totals)
     return [EditStatistics(*row) for row in statistics.reshape(N, 4).cpu().tolist()]
 
 
@@ -718,8 +850,8 @@ def levensthein_operations_batch(expected: Sequence[Sequence[Hashable]], actual:
     if N == 0:
         return []
     p = _pairs(expected, actual, device)
-    operations, counts, _ = _run_operations(device, p.tokens[:, :, 0], p.counts[:, :, 0], None, p.labels, N, 1, p.maps,
-                                            p.V + 1, p.descriptor, p.descriptor, 1, p.max_expected, p.T, None)
+    operations, counts, _, _ = _run_operations(device, p.tokens[:, :, 0], p.counts[:, :, 0], None, p.labels, N, 1, p.maps,
+                                               p.V + 1, p.descriptor, p.descriptor, 1, p.max_expected, p.T, None)
     records, lengths = operations[0].cpu().numpy(), counts[0].cpu().tolist()
     return [([(Action(action), i, j) for action, i, j in records[n, :lengths[n], :3].tolist()], float(lengths[n]))
             for n in range(N)]
@@ -735,3 +867,174 @@ def levensthein_operations(expected: Sequence[Hashable], actual: Sequence[Hashab
 def levensthein_substitutions(expected: Sequence[str], actual: Sequence[str], device=None) -> List[Substitution]:
     """Upstream's ``predictions.levensthein_substitutions``: ``to_substitutions`` of ``levensthein_operations``."""
     return to_substitutions(expected, actual, levensthein_operations(expected, actual, device)[0])
+
+
+def _row(table, symbol) -> np.ndarray:
+    """``table[symbol]`` as a 1-D array; ``KeyError`` naming the symbol when the table lacks it."""
+    try:
+        row = table[symbol]
+    except (KeyError, IndexError, TypeError):
+        raise KeyError(symbol) from None
+    if isinstance(row, Tensor):
+        row = row.detach().cpu().numpy()
+    return np.asarray(row).reshape(-1)
+
+
+class PropertyWeighting:
+    """Upstream's ``allophant.phonemes.PropertyWeighting`` (edit_distance.rs:498-599) on the device: Levenshtein paths whose
+    insertions and deletions cost ``insertion_cost`` / ``deletion_cost`` (fp32) and whose substitutions cost the number of
+    positions in which ``property_table[a]`` and ``property_table[b]`` differ.  ``property_table`` is anything with
+    ``__getitem__`` from a symbol to a 1-D row (tensor, array or list), e.g. ``AttributeTable.property_table()``.
+
+    Upstream's first matrix row costs 1 per insertion whatever ``insertion_cost`` is; kept.  Beyond upstream: both costs must
+    be finite and above 0, rows have one width of at most 255 columns, a column holds at most 256 distinct values, and a
+    call compares at most 8192 distinct symbols (``ValueError``).  A symbol the table lacks raises ``KeyError``."""
+
+    def __init__(self, insertion_cost: float, deletion_cost: float, property_table):
+        self.insertion_cost = float(np.float32(insertion_cost))
+        self.deletion_cost = float(np.float32(deletion_cost))
+        for name, cost in (("insertion_cost", self.insertion_cost), ("deletion_cost", self.deletion_cost)):
+            if not (np.isfinite(cost) and cost > 0):
+                raise ValueError(f"{name} must be finite and above 0, not {cost}")
+        if not hasattr(property_table, "__getitem__"):
+            raise TypeError("property_table needs __getitem__")
+        self.property_table = property_table
+
+    def has(self, symbol) -> bool:
+        try:
+            _row(self.property_table, symbol)
+        except KeyError:
+            return False
+        return True
+
+    def codes(self, symbols: Sequence[Hashable]) -> np.ndarray:
+        """The kernels' feature codes uint8 [V, F] of ``symbols``: per column the values numbered in order of first
+        appearance (only equality matters)."""
+        rows = [_row(self.property_table, s) for s in symbols]
+        widths = {len(r) for r in rows}
+        if len(widths) > 1:
+            raise ValueError(f"property rows differ in width: {sorted(widths)}")
+        F = widths.pop() if widths else 0
+        if F > _lib.EDIT_MAX_FEATURES:
+            raise ValueError(f"property rows have {F} columns; the limit is {_lib.EDIT_MAX_FEATURES}")
+        if len(rows) > _lib.EDIT_MAX_SYMBOLS:
+            raise ValueError(f"{len(rows)} distinct symbols; a cost table covers {_lib.EDIT_MAX_SYMBOLS}")
+        codes = np.zeros((len(rows), F), dtype=np.uint8)
+        for f in range(F):
+            seen: Dict = {}
+            for v, row in enumerate(rows):
+                value = row[f].item()
+                code = seen.setdefault(value, len(seen))
+                if code > 255:
+                    raise ValueError(f"property column {f} holds more than 256 distinct values")
+                codes[v, f] = code
+        return codes
+
+    def cost_table(self, symbols: Sequence[Hashable], device: torch.device) -> Tensor:
+        """The pairwise substitution costs uint8 [V * V] of ``symbols`` (ids in that order), built on the device."""
+        codes = self.codes(symbols)
+        V, F = codes.shape
+        if V == 0:
+            return torch.empty(0, dtype=torch.uint8, device=device)
+        handle = _weighted_library()
+        size = C.c_size_t()
+        _lib.check(handle, None, handle.amx_edit_cost_table_bytes(V, C.byref(size)))
+        table = torch.empty(size.value, dtype=torch.uint8, device=device)
+        device_codes = torch.from_numpy(codes.reshape(-1)).to(device)
+        with torch.cuda.device(device):
+            code = handle.amx_edit_cost_table(device.index, _ptr(device_codes), V, F, _ptr(table),
+                                              C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+        _lib.check(handle, None, code)
+        return table
+
+    def _prepare(self, expected, actual, device) -> Tuple[torch.device, "_Pairs", "_Weights"]:
+        if len(expected) != len(actual):
+            raise ValueError("expected and actual differ in length")
+        symbols = list(dict.fromkeys(s for sequence in (*expected, *actual) for s in sequence))
+        for s in symbols:  # KeyError before anything is launched
+            _row(self.property_table, s)
+        codes = self.codes(symbols)
+        device = _device(device)
+        p = _pairs(expected, actual, device)
+        assert p.symbols == symbols
+        table = self.cost_table(symbols, device)
+        descriptors = torch.tensor([[0, len(symbols)]], dtype=torch.int64, device=device)
+        return device, p, _Weights(self.insertion_cost, self.deletion_cost, descriptors, table if len(symbols) else None)
+
+    def levensthein_statistics_batch(self, expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                     device=None) -> List[EditStatistics]:
+        if len(expected) == 0 and len(actual) == 0:
+            return []
+        device, p, weights = self._prepare(expected, actual, device)
+        N = len(expected)
+        totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=device)
+        statistics, _, _, _ = _run(device, p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor,
+                                   1, p.max_expected, p.T, None, totals, weights)
+        return [EditStatistics(*row) for row in statistics.reshape(N, 4).cpu().tolist()]
+
+    def levensthein_statistics(self, expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> EditStatistics:
+        """Upstream's ``PropertyWeighting.levensthein_statistics(string_a=expected, string_b=actual)``."""
+        return self.levensthein_statistics_batch([expected], [actual], device)[0]
+
+    def levensthein_operations_batch(self, expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                     device=None) -> List[Tuple[List[Operation], float]]:
+        if len(expected) == 0 and len(actual) == 0:
+            return []
+        device, p, weights = self._prepare(expected, actual, device)
+        N = len(expected)
+        operations, counts, _, costs = _run_operations(device, p.tokens[:, :, 0], p.counts[:, :, 0], None, p.labels, N, 1, p.maps,
+                                                       p.V + 1, p.descriptor, p.descriptor, 1, p.max_expected, p.T, None, weights)
+        records, lengths, costs = operations[0].cpu().numpy(), counts[0].cpu().tolist(), costs[0].cpu().tolist()
+        return [([(Action(action), i, j) for action, i, j in records[n, :lengths[n], :3].tolist()], costs[n]) for n in range(N)]
+
+    def levensthein_operations(self, expected: Sequence[Hashable], actual: Sequence[Hashable], device=None
+                               ) -> Tuple[List[Operation], float]:
+        """Upstream's ``PropertyWeighting.levensthein_operations``: the first best path's operations (action, i, j) in order,
+        and the fp32 cost."""
+        return self.levensthein_operations_batch([expected], [actual], device)[0]
+
+    def levensthein_matrix_batch(self, expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                 device=None) -> List[Tensor]:
+        if len(expected) == 0 and len(actual) == 0:
+            return []
+        device, p, weights = self._prepare(expected, actual, device)
+        return _matrices(device, expected, actual, p, weights)
+
+    def levensthein_matrix(self, expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> Tensor:
+        """Upstream's ``PropertyWeighting.levensthein_matrix``: the (m + 1) x (n + 1) float32 cost matrix (a device tensor)."""
+        return self.levensthein_matrix_batch([expected], [actual], device)[0]
+
+
+def _matrices(device: torch.device, expected, actual, p: _Pairs, weights: _Weights) -> List[Tensor]:
+    """One ``amx_edit_matrix`` call over the pairs of ``p``; each pair's (m + 1) x (n + 1) matrix."""
+    handle = _weighted_library()
+    N = len(expected)
+    label_offsets = p.labels[:N + 1]
+    actual_offsets = torch.zeros(N + 1, dtype=torch.int32, device=device)
+    actual_offsets[1:] = torch.cumsum(p.counts.reshape(N), 0)
+    # (one spare element: the buffer has an address even when every actual sequence is empty)
+    actual_ids = torch.cat([p.tokens[0, n, 0, :len(a)] for n, a in enumerate(actual)] + [p.tokens.new_zeros(1)]).to(torch.int32)
+    max_actual = max(map(len, actual))
+    size = C.c_size_t()
+    _lib.check(handle, None, handle.amx_edit_workspace(N, p.max_expected, max_actual, C.byref(size)))
+    workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=device)
+    matrix = torch.empty(N, p.max_expected + 1, max_actual + 1, dtype=torch.float32, device=device)
+    status = torch.empty(N, dtype=torch.int32, device=device)
+    V = int(weights.descriptors[0, 1]) if weights.data is not None else 0
+    with torch.cuda.device(device):
+        code = handle.amx_edit_matrix(
+            device.index, _ptr(label_offsets), _ptr(p.labels, 2 * N + 1), _ptr(actual_offsets), _ptr(actual_ids), N,
+            p.max_expected, max_actual, weights.insertion_cost, weights.deletion_cost, _ptr(weights.data), V, _ptr(workspace),
+            workspace.numel(), _ptr(matrix), _ptr(status), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    _lib.check(handle, None, code)
+    if int(status.min()) < 0:
+        raise RuntimeError("amx_edit_matrix flagged a row")
+    return [matrix[n, :len(e) + 1, :len(a) + 1].clone() for n, (e, a) in enumerate(zip(expected, actual))]
+
+
+def levensthein_matrix(expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> Tensor:
+    """Upstream's module-level ``phonemes.levensthein_matrix(string_a=expected, string_b=actual)``: unit costs, ``a != b``."""
+    device = _device(device)
+    p = _pairs([expected], [actual], device)
+    weights = _Weights(1.0, 1.0, torch.zeros(1, 2, dtype=torch.int64, device=device), None)
+    return _matrices(device, [expected], [actual], p, weights)[0]

@@ -48,7 +48,11 @@ RESAMPLE_MAX_PHASES = 4096  # AMX_RESAMPLE_MAX_PHASES
 RESAMPLE_MAX_WINDOW = 16384  # AMX_RESAMPLE_MAX_WINDOW
 # the edit-statistics entry points (include/allophant_amx_edit.h; added to ABI 6, detected by name)
 EDIT_EXPORTS = ["amx_edit_workspace", "amx_edit_statistics", "amx_edit_operations_workspace", "amx_edit_operations"]
+EDIT_WEIGHTED_EXPORTS = ["amx_edit_cost_table_bytes", "amx_edit_cost_table", "amx_edit_weighted_statistics",
+                         "amx_edit_weighted_operations", "amx_edit_matrix"]
 EDIT_MAX_LENGTH = 65535  # AMX_EDIT_MAX_LENGTH
+EDIT_MAX_SYMBOLS = 8192  # AMX_EDIT_MAX_SYMBOLS
+EDIT_MAX_FEATURES = 255  # AMX_EDIT_MAX_FEATURES
 EDIT_MAX_CANDIDATES = 64  # AMX_EDIT_MAX_CANDIDATES
 
 
@@ -158,6 +162,20 @@ def load() -> C.CDLL:
         lib.amx_edit_operations.argtypes = [i32, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64,
                                             i64, vp, C.c_size_t, i64, vp, vp, vp]
         lib.amx_edit_operations.restype = i32
+    if hasattr(lib, "amx_edit_weighted_statistics"):
+        f32 = C.c_float
+        lib.amx_edit_cost_table_bytes.argtypes = [i64, C.POINTER(C.c_size_t)]
+        lib.amx_edit_cost_table_bytes.restype = i32
+        lib.amx_edit_cost_table.argtypes = [i32, vp, i64, i64, vp, vp]
+        lib.amx_edit_cost_table.restype = i32
+        lib.amx_edit_weighted_statistics.argtypes = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp,
+                                                     vp, vp, i32, i64, i64, vp, C.c_size_t, f32, f32, vp, vp, vp, vp, vp, vp, vp]
+        lib.amx_edit_weighted_statistics.restype = i32
+        lib.amx_edit_weighted_operations.argtypes = [i32, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
+                                                     i32, i64, i64, vp, C.c_size_t, f32, f32, vp, vp, i64, vp, vp, vp, vp]
+        lib.amx_edit_weighted_operations.restype = i32
+        lib.amx_edit_matrix.argtypes = [i32, vp, vp, vp, vp, i64, i64, i64, f32, f32, vp, i64, vp, C.c_size_t, vp, vp, vp]
+        lib.amx_edit_matrix.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]

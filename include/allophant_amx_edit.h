@@ -99,6 +99,80 @@ int amx_edit_operations(int device, const int64_t* tokens, int64_t stride_o, int
                         void* workspace, size_t workspace_bytes, int64_t max_ops, int32_t* operations,
                         int32_t* operation_counts, void* stream);
 
+/* Upstream's `PropertyWeighting(insertion_cost, deletion_cost, property_table)` (edit_distance.rs:498-599) on decoded
+ * hypotheses: levensthein_statistics, levensthein_operations and levensthein_matrix with fp32 costs, a substitution costing the
+ * number of feature columns in which the two symbols' rows differ.  Added to ABI 6 like the calls above.  The contract is
+ * restated in DESIGN 9 and, as Python, in tests/edit_weighted_util.py.  With expected of length m and actual of length n, all
+ * arithmetic in fp32:
+ *     M[0][j] = (float)j                      (one per insertion whatever insertion_cost is: upstream's first row)
+ *     M[i][0] = M[i - 1][0] + deletion_cost   (repeated addition, rounded each time)
+ *     M[i][j] = min(min(M[i][j - 1] + insertion_cost, M[i - 1][j] + deletion_cost), M[i - 1][j - 1] + d(expected_i, actual_j))
+ * and the walk is the uniform calls' (it reads matrix values only).  The kernels perform these additions and minima, so every
+ * cost is upstream's bit for bit.  Two different symbols with equal rows cost 0: a match, no record.
+ *
+ * d comes from a COST TABLE per id space: uint8 [V, V], entry (x, y) the number of differing feature columns of symbols x and
+ * y, built on the device by amx_edit_cost_table from feature codes uint8 [V, F] (the caller canonicalises each column's values
+ * to codes: only equality matters).  Limits (AMX_EINVAL otherwise): 1 <= V <= AMX_EDIT_MAX_SYMBOLS (a table of at most 64 MiB;
+ * PHOIBLE's about 3200 phonemes and their split segments fit), 0 <= F <= AMX_EDIT_MAX_FEATURES (a count fits a byte); both
+ * costs finite and > 0 (with a cost of 0 upstream's walk can stop off the diagonal, where its `correct` count means nothing).
+ *
+ * Each output o has a cost-table descriptor int64 (first, V) in cost_tables [O, 2] (device memory): its table starts at
+ * cost_table_data + first; V == 0 says "none": d = (expected_i != actual_j), and cost_table_data may be NULL if every output
+ * says so.  A row with an expanded symbol id outside [0, V) of its output's table is flagged -2; nothing out of range is read. */
+#define AMX_EDIT_MAX_SYMBOLS 8192  /* V: symbols of one cost table */
+#define AMX_EDIT_MAX_FEATURES 255  /* F: feature columns of a row */
+
+/* Pure host function (no device, no HIP call): bytes of a cost table over V symbols (V * V). */
+int amx_edit_cost_table_bytes(int64_t V, size_t* bytes);
+
+/* Builds table uint8 [V, V] from codes uint8 [V, F] (DEVICE pointers) on `device`.  One launch, stream-ordered on `stream`. */
+int amx_edit_cost_table(int device, const uint8_t* codes, int64_t V, int64_t F, uint8_t* table, void* stream);
+
+/* amx_edit_statistics under the weighted costs: arguments, limits, workspace (amx_edit_workspace), flags (-1 / -2), candidate
+ * choice (the first candidate of strictly lowest fp32 word_error_rate of its integer counts) and totals as there.  Also
+ *   costs         float [O, N, K]: M[m][n] of every scored candidate (flagged and absent candidates: not written)
+ * Two launches, stream-ordered on `stream`: no allocation and no host synchronisation (capturable in a graph). */
+int amx_edit_weighted_statistics(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O,
+                                 int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                 const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                 const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                 const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual, void* workspace,
+                                 size_t workspace_bytes, float insertion_cost, float deletion_cost, const int64_t* cost_tables,
+                                 const uint8_t* cost_table_data, int32_t* statistics, int32_t* best, uint64_t* totals,
+                                 float* costs, void* stream);
+
+/* amx_edit_operations under the weighted costs: arguments, limits, workspace (amx_edit_operations_workspace), records and
+ * flags as there, except that an operation no longer costs 1:
+ *   operation_counts  int32 [O, N]: the number of records, S + D + I of the row's statistics (or -1 / -2)
+ *   costs             float [O, N]: M[m][n] (rows flagged or without a candidate: not written)
+ * A dear substitution may be replaced by a deletion and an insertion, so a row holds up to m + n records:
+ * max_expected + max_actual <= max_ops < 2^31.  One launch, stream-ordered on `stream`; capturable in a graph. */
+int amx_edit_weighted_operations(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int O, int N, int64_t T,
+                                 const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets,
+                                 const int32_t* label_ids, const int32_t* groups, int G, const int32_t* map_offsets,
+                                 const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
+                                 int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes,
+                                 float insertion_cost, float deletion_cost, const int64_t* cost_tables,
+                                 const uint8_t* cost_table_data, int64_t max_ops, int32_t* operations, int32_t* operation_counts,
+                                 float* costs, void* stream);
+
+/* levensthein_matrix for pairs of id sequences handed over directly (no maps).  All pointers are DEVICE pointers:
+ *   expected_offsets int32 [rows + 1], expected_ids int32: row r's expected is expected_ids[expected_offsets[r] ..
+ *                    expected_offsets[r + 1]); actual_offsets / actual_ids the same for actual
+ *   cost_table       uint8 [V, V] of the pairs' id space, or V == 0 (then it may be NULL): d = (expected_i != actual_j); unit
+ *                    costs with V == 0 give upstream's module-level levensthein_matrix
+ *   workspace        workspace_bytes >= amx_edit_workspace(rows, max_expected, max_actual)
+ * and writes
+ *   matrix  float [rows, max_expected + 1, max_actual + 1]: cells [0, m] x [0, n] of row r; nothing outside them
+ *   status  int32 [rows]: 0, or -2 for a row longer than max_expected / max_actual, with bad offsets or with an id outside
+ *           [0, V) (its matrix is not written; nothing out of range is read)
+ * Limits: 0 <= rows < 2^31, lengths as above, 0 <= V <= AMX_EDIT_MAX_SYMBOLS, costs finite and > 0; the caller's matrix buffer
+ * bounds the size.  One launch, stream-ordered on `stream`; capturable in a graph. */
+int amx_edit_matrix(int device, const int32_t* expected_offsets, const int32_t* expected_ids, const int32_t* actual_offsets,
+                    const int32_t* actual_ids, int64_t rows, int64_t max_expected, int64_t max_actual, float insertion_cost,
+                    float deletion_cost, const uint8_t* cost_table, int64_t V, void* workspace, size_t workspace_bytes,
+                    float* matrix, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
