@@ -10,7 +10,7 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "BeamDecoded", "feature_decoders", "EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator",
            "levensthein_statistics", "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations",
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
-           "levensthein_matrix"]
+           "levensthein_matrix", "Alignment", "Aligned", "ctc_forced_align", "label_targets"]
 __version__ = "0.1.0"
 
 
@@ -27,4 +27,8 @@ def __getattr__(name):
         from . import evaluation
 
         return getattr(evaluation, name)
+    if name in ("Alignment", "Aligned", "ctc_forced_align", "label_targets"):
+        from . import alignment
+
+        return getattr(alignment, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,213 @@
+"""CTC forced alignment on the device (``include/allophant_amx_align.h``): where in the frames each symbol of a known label
+sequence lies.
+
+  * ``ctc_forced_align``  one ``[N, T, C]`` emission tensor, like ``beam_ctc_decode``
+  * ``Estimator.align_device`` / ``Estimator.align``  every output of a ``Predictions`` (``Aligned`` stays in HBM)
+  * ``label_targets``  expected strings per output (``EvaluationMaps.expand_label``) -> class indices, the inverse of
+    ``phonetic.hypothesis_symbols``
+
+The path is the Viterbi path of the CTC trellis with ties going to the smaller move; there is no CPU path."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
+
+import torch
+from torch import Tensor
+
+from . import lib as _lib
+from .phonetic import BLANK_OFFSET, IPA_LAYERS
+
+ALIGN_MAX_TARGET = _lib.ALIGN_MAX_TARGET
+
+
+def frame_stride(spec: Dict[str, Any]) -> int:
+    """Samples per output frame: the product of the spec's convolution strides."""
+    return math.prod(int(s) for s in spec["conv_stride"])
+
+
+class Alignment(NamedTuple):
+    """One aligned row on the host: ``tokens`` int32 ``[T]`` the class of every frame (blank between symbols), ``scores``
+    fp32 ``[T]`` its log-probability, ``spans`` int32 ``[L, 2]`` (first frame, last frame + 1) per target, ``span_scores``
+    fp32 ``[L]`` the sum of the span's frame scores, ``total`` the path's log-probability."""
+    tokens: Tensor
+    scores: Tensor
+    spans: Tensor
+    span_scores: Tensor
+    total: float
+
+    def seconds(self, spec: Dict[str, Any], sample_rate: int = 16000) -> Tensor:
+        """``spans`` in seconds (float64 ``[L, 2]``): frame index x the spec's frame stride / sample rate."""
+        return self.spans.to(torch.float64) * (frame_stride(spec) / float(sample_rate))
+
+
+def _rows(paths: Tensor, frame_scores: Tensor, spans: Tensor, span_scores: Tensor, totals: Tensor, status: Tensor,
+          lengths: Sequence[int], target_counts: Sequence[int], label: str = "row") -> List[Optional[Alignment]]:
+    """Host form of ``R`` aligned rows (``lengths`` / ``target_counts`` per row): ``None`` where no alignment exists,
+    ``ValueError`` for a row the kernel flagged as malformed."""
+    status_h = status.cpu().tolist()
+    bad = [r for r, s in enumerate(status_h) if s == -2]
+    if bad:
+        raise ValueError(f"{label} {bad[0]}: malformed alignment row (a target equal to the blank or outside the classes, a "
+                         "frame length outside the tensor, more targets than max_target, or offsets that do not ascend)")
+    paths_h, scores_h, spans_h, span_scores_h, totals_h = (t.cpu() for t in (paths, frame_scores, spans, span_scores, totals))
+    out: List[Optional[Alignment]] = []
+    for r, s in enumerate(status_h):
+        if s != 0:
+            out.append(None)
+            continue
+        k, L = int(lengths[r]), int(target_counts[r])
+        out.append(Alignment(paths_h[r, :k].clone(), scores_h[r, :k].clone(), spans_h[r, :L].clone(),
+                             span_scores_h[r, :L].clone(), float(totals_h[r])))
+    return out
+
+
+class Aligned(NamedTuple):
+    """Forced alignments of a batch, one row per output: ``paths`` int32 / ``frame_scores`` fp32 ``[O, N, T]``, ``spans`` int32
+    ``[O, N, max_target, 2]``, ``span_scores`` fp32 ``[O, N, max_target]``, ``totals`` fp32 / ``status`` int32 ``[O, N]`` on the
+    device (layout and status codes as in ``include/allophant_amx_align.h``); ``lengths`` / ``target_counts`` on the host.
+    ``names`` are the outputs, ``present`` those that were given targets."""
+    names: List[str]
+    present: List[str]
+    paths: Tensor
+    frame_scores: Tensor
+    spans: Tensor
+    span_scores: Tensor
+    totals: Tensor
+    status: Tensor
+    lengths: List[int]
+    target_counts: List[List[int]]
+
+    def alignments(self) -> Dict[str, List[Optional[Alignment]]]:
+        """Fetched to the host: per present output and utterance an ``Alignment``, or ``None`` where none exists."""
+        result = {}
+        for o, name in enumerate(self.names):
+            if name in self.present:
+                result[name] = _rows(self.paths[o], self.frame_scores[o], self.spans[o], self.span_scores[o], self.totals[o],
+                                     self.status[o], self.lengths, self.target_counts[o], label=f"output {name!r}, utterance")
+        return result
+
+
+def pack_targets(rows: Sequence[Sequence[int]]) -> Tuple[Tensor, Tensor, List[int]]:
+    """Target rows as the C ABI takes them: int32 offsets ``[R + 1]``, int32 ids, and the rows' lengths (host tensors)."""
+    counts = [len(row) for row in rows]
+    if counts and max(counts) > ALIGN_MAX_TARGET:
+        raise ValueError(f"at most {ALIGN_MAX_TARGET} targets per row on the device, got {max(counts)}")
+    offsets = torch.zeros(len(rows) + 1, dtype=torch.int32)
+    if rows:
+        offsets[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0).to(torch.int32)
+    ids = torch.tensor([int(v) for row in rows for v in row], dtype=torch.int32)
+    return offsets, ids, counts
+
+
+class _Buffers(NamedTuple):
+    workspace: Tensor
+    size: int
+    paths: Tensor
+    frame_scores: Tensor
+    spans: Tensor
+    span_scores: Tensor
+    totals: Tensor
+    status: Tensor
+
+    def pointers(self):
+        return (C.c_void_p(self.workspace.data_ptr()), self.size, C.c_void_p(self.paths.data_ptr()),
+                C.c_void_p(self.frame_scores.data_ptr()), C.c_void_p(self.spans.data_ptr()),
+                C.c_void_p(self.span_scores.data_ptr()), C.c_void_p(self.totals.data_ptr()), C.c_void_p(self.status.data_ptr()))
+
+
+def allocate(lib, rows: int, T: int, max_target: int, device) -> _Buffers:
+    """The workspace and outputs of ``rows`` rows of ``T`` frames (at least one element each, so every pointer is valid)."""
+    size = C.c_size_t()
+    _lib.check(lib, None, lib.amx_ctc_align_workspace(rows, T, max_target, C.byref(size)))
+    empty = lambda *shape, dtype: torch.empty(max(1, math.prod(shape)), dtype=dtype, device=device)[:math.prod(shape)].view(*shape)  # noqa: E731
+    return _Buffers(torch.empty(max(1, size.value), dtype=torch.uint8, device=device), size.value,
+                    empty(rows, T, dtype=torch.int32), empty(rows, T, dtype=torch.float32),
+                    empty(rows, max_target, 2, dtype=torch.int32), empty(rows, max_target, dtype=torch.float32),
+                    empty(rows, dtype=torch.float32), empty(rows, dtype=torch.int32))
+
+
+def ctc_forced_align(log_emissions: Tensor, lengths: Optional[Tensor],
+                     targets: Union[Sequence[Sequence[int]], Tuple[Tensor, Tensor]], blank_index: int = 0
+                     ) -> List[Optional[Alignment]]:
+    """The best CTC path of each row's ``targets`` through ``log_emissions`` (an fp32 ``[N, T, C]`` cuda tensor of any strides
+    with a unit class stride, read in place) via ``amx_ctc_align_emissions``.  ``targets``: one int sequence per row, or a
+    padded ``[N, max_len]`` tensor with its lengths ``(padded, target_lengths)``.  Per row an ``Alignment``, or ``None`` where
+    no alignment exists (too few frames, or ``-inf`` emissions on every path); ``ValueError`` names a malformed row."""
+    if log_emissions.dim() != 3:
+        raise ValueError("log_emissions must be [N, T, C]")
+    if log_emissions.device.type != "cuda":
+        raise RuntimeError("allophant_amd aligns on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    lib = _lib.load()
+    device = log_emissions.device
+    if log_emissions.dtype != torch.float32:
+        log_emissions = log_emissions.float()
+    if log_emissions.stride(2) != 1:
+        log_emissions = log_emissions.contiguous()
+    N, T, Cn = log_emissions.shape
+    if isinstance(targets, tuple) and len(targets) == 2 and isinstance(targets[0], Tensor):
+        padded, target_lengths = targets[0].cpu().tolist(), [int(v) for v in targets[1].cpu().tolist()]
+        targets = [row[:k] for row, k in zip(padded, target_lengths)]
+    if len(targets) != N:
+        raise ValueError(f"{len(targets)} target rows for {N} emission rows")
+    if Cn < 2:
+        raise ValueError("alignment needs at least 2 classes")
+    if not 0 <= blank_index < Cn:
+        raise ValueError("blank_index out of range")
+    if N == 0:
+        return []
+    offsets, ids, counts = pack_targets(targets)
+    max_target = max(counts)
+    with torch.cuda.device(device):
+        if lengths is None:
+            frame_lengths = torch.full((N,), T, dtype=torch.int32, device=device)
+        else:
+            frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(device)  # (never an empty tensor)
+        b = allocate(lib, N, T, max_target, device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        code = lib.amx_ctc_align_emissions(
+            index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
+            C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, C.c_void_p(meta.data_ptr()),
+            C.c_void_p(meta.data_ptr() + 4 * (N + 1)), max_target, *b.pointers(), C.c_void_p(stream))
+        _lib.check(lib, None, code)
+        host_lengths = frame_lengths.cpu().tolist()
+        return _rows(b.paths, b.frame_scores, b.spans, b.span_scores, b.totals, b.status, host_lengths, counts)
+
+
+def label_targets(maps_or_evaluator, labels: Sequence[Sequence[str]], languages: Optional[Sequence[str]] = None
+                  ) -> Dict[str, List[List[int]]]:
+    """Per output of an ``Evaluator`` (or its ``EvaluationMaps``) and utterance, the class indices of the expected symbols:
+    the label expanded exactly as ``EvaluationMaps.expand_label`` does (contours, split segments, replacements), then
+    ``inventory.index(p) + BLANK_OFFSET`` on the ``phone`` / ``phoneme`` outputs and
+    ``feature_categories(name).index(v) + BLANK_OFFSET`` on attribute outputs -- the inverse of
+    ``phonetic.hypothesis_symbols``.  ``languages`` (one per utterance, optional) are checked against the maps' languages.
+    A symbol with no class (e.g. a phoneme outside the inventory) raises ``ValueError`` naming the output and the symbol."""
+    maps = getattr(maps_or_evaluator, "maps", maps_or_evaluator)
+    if languages is not None:
+        if len(languages) != len(labels):
+            raise ValueError(f"{len(languages)} languages for {len(labels)} labels")
+        unknown = sorted(set(languages) - set(maps.languages))
+        if unknown:
+            raise ValueError(f"languages {unknown} are not among {maps.languages}")
+    result: Dict[str, List[List[int]]] = {}
+    for o, name in enumerate(maps.names):
+        categories = list(maps.inventory) if name in IPA_LAYERS else maps.table.feature_categories(name)
+        classes = {}
+        for k, symbol in enumerate(categories):
+            classes.setdefault(symbol, k + BLANK_OFFSET)
+        rows = []
+        for n, label in enumerate(labels):
+            unknown = [s for s in label if s not in maps.label_ids]
+            if unknown:
+                raise ValueError(f"output {name!r}, utterance {n}: label symbol {unknown[0]!r} is not in the attribute table")
+            row = []
+            for symbol in maps.expand_label(o, label):
+                if symbol not in classes:
+                    raise ValueError(f"output {name!r}, utterance {n}: symbol {symbol!r} has no class under this inventory")
+                row.append(classes[symbol])
+            rows.append(row)
+        result[name] = rows
+    return result

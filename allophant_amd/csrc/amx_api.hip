@@ -3,6 +3,7 @@
 #include "../../include/allophant_amx.h"
 #include "../../include/allophant_amx_allophones.h"
 #include "../../include/allophant_amx_beam.h"
+#include "../../include/allophant_amx_align.h"
 #include "../../include/allophant_amx_resample.h"
 #include "../../include/allophant_amx_edit.h"
 #include "amx_common.h"
@@ -2303,6 +2304,95 @@ extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_
                               (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores,
                               hyp_counts, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "beam-search kernel launch failed");
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// CTC forced alignment
+// =================================================================================================================
+namespace {
+int align_check(amx_handle h, int64_t rows, int64_t T, int64_t max_target) {
+    if (rows < 0 || T < 0) return fail(h, AMX_EINVAL, "negative alignment geometry");
+    if (max_target < 0 || max_target > AMX_ALIGN_MAX_TARGET)
+        return fail(h, AMX_EINVAL, "max_target must be 0 to " + std::to_string(AMX_ALIGN_MAX_TARGET) + ", got " + std::to_string(max_target));
+    int64_t cells = 0;
+    if (__builtin_mul_overflow(rows, T, &cells) || cells > INT32_MAX) return fail(h, AMX_EINVAL, "rows * T must be below 2^31");
+    return AMX_OK;
+}
+int align_check_classes(amx_handle h, int C, int blank) {
+    if (C < 2) return fail(h, AMX_EINVAL, "alignment needs at least 2 classes, got " + std::to_string(C));
+    if (blank < 0 || blank >= C) return fail(h, AMX_EINVAL, "blank_index out of range");
+    return AMX_OK;
+}
+int align_check_workspace(amx_handle h, int64_t rows, int64_t T, int64_t max_target, const void* workspace, size_t workspace_bytes) {
+    size_t need = 0;
+    if (!ctc_align_workspace_bytes(rows, T, max_target, &need)) return fail(h, AMX_EINVAL, "alignment workspace size not representable");
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(h, AMX_EINVAL, "alignment workspace too small: " + std::to_string(need) + " bytes needed");
+    return AMX_OK;
+}
+}  // namespace
+
+extern "C" int amx_ctc_align_workspace(int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = align_check(nullptr, rows, T, max_target)) return rc;
+    if (!ctc_align_workspace_bytes(rows, T, max_target, bytes)) return fail(nullptr, AMX_EINVAL, "alignment workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_align_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                       const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index,
+                                       const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
+                                       size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores,
+                                       float* totals, int32_t* status, void* stream) {
+    if (int rc = align_check(nullptr, N, T, max_target)) return rc;
+    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
+    if (N == 0) return AMX_OK;
+    if (!frame_lengths || !target_offsets || !totals || !status || (T && (!emissions || !paths || !frame_scores)) ||
+        (max_target && (!target_ids || !spans || !span_scores)))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (int rc = align_check_workspace(nullptr, N, T, max_target, workspace, workspace_bytes)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    AlignArgs a{};
+    a.emissions = emissions, a.stride_n = stride_n, a.stride_t = stride_t, a.descs = nullptr;
+    a.frame_lengths = frame_lengths, a.target_offsets = target_offsets, a.target_ids = target_ids;
+    a.rows = N, a.N = N, a.T = (int)T, a.C = C, a.blank = blank_index, a.max_target = (int)max_target;
+    a.workspace = (uint4*)workspace;
+    a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
+    launch_ctc_align(a, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "alignment kernel launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_align(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
+                             const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
+                             size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores,
+                             float* totals, int32_t* status, void* stream) {
+    if (!h) return AMX_EINVAL;
+    if (!out || !frame_lengths || !target_offsets || !paths || !frame_scores || !totals || !status ||
+        (max_target > 0 && (!target_ids || !spans || !span_scores)))
+        return fail(h, AMX_EINVAL, "null buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = compute_layout(h, N, L);
+    if (rc) return rc;
+    const int T = (int)h->layout_T;
+    const int64_t rows = (int64_t)h->out_all.size() * N;
+    if ((rc = align_check(h, rows, T, max_target))) return rc;
+    if (rows == 0) return AMX_OK;
+    for (const OutDesc& d : h->out_all)
+        if ((rc = align_check_classes(h, d.C, 0))) return rc;
+    if ((rc = align_check_workspace(h, rows, T, max_target, workspace, workspace_bytes))) return rc;
+    const int* d_fl;
+    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
+    AlignArgs a{};
+    a.emissions = out, a.descs = cur_inv(h).out_all_dev;
+    a.frame_lengths = d_fl, a.target_offsets = target_offsets, a.target_ids = target_ids;
+    a.rows = rows, a.N = N, a.T = T, a.max_target = (int)max_target;
+    a.workspace = (uint4*)workspace;
+    a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
+    launch_ctc_align(a, s);
+    HIPCHK(h, hipGetLastError());
     return AMX_OK;
 }
 

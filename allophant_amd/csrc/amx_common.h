@@ -496,6 +496,32 @@ void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t
                                int blank, int beam, int n_best, int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps,
                                int* counts, double* scores, int* hyp_counts, hipStream_t s);
 
+// CTC forced alignment (amx_ctc_align.hip), one workgroup per row: contract in include/allophant_amx_align.h.  With `descs`
+// the rows are o * N + n over every output block of `emissions` (the output buffer; blank 0), else the N utterances of one
+// [N, T, C] tensor read with element strides (stride_n, stride_t, 1).  The launcher fills the workspace geometry: per row
+// `strips` strips of 64 states, each holding t_pad 16-byte move words.  Limits (checked by the callers): 2 <= C,
+// 0 <= max_target <= 4095, rows * T < 2^31.
+constexpr int ALIGN_MAX_WAVES = 16;
+struct AlignArgs {
+    const float* emissions;
+    int64_t stride_n, stride_t;
+    const OutDesc* descs;
+    const int32_t *frame_lengths, *target_offsets, *target_ids;
+    int64_t rows;
+    int N, T, C, blank, max_target;
+    int strips;
+    int64_t t_pad;
+    uint4* workspace;
+    int32_t* paths;
+    float* frame_scores;
+    int32_t* spans;
+    float *span_scores, *totals;
+    int32_t* status;
+};
+// false when the size is not representable in size_t
+bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
+void launch_ctc_align(AlignArgs a, hipStream_t s);
+
 // allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
 // strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]
 // of ent_p / ent_w and the accumulator start col_init[l * Q1 + q]; language_ids int32 [N] in [0, n_lang)

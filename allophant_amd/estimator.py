@@ -25,8 +25,10 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
+from . import alignment as _alignment
 from . import lib as _lib
 from . import spec as _spec
+from .alignment import Aligned, Alignment, ctc_forced_align, label_targets  # noqa: F401  (the façade's alignment names)
 
 
 @dataclass
@@ -635,6 +637,52 @@ class Estimator:
                     exp_emissions: bool = True) -> Dict[str, List[List[CTCHypothesis]]]:
         """``beam_decode_device`` fetched to the host: per output and utterance up to ``n_best`` hypotheses, best first."""
         return self.beam_decode_device(predictions, beam_width, n_best, exp_emissions).hypotheses()
+
+    def align_device(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]]) -> "_alignment.Aligned":
+        """On-device CTC forced alignment (``amx_ctc_align``) of every output of ``predictions`` against ``targets``: output
+        name -> one class-index sequence per utterance (``alignment.label_targets`` builds them from labels).  An output
+        without an entry is aligned against nothing and left out of ``Aligned.present``.  The result stays in HBM."""
+        if predictions._flat is None or predictions._geometry is None:
+            raise ValueError("predictions were not produced by this estimator")
+        N, L = predictions._geometry
+        if predictions._inventory is not None:
+            self._set_inventory(predictions._inventory)  # align under the inventory of THESE predictions (greedy_decode_device)
+        names = list(predictions.outputs.keys())
+        unknown = [name for name in targets if name not in predictions.outputs]
+        if unknown:
+            raise ValueError(f"targets name the outputs {unknown}, the predictions hold {names}")
+        rows: List[Sequence[int]] = []
+        for name in names:
+            per_utterance = targets.get(name)
+            if per_utterance is not None and len(per_utterance) != N:
+                raise ValueError(f"output {name!r}: {len(per_utterance)} target rows for {N} utterances")
+            rows += [[] for _ in range(N)] if per_utterance is None else list(per_utterance)
+        if N == 0:
+            raise ValueError("predictions hold no utterances: nothing to align")
+        offsets, ids, counts = _alignment.pack_targets(rows)
+        max_target = max(counts)
+        T = next(iter(predictions.outputs.values())).shape[0]
+        O = len(names)
+        with torch.cuda.device(self._device):
+            meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(self._device)
+            b = _alignment.allocate(self._lib, O * N, T, max_target, self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
+            code = self._lib.amx_ctc_align(
+                self._handle, C.c_void_p(predictions._flat.data_ptr()), C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)),
+                N, L, C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 4 * (O * N + 1)), max_target, *b.pointers(),
+                C.c_void_p(stream))
+            _lib.check(self._lib, self._handle, code)
+        return _alignment.Aligned(names, [name for name in names if name in targets], b.paths.view(O, N, T),
+                                  b.frame_scores.view(O, N, T), b.spans.view(O, N, max_target, 2),
+                                  b.span_scores.view(O, N, max_target), b.totals.view(O, N), b.status.view(O, N),
+                                  frame_lengths.tolist(), [counts[o * N:(o + 1) * N] for o in range(O)])
+
+    def align(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]]
+              ) -> Dict[str, List[Optional["_alignment.Alignment"]]]:
+        """``align_device`` fetched to the host: per output with targets and utterance an ``Alignment`` (``None`` where no
+        alignment exists)."""
+        return self.align_device(predictions, targets).alignments()
 
     def debug_fetch(self, what: str, index: int = 0) -> Tensor:
         """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors."""

@@ -434,6 +434,7 @@ class EvaluationMaps:
         if not self.names or not self.languages:
             raise ValueError("evaluation needs at least one output and one language")
         inventory = list(inventory.inventory if isinstance(inventory, InventoryView) else inventory)
+        self.table, self.inventory = table, inventory  # (what alignment.label_targets turns expected strings into classes with)
         replacements = dict(replacements or {})
         if source_maps is not None:
             missing = [lang for lang in self.languages if lang not in source_maps]

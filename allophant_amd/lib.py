@@ -54,6 +54,9 @@ EDIT_MAX_LENGTH = 65535  # AMX_EDIT_MAX_LENGTH
 EDIT_MAX_SYMBOLS = 8192  # AMX_EDIT_MAX_SYMBOLS
 EDIT_MAX_FEATURES = 255  # AMX_EDIT_MAX_FEATURES
 EDIT_MAX_CANDIDATES = 64  # AMX_EDIT_MAX_CANDIDATES
+# the CTC forced-alignment entry points (include/allophant_amx_align.h; added to ABI 6, detected by name)
+ALIGN_EXPORTS = ["amx_ctc_align_workspace", "amx_ctc_align_emissions", "amx_ctc_align"]
+ALIGN_MAX_TARGET = 4095  # AMX_ALIGN_MAX_TARGET
 
 
 def dep_output_layer(i: int) -> int:
@@ -176,6 +179,14 @@ def load() -> C.CDLL:
         lib.amx_edit_weighted_operations.restype = i32
         lib.amx_edit_matrix.argtypes = [i32, vp, vp, vp, vp, i64, i64, i64, f32, f32, vp, i64, vp, C.c_size_t, vp, vp, vp]
         lib.amx_edit_matrix.restype = i32
+    if hasattr(lib, "amx_ctc_align"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_ctc_align_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_ctc_align_workspace.restype = i32
+        lib.amx_ctc_align_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp,
+                                                vp, vp, vp, vp]
+        lib.amx_ctc_align_emissions.restype = i32
+        lib.amx_ctc_align.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+        lib.amx_ctc_align.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
