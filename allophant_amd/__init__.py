@@ -10,7 +10,8 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "BeamDecoded", "feature_decoders", "EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator",
            "levensthein_statistics", "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations",
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
-           "levensthein_matrix", "Alignment", "Aligned", "ctc_forced_align", "label_targets"]
+           "levensthein_matrix", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "Score", "Scored",
+           "Rescored", "ctc_score"]
 __version__ = "0.1.0"
 
 
@@ -31,4 +32,8 @@ def __getattr__(name):
         from . import alignment
 
         return getattr(alignment, name)
+    if name in ("Score", "Scored", "Rescored", "ctc_score"):
+        from . import scoring
+
+        return getattr(scoring, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -4,6 +4,7 @@
 #include "../../include/allophant_amx_allophones.h"
 #include "../../include/allophant_amx_beam.h"
 #include "../../include/allophant_amx_align.h"
+#include "../../include/allophant_amx_score.h"
 #include "../../include/allophant_amx_resample.h"
 #include "../../include/allophant_amx_edit.h"
 #include "amx_common.h"
@@ -2392,6 +2393,93 @@ extern "C" int amx_ctc_align(amx_handle h, const float* out, const int64_t* fram
     a.workspace = (uint4*)workspace;
     a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
     launch_ctc_align(a, s);
+    HIPCHK(h, hipGetLastError());
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// CTC forward-backward scoring (the alignment's geometry checks, on rows that count the candidates)
+// =================================================================================================================
+namespace {
+int score_rows(amx_handle h, int64_t rows, int candidates, int64_t* out) {
+    if (candidates < 1) return fail(h, AMX_EINVAL, "candidates must be at least 1, got " + std::to_string(candidates));
+    if (rows < 0) return fail(h, AMX_EINVAL, "negative scoring geometry");
+    if (__builtin_mul_overflow(rows, (int64_t)candidates, out)) return fail(h, AMX_EINVAL, "rows * T must be below 2^31");
+    return AMX_OK;
+}
+int score_check_workspace(amx_handle h, int64_t rows, int64_t T, int64_t max_target, const void* workspace, size_t workspace_bytes) {
+    size_t need = 0;
+    if (!ctc_score_workspace_bytes(rows, T, max_target, &need)) return fail(h, AMX_EINVAL, "scoring workspace size not representable");
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(h, AMX_EINVAL, "scoring workspace too small: " + std::to_string(need) + " bytes needed");
+    return AMX_OK;
+}
+}  // namespace
+
+extern "C" int amx_ctc_score_workspace(int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = align_check(nullptr, rows, T, max_target)) return rc;
+    if (!ctc_score_workspace_bytes(rows, T, max_target, bytes)) return fail(nullptr, AMX_EINVAL, "scoring workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_score_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                       const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index, int candidates,
+                                       const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
+                                       size_t workspace_bytes, float* log_likelihood, float* occupancy, float* position_sums,
+                                       float* score_sums, float* posteriors, int32_t* status, void* stream) {
+    int64_t rows = 0;
+    if (int rc = score_rows(nullptr, N, candidates, &rows)) return rc;
+    if (int rc = align_check(nullptr, rows, T, max_target)) return rc;
+    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
+    if (N == 0) return AMX_OK;
+    if (!frame_lengths || !target_offsets || !log_likelihood || !status || (T && !emissions) ||
+        (max_target && (!target_ids || !occupancy || !position_sums || !score_sums)))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (int rc = score_check_workspace(nullptr, rows, T, max_target, workspace, workspace_bytes)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    ScoreArgs a{};
+    a.emissions = emissions, a.stride_n = stride_n, a.stride_t = stride_t, a.descs = nullptr;
+    a.frame_lengths = frame_lengths, a.target_offsets = target_offsets, a.target_ids = target_ids;
+    a.rows = rows, a.N = N, a.T = (int)T, a.C = C, a.blank = blank_index, a.max_target = (int)max_target, a.candidates = candidates;
+    a.workspace = (float*)workspace;
+    a.log_likelihood = log_likelihood, a.occupancy = occupancy, a.position_sums = position_sums, a.score_sums = score_sums;
+    a.posteriors = posteriors, a.status = status;
+    launch_ctc_score(a, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "scoring kernel launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_score(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L, int candidates,
+                             const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
+                             size_t workspace_bytes, float* log_likelihood, float* occupancy, float* position_sums,
+                             float* score_sums, float* posteriors, int32_t* status, void* stream) {
+    if (!h) return AMX_EINVAL;
+    if (!out || !frame_lengths || !target_offsets || !log_likelihood || !status ||
+        (max_target > 0 && (!target_ids || !occupancy || !position_sums || !score_sums)))
+        return fail(h, AMX_EINVAL, "null buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = compute_layout(h, N, L);
+    if (rc) return rc;
+    const int T = (int)h->layout_T;
+    int64_t rows = 0;
+    if ((rc = score_rows(h, (int64_t)h->out_all.size() * N, candidates, &rows))) return rc;
+    if ((rc = align_check(h, rows, T, max_target))) return rc;
+    if (rows == 0) return AMX_OK;
+    for (const OutDesc& d : h->out_all)
+        if ((rc = align_check_classes(h, d.C, 0))) return rc;
+    if ((rc = score_check_workspace(h, rows, T, max_target, workspace, workspace_bytes))) return rc;
+    const int* d_fl;
+    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
+    ScoreArgs a{};
+    a.emissions = out, a.descs = cur_inv(h).out_all_dev;
+    a.frame_lengths = d_fl, a.target_offsets = target_offsets, a.target_ids = target_ids;
+    a.rows = rows, a.N = N, a.T = T, a.max_target = (int)max_target, a.candidates = candidates;
+    a.workspace = (float*)workspace;
+    a.log_likelihood = log_likelihood, a.occupancy = occupancy, a.position_sums = position_sums, a.score_sums = score_sums;
+    a.posteriors = posteriors, a.status = status;
+    launch_ctc_score(a, s);
     HIPCHK(h, hipGetLastError());
     return AMX_OK;
 }

@@ -522,6 +522,26 @@ struct AlignArgs {
 bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
 void launch_ctc_align(AlignArgs a, hipStream_t s);
 
+// CTC forward-backward scoring (amx_ctc_score.hip), one workgroup per row: contract in include/allophant_amx_score.h.  Rows
+// are (o * N + n) * G + g with `descs` (every output block of `emissions`, blank 0), else n * G + g over one [N, T, C] tensor
+// read with element strides (stride_n, stride_t, 1); G = candidates.  The launcher fills `strips`: the workspace holds per
+// row and frame strips * 64 forward values.  Limits as for the alignment, on rows = (O *) N * G.
+struct ScoreArgs {
+    const float* emissions;
+    int64_t stride_n, stride_t;
+    const OutDesc* descs;
+    const int32_t *frame_lengths, *target_offsets, *target_ids;
+    int64_t rows;
+    int N, T, C, blank, max_target, candidates;
+    int strips;
+    float* workspace;
+    float *log_likelihood, *occupancy, *position_sums, *score_sums, *posteriors;  // posteriors may be null
+    int32_t* status;
+};
+// false when the size is not representable in size_t
+bool ctc_score_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
+void launch_ctc_score(ScoreArgs a, hipStream_t s);
+
 // allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
 // strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]
 // of ent_p / ent_w and the accumulator start col_init[l * Q1 + q]; language_ids int32 [N] in [0, n_lang)

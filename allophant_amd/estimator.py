@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import math
 from dataclasses import dataclass
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
@@ -27,8 +28,10 @@ from torch import Tensor
 
 from . import alignment as _alignment
 from . import lib as _lib
+from . import scoring as _scoring
 from . import spec as _spec
 from .alignment import Aligned, Alignment, ctc_forced_align, label_targets  # noqa: F401  (the façade's alignment names)
+from .scoring import Rescored, Score, Scored, ctc_score  # noqa: F401  (the façade's scoring names)
 
 
 @dataclass
@@ -683,6 +686,89 @@ class Estimator:
         """``align_device`` fetched to the host: per output with targets and utterance an ``Alignment`` (``None`` where no
         alignment exists)."""
         return self.align_device(predictions, targets).alignments()
+
+    def _score_call(self, predictions: Predictions, candidates: int, meta: Tensor, max_target: int, posteriors: bool):
+        """``amx_ctc_score`` over every output of ``predictions``: ``meta`` holds the device int32 offsets
+        ``[O * N * candidates + 1]`` followed by the ids.  Returns the buffers, the host frame lengths and (O, N, T)."""
+        N, L = predictions._geometry
+        T = next(iter(predictions.outputs.values())).shape[0]
+        O = len(predictions.outputs)
+        rows = O * N * candidates
+        b = _scoring.allocate(self._lib, rows, T, max_target, self._device, posteriors)
+        stream = torch.cuda.current_stream(self._device).cuda_stream
+        frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
+        code = self._lib.amx_ctc_score(
+            self._handle, C.c_void_p(predictions._flat.data_ptr()), C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)),
+            N, L, candidates, C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 4 * (rows + 1)), max_target,
+            *b.pointers(), C.c_void_p(stream))
+        _lib.check(self._lib, self._handle, code)
+        return b, frame_lengths.tolist(), (O, N, T)
+
+    def score_device(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]],
+                     posteriors: bool = False) -> "_scoring.Scored":
+        """On-device CTC forward-backward scoring (``amx_ctc_score``) of every output of ``predictions`` against ``targets``,
+        given as ``align_device`` takes them: the log-likelihood of each target sequence and, per target, its posterior
+        occupancy, position and score sums (with ``posteriors`` also the state posteriors of every frame).  An output without
+        an entry is scored against nothing and left out of ``Scored.present``.  The result stays in HBM, leading shape
+        ``[O, N, 1]``."""
+        if predictions._flat is None or predictions._geometry is None:
+            raise ValueError("predictions were not produced by this estimator")
+        N, _ = predictions._geometry
+        if predictions._inventory is not None:
+            self._set_inventory(predictions._inventory)  # score under the inventory of THESE predictions (greedy_decode_device)
+        names = list(predictions.outputs.keys())
+        unknown = [name for name in targets if name not in predictions.outputs]
+        if unknown:
+            raise ValueError(f"targets name the outputs {unknown}, the predictions hold {names}")
+        rows: List[Sequence[int]] = []
+        for name in names:
+            per_utterance = targets.get(name)
+            if per_utterance is not None and len(per_utterance) != N:
+                raise ValueError(f"output {name!r}: {len(per_utterance)} target rows for {N} utterances")
+            rows += [[] for _ in range(N)] if per_utterance is None else list(per_utterance)
+        if N == 0:
+            raise ValueError("predictions hold no utterances: nothing to score")
+        offsets, ids, counts = _scoring.pack_targets(rows)
+        max_target = max(counts)
+        with torch.cuda.device(self._device):
+            meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(self._device)
+            b, lengths, (O, _, T) = self._score_call(predictions, 1, meta, max_target, posteriors)
+        return _scoring.scored(b, (O, N, 1), T, max_target, names, [name for name in names if name in targets], lengths, counts)
+
+    def score(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]], posteriors: bool = False
+              ) -> Dict[str, List[Optional["_scoring.Score"]]]:
+        """``score_device`` fetched to the host: per output with targets and utterance a ``Score`` (``None`` where the targets
+        have no path through the frames)."""
+        return {name: [row[0] for row in rows] for name, rows in self.score_device(predictions, targets, posteriors).scores().items()}
+
+    def rescore_device(self, predictions: Predictions, beam_decoded: "BeamDecoded") -> "_scoring.Rescored":
+        """The exact log P(hypothesis | emissions) of every hypothesis of ``beam_decoded`` (``beam_decode_device`` of these
+        predictions), whose own scores are those of a pruned search, and the softmax over each n-best list.  The targets are
+        packed on the device from ``tokens`` / ``counts``; the host synchronises once, for their sizes."""
+        if predictions._flat is None or predictions._geometry is None:
+            raise ValueError("predictions were not produced by this estimator")
+        N, _ = predictions._geometry
+        if predictions._inventory is not None:
+            self._set_inventory(predictions._inventory)
+        names = list(predictions.outputs.keys())
+        O, Nb, B, T = beam_decoded.tokens.shape
+        if beam_decoded.names != names or Nb != N or N == 0:
+            raise ValueError("beam_decoded does not belong to these predictions")
+        with torch.cuda.device(self._device):
+            present = torch.arange(B, device=self._device).view(1, 1, B) < beam_decoded.hyp_counts.view(O, N, 1)
+            counts = torch.where(present, beam_decoded.counts, torch.zeros_like(beam_decoded.counts)).reshape(-1).to(torch.int64)
+            ends = torch.cumsum(counts, 0)
+            total, max_target = (int(v) for v in torch.stack([ends[-1], counts.max()]).cpu())  # the one synchronisation
+            if max_target > _scoring.SCORE_MAX_TARGET:
+                raise ValueError(f"at most {_scoring.SCORE_MAX_TARGET} targets per row on the device, got {max_target}")
+            at = torch.arange(total, device=self._device)
+            row = torch.searchsorted(ends, at, right=True)
+            ids = beam_decoded.tokens.reshape(-1, T)[row, at - (ends - counts)[row]]
+            meta = torch.cat([torch.zeros(1, dtype=torch.int64, device=self._device), ends, ids,
+                              torch.zeros(1, dtype=torch.int64, device=self._device)]).to(torch.int32)
+            b, _, _ = self._score_call(predictions, B, meta, max_target, False)
+            ll = torch.where(present, b.log_likelihood.view(O, N, B), torch.full((), -math.inf, device=self._device))
+            return _scoring.Rescored(names, ll, torch.nan_to_num(torch.softmax(ll, -1), nan=0.0), b.status.view(O, N, B))
 
     def debug_fetch(self, what: str, index: int = 0) -> Tensor:
         """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors."""

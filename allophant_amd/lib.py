@@ -57,6 +57,9 @@ EDIT_MAX_CANDIDATES = 64  # AMX_EDIT_MAX_CANDIDATES
 # the CTC forced-alignment entry points (include/allophant_amx_align.h; added to ABI 6, detected by name)
 ALIGN_EXPORTS = ["amx_ctc_align_workspace", "amx_ctc_align_emissions", "amx_ctc_align"]
 ALIGN_MAX_TARGET = 4095  # AMX_ALIGN_MAX_TARGET
+# the CTC forward-backward scoring entry points (include/allophant_amx_score.h; added to ABI 6, detected by name)
+SCORE_EXPORTS = ["amx_ctc_score_workspace", "amx_ctc_score_emissions", "amx_ctc_score"]
+SCORE_MAX_TARGET = 4095  # AMX_SCORE_MAX_TARGET
 
 
 def dep_output_layer(i: int) -> int:
@@ -187,6 +190,14 @@ def load() -> C.CDLL:
         lib.amx_ctc_align_emissions.restype = i32
         lib.amx_ctc_align.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
         lib.amx_ctc_align.restype = i32
+    if hasattr(lib, "amx_ctc_score"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_ctc_score_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_ctc_score_workspace.restype = i32
+        lib.amx_ctc_score_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, i32, vp, vp, i64, vp, C.c_size_t, vp, vp,
+                                                vp, vp, vp, vp, vp]
+        lib.amx_ctc_score_emissions.restype = i32
+        lib.amx_ctc_score.argtypes = [vp, vp, C.POINTER(i64), i32, i64, i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+        lib.amx_ctc_score.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
