@@ -11,7 +11,7 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "levensthein_statistics", "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations",
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
            "levensthein_matrix", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "Score", "Scored",
-           "Rescored", "ctc_score"]
+           "Rescored", "ctc_score", "Found", "Hit", "ctc_search", "pick_hits", "query_targets"]
 __version__ = "0.1.0"
 
 
@@ -36,4 +36,8 @@ def __getattr__(name):
         from . import scoring
 
         return getattr(scoring, name)
+    if name in ("Found", "Hit", "ctc_search", "pick_hits", "query_targets"):
+        from . import search
+
+        return getattr(search, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -192,22 +192,25 @@ def label_targets(maps_or_evaluator, labels: Sequence[Sequence[str]], languages:
         unknown = sorted(set(languages) - set(maps.languages))
         if unknown:
             raise ValueError(f"languages {unknown} are not among {maps.languages}")
-    result: Dict[str, List[List[int]]] = {}
-    for o, name in enumerate(maps.names):
-        categories = list(maps.inventory) if name in IPA_LAYERS else maps.table.feature_categories(name)
-        classes = {}
-        for k, symbol in enumerate(categories):
-            classes.setdefault(symbol, k + BLANK_OFFSET)
-        rows = []
-        for n, label in enumerate(labels):
-            unknown = [s for s in label if s not in maps.label_ids]
-            if unknown:
-                raise ValueError(f"output {name!r}, utterance {n}: label symbol {unknown[0]!r} is not in the attribute table")
-            row = []
-            for symbol in maps.expand_label(o, label):
-                if symbol not in classes:
-                    raise ValueError(f"output {name!r}, utterance {n}: symbol {symbol!r} has no class under this inventory")
-                row.append(classes[symbol])
-            rows.append(row)
-        result[name] = rows
-    return result
+    return {name: output_targets(maps, o, labels) for o, name in enumerate(maps.names)}
+
+
+def output_targets(maps, o: int, labels: Sequence[Sequence[str]], row_name: str = "utterance") -> List[List[int]]:
+    """``label_targets`` for output ``o`` of ``maps`` alone; ``row_name`` is what an error calls a row of ``labels``."""
+    name = maps.names[o]
+    categories = list(maps.inventory) if name in IPA_LAYERS else maps.table.feature_categories(name)
+    classes = {}
+    for k, symbol in enumerate(categories):
+        classes.setdefault(symbol, k + BLANK_OFFSET)
+    rows = []
+    for n, label in enumerate(labels):
+        unknown = [s for s in label if s not in maps.label_ids]
+        if unknown:
+            raise ValueError(f"output {name!r}, {row_name} {n}: label symbol {unknown[0]!r} is not in the attribute table")
+        row = []
+        for symbol in maps.expand_label(o, label):
+            if symbol not in classes:
+                raise ValueError(f"output {name!r}, {row_name} {n}: symbol {symbol!r} has no class under this inventory")
+            row.append(classes[symbol])
+        rows.append(row)
+    return rows

@@ -5,6 +5,7 @@
 #include "../../include/allophant_amx_beam.h"
 #include "../../include/allophant_amx_align.h"
 #include "../../include/allophant_amx_score.h"
+#include "../../include/allophant_amx_search.h"
 #include "../../include/allophant_amx_resample.h"
 #include "../../include/allophant_amx_edit.h"
 #include "amx_common.h"
@@ -2481,6 +2482,56 @@ extern "C" int amx_ctc_score(amx_handle h, const float* out, const int64_t* fram
     a.posteriors = posteriors, a.status = status;
     launch_ctc_score(a, s);
     HIPCHK(h, hipGetLastError());
+    return AMX_OK;
+}
+
+// =================================================================================================================
+// CTC search for label sequences within utterances
+// =================================================================================================================
+namespace {
+int search_check(int64_t N, int64_t Q, int64_t T, int64_t max_query) {
+    if (N < 0 || Q < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative search geometry");
+    if (max_query < 1 || max_query > AMX_SEARCH_MAX_QUERY)
+        return fail(nullptr, AMX_EINVAL, "max_query must be 1 to " + std::to_string(AMX_SEARCH_MAX_QUERY) + ", got " + std::to_string(max_query));
+    int64_t cells = 0;
+    if (__builtin_mul_overflow(N, Q, &cells) || cells > INT32_MAX || __builtin_mul_overflow(cells, T, &cells) || cells > INT32_MAX)
+        return fail(nullptr, AMX_EINVAL, "N * Q * T must be below 2^31");
+    return AMX_OK;
+}
+}  // namespace
+
+extern "C" int amx_ctc_search_workspace(int64_t N, int64_t Q, int64_t T, int64_t max_query, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = search_check(N, Q, T, max_query)) return rc;
+    if (!ctc_search_workspace_bytes(N, T, bytes)) return fail(nullptr, AMX_EINVAL, "search workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_search_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                        const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index,
+                                        const int32_t* query_offsets, const int32_t* query_ids, int Q, int64_t max_query,
+                                        void* workspace, size_t workspace_bytes, float* best_scores, int32_t* best_spans,
+                                        int32_t* status, float* end_scores, int32_t* end_starts, void* stream) {
+    if (int rc = search_check(N, Q, T, max_query)) return rc;
+    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
+    if ((end_scores == nullptr) != (end_starts == nullptr))
+        return fail(nullptr, AMX_EINVAL, "end_scores and end_starts must both be null or both be given");
+    if (N == 0 || Q == 0) return AMX_OK;
+    if (!frame_lengths || !query_offsets || !query_ids || !best_scores || !best_spans || !status || (T && !emissions))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    size_t need = 0;
+    if (!ctc_search_workspace_bytes(N, T, &need)) return fail(nullptr, AMX_EINVAL, "search workspace size not representable");
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(nullptr, AMX_EINVAL, "search workspace too small: " + std::to_string(need) + " bytes needed");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    SearchArgs a{};
+    a.emissions = emissions, a.stride_n = stride_n, a.stride_t = stride_t;
+    a.frame_lengths = frame_lengths, a.query_offsets = query_offsets, a.query_ids = query_ids;
+    a.N = N, a.T = (int)T, a.C = C, a.blank = blank_index, a.Q = Q, a.max_query = (int)max_query;
+    a.frame_max = (float*)workspace;
+    a.best_scores = best_scores, a.best_spans = best_spans, a.status = status, a.end_scores = end_scores, a.end_starts = end_starts;
+    launch_ctc_search(a, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "search kernel launch failed");
     return AMX_OK;
 }
 

@@ -542,6 +542,24 @@ struct ScoreArgs {
 bool ctc_score_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
 void launch_ctc_score(ScoreArgs a, hipStream_t s);
 
+// CTC search (amx_ctc_search.hip), one wave per (utterance, query) row n * Q + q over one [N, T, C] tensor read with element
+// strides (stride_n, stride_t, 1): contract in include/allophant_amx_search.h.  `frame_max` is the workspace, the per-frame
+// maxima [N, T] that a pre-pass writes.  Limits (checked by the caller): 2 <= C, 1 <= max_query <= 256, N * Q * T < 2^31.
+struct SearchArgs {
+    const float* emissions;
+    int64_t stride_n, stride_t;
+    const int32_t *frame_lengths, *query_offsets, *query_ids;
+    int N, T, C, blank, Q, max_query;
+    float* frame_max;
+    float* best_scores;
+    int32_t *best_spans, *status;
+    float* end_scores;  // the curves: both null or both not
+    int32_t* end_starts;
+};
+// false when the size is not representable in size_t
+bool ctc_search_workspace_bytes(int64_t N, int64_t T, size_t* bytes);
+void launch_ctc_search(SearchArgs a, hipStream_t s);
+
 // allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
 // strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]
 // of ent_p / ent_w and the accumulator start col_init[l * Q1 + q]; language_ids int32 [N] in [0, n_lang)

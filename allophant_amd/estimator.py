@@ -29,9 +29,11 @@ from torch import Tensor
 from . import alignment as _alignment
 from . import lib as _lib
 from . import scoring as _scoring
+from . import search as _search
 from . import spec as _spec
 from .alignment import Aligned, Alignment, ctc_forced_align, label_targets  # noqa: F401  (the façade's alignment names)
 from .scoring import Rescored, Score, Scored, ctc_score  # noqa: F401  (the façade's scoring names)
+from .search import Found, Hit, ctc_search, pick_hits, query_targets  # noqa: F401  (the façade's search names)
 
 
 @dataclass
@@ -769,6 +771,22 @@ class Estimator:
             b, _, _ = self._score_call(predictions, B, meta, max_target, False)
             ll = torch.where(present, b.log_likelihood.view(O, N, B), torch.full((), -math.inf, device=self._device))
             return _scoring.Rescored(names, ll, torch.nan_to_num(torch.softmax(ll, -1), nan=0.0), b.status.view(O, N, B))
+
+    def search_device(self, predictions: Predictions, queries: Sequence[Sequence[int]], output: str,
+                      curves: bool = False) -> "_search.Found":
+        """On-device CTC search (``amx_ctc_search_emissions``) of every utterance of ``predictions.outputs[output]`` for every
+        query (class indices of that output under the predictions' own inventory, e.g. from ``query_targets``): where each
+        query occurs best, and with ``curves`` the best occurrence ending at every frame (``Found.hits``).  The output's
+        ``[T, N, C]`` tensor is read in place through its transposed view; the result stays in HBM."""
+        if output not in predictions.outputs:
+            raise ValueError(f"unknown output {output!r}, the predictions hold {list(predictions.outputs.keys())}")
+        return _search.ctc_search(predictions.outputs[output].transpose(0, 1), predictions.lengths, queries, 0, curves)
+
+    def search(self, predictions: Predictions, queries: Sequence[Sequence[int]], output: str
+               ) -> List[List[Optional["_search.Hit"]]]:
+        """``search_device`` fetched to the host: per utterance and query the best ``Hit`` (``None`` where the query does not
+        occur)."""
+        return self.search_device(predictions, queries, output).best()
 
     def debug_fetch(self, what: str, index: int = 0) -> Tensor:
         """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors."""
