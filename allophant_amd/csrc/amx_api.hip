@@ -206,6 +206,7 @@ struct amx_handle_s {
     int last_N = 0;
     bool last_fold = false;  // amx_pass_info: the last pass ran its encoder layers with the LayerNorm fold ...
     int last_packed = 0, last_graph = 0;  // ... on packed rows (1; 2: from the feature projection on); eager / recorded / replayed
+    int last_attention = -1;              // ... with this form of the attention kernels (AttnForm; -1: an encoder without layers)
     int64_t last_rows = 0;
     bool qkv_dirty = false;
     int64_t last_L = 0, last_T = 0;
@@ -1298,6 +1299,18 @@ struct PassPlan {
         g.splitk_ws_elems = splitk ? (int64_t)(SPLITK_BYTES / 4) : 0;
         return g;
     }
+    // ---- the attention of an encoder layer (the same for every layer) ----
+    AttnParams attn_params() const {
+        AttnParams a{};
+        a.q = qb; a.k = kb; a.v = vtb;
+        a.qk_plane = qk_plane;
+        a.out = ao; a.out_plane = xp_plane;
+        a.frame_len = d_frames_enc;
+        a.N = N; a.H = H; a.T = T; a.Tp = packed ? TpTot : Tp; a.dh = dh; a.dhp = dhp;
+        a.row_off = packed ? (const int*)d_rowoff : nullptr;
+        a.order = packed ? (const int*)d_rowoff + N + 1 : nullptr;
+        return a;
+    }
     // ---- the products of an encoder layer ----
     GemmParams qkv_params(amx_handle h, const Layer& ly) const {
         GemmParams g{};
@@ -1670,6 +1683,7 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     ++h->pass_counter;
     h->last_fold = P.fold;
     h->last_packed = P.packed_early ? 2 : (P.packed ? 1 : 0);
+    h->last_attention = c.layers > 0 ? attention_form(P.attn_params()) : -1;
     h->last_rows = P.Mrows;
     h->last_graph = 0;
 #undef WS
@@ -1910,15 +1924,9 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
         }
         gemm(P.fold ? P.as_consumer(P.qkv_params(h, ly), ly.c_qkv) : P.qkv_params(h, ly));
         {
-            AttnParams a{};
-            a.q = P.qb; a.k = P.kb; a.v = P.vtb;
-            a.qk_plane = P.qk_plane;
-            a.out = P.ao; a.out_plane = P.xp_plane;
-            a.frame_len = P.d_frames_enc;
-            a.N = N; a.H = P.H; a.T = T; a.Tp = P.packed ? P.TpTot : P.Tp; a.dh = P.dh; a.dhp = P.dhp;
-            a.row_off = P.packed ? (const int*)P.d_rowoff : nullptr;
-            a.order = P.packed ? (const int*)P.d_rowoff + N + 1 : nullptr;
-            { Timed t_(h, AMX_KC_ATTENTION); launch_attention(prec, a, s); }
+            // (the form is what plan_pass reported: attention_form of the same parameters)
+            Timed t_(h, AMX_KC_ATTENTION);
+            launch_attention(prec, P.attn_params(), s);
         }
         if (P.fold) {
             residual_gemm(P.as_producer(P.oproj_params(h, ly), false), false);  // (nothing reads the stream between the two halves of a layer)
@@ -2149,7 +2157,8 @@ extern "C" int amx_forward(amx_handle h, const float* audio, const int64_t* leng
 extern "C" int amx_pass_info(amx_handle h, int32_t* info, int n) {
     if (!h || !info || n < 0) return AMX_EINVAL;
     const int32_t values[AMX_PASS_INFO_COUNT] = {h->last_fold ? 1 : 0, h->last_packed, h->last_graph,
-                                                 (int32_t)std::min<int64_t>(h->last_rows, INT32_MAX), (int32_t)(h->pass_counter & 0x7fffffff)};
+                                                 (int32_t)std::min<int64_t>(h->last_rows, INT32_MAX), (int32_t)(h->pass_counter & 0x7fffffff),
+                                                 h->last_attention};
     for (int i = 0; i < n && i < AMX_PASS_INFO_COUNT; ++i) info[i] = values[i];
     return AMX_OK;
 }

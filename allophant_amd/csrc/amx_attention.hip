@@ -299,7 +299,9 @@ __global__ __launch_bounds__(WAVES * KS * 64, AMX_ATTN_OCC) void attn_kernel(con
         // starts at 0, not at the scores' level); afterwards the maximum only moves when a tile exceeds it by 2^THR.
         if (i == 0 || !__all(mx <= DEFER_THR)) {
             const float d = i == 0 ? mx : fmaxf(mx, 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-d);
+            // alpha only ever shrinks: the first tile has nothing to rescale (l_run and O are zero) and its maximum may lie below
+            // -128, where 2^-d is an infinity and 0 * inf a NaN
+            const float alpha = __builtin_amdgcn_exp2f(-fmaxf(d, 0.f));
             m_run += d;
             l_run *= alpha;
 #pragma unroll
@@ -751,7 +753,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 1 : 2) void attn2_kernel(c
                     // the first block takes its own maximum; afterwards the maximum only moves when a block exceeds it by 2^THR
                     if (first_block || !__all(mx <= DEFER_THR)) {
                         const float d = first_block ? mx : fmaxf(mx, 0.f);
-                        const float alpha = __builtin_amdgcn_exp2f(-d);
+                        const float alpha = __builtin_amdgcn_exp2f(-fmaxf(d, 0.f));  // (never above 1: see attn_kernel)
                         m_run[sb] += d;
                         l_run[sb] *= alpha;
 #pragma unroll
@@ -944,48 +946,61 @@ void launch_attn_wide(const AttnParams& p, hipStream_t stream) {
     else launch_attn_other_dh<T, NT, PACKED, 2>(p, stream);
 }
 
-template <typename T, int NT>
-void launch_attn_any(const AttnParams& p, hipStream_t stream) {
-    if (p.dh != DH) {
-        if (p.dhp > 64) {
-            if (p.row_off) launch_attn_wide<T, NT, true>(p, stream);
-            else launch_attn_wide<T, NT, false>(p, stream);
-        } else {
-            if (p.row_off) launch_attn_other_dh<T, NT, true, 1>(p, stream);
-            else launch_attn_other_dh<T, NT, false, 1>(p, stream);
-        }
-        return;
-    }
-    // Short batches (e.g. 4 x 10 s: 64 (utterance, head) pairs x 2 blocks of 256 queries) leave most CUs without a
-    // workgroup while the busy ones run two waves per SIMD: with 128-query workgroups of 4 waves the same waves spread over
-    // twice as many CUs, one per SIMD.  Each query's arithmetic is identical in both forms (bitwise equal outputs).
+static int device_cus() {
     static int cus_of[MAX_DEVICES] = {};
     int& cus = cus_of[current_device()];
     if (!cus) {
         hipDeviceProp_t prop;
         cus = hipGetDeviceProperties(&prop, current_device()) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
+    return cus;
+}
+
+int attention_form(const AttnParams& p) {
+    if (p.dh != DH) return p.dhp > 64 ? ATTN_FORM_DH_WIDE : ATTN_FORM_DH_OTHER;
+    // Short batches (e.g. 4 x 10 s: 64 (utterance, head) pairs x 2 blocks of 256 queries) leave most CUs without a
+    // workgroup while the busy ones run two waves per SIMD: with 128-query workgroups of 4 waves the same waves spread over
+    // twice as many CUs, one per SIMD.  Each query's arithmetic is identical in both forms (bitwise equal outputs).
+    const int cus = device_cus();
     const int64_t wg8 = (int64_t)p.N * p.H * ((p.T + 255) / 256);
     // 64 queries per wave (attn2_kernel, 256-query workgroups) for long key loops on a full chip
     // (crossover measured at 12-15 key tiles per item with the chip full: T = 749 123 -> 147 us, T = 999 235 -> 221,
     // T = 1499 246 -> 234, T = 1999 640 -> 558, T = 2999 849 -> 752; one utterance alone keeps the 32-query waves)
-    if (wg8 * 2 >= 3 * (int64_t)cus && p.T >= 960) {
-        launch_attn2<T, NT, 4, 2>(p, cus, stream);
-        return;
-    }
+    if (wg8 * 2 >= 3 * (int64_t)cus && p.T >= 960) return ATTN_FORM_LONG;
     const bool small = wg8 * 2 <= cus;
     // ... and when even the 128-query workgroups are at most one per CU, the key tiles of a query block are split over two wave
     // groups (KS = 2): two waves per SIMD instead of one, half the serial key loop
     const int64_t wg4 = (int64_t)p.N * p.H * ((p.T + 127) / 128);
     // (tools/attn_bench.hip, per launch: 4 x 10 s 23.0 -> 21.2 us, 1 x 10 s 19.2 -> 17.4, 2 x 20 s 38.7 -> 34.4; 1 x 3 s -- three key
     // tiles -- 10.3 -> 10.9: from six tiles on)
-    if (small && wg4 <= cus && p.T >= 384) launch_attn<T, NT, 4, 64, 2>(p, stream);
-    else if (small) launch_attn<T, NT, 4, 64>(p, stream);
-    else launch_attn<T, NT, 8, 64>(p, stream);
+    if (small && wg4 <= cus && p.T >= 384) return ATTN_FORM_W4_KS2;
+    return small ? ATTN_FORM_W4 : ATTN_FORM_W8;
 }
 
-void launch_attention(int prec, const AttnParams& p, hipStream_t stream) {
-    AMX_DISPATCH(prec, (launch_attn_any<T16, NT>(p, stream)));
+template <typename T, int NT>
+int launch_attn_any(const AttnParams& p, hipStream_t stream) {
+    const int form = attention_form(p);
+    switch (form) {
+        case ATTN_FORM_DH_WIDE:
+            if (p.row_off) launch_attn_wide<T, NT, true>(p, stream);
+            else launch_attn_wide<T, NT, false>(p, stream);
+            break;
+        case ATTN_FORM_DH_OTHER:
+            if (p.row_off) launch_attn_other_dh<T, NT, true, 1>(p, stream);
+            else launch_attn_other_dh<T, NT, false, 1>(p, stream);
+            break;
+        case ATTN_FORM_LONG: launch_attn2<T, NT, 4, 2>(p, device_cus(), stream); break;
+        case ATTN_FORM_W4_KS2: launch_attn<T, NT, 4, 64, 2>(p, stream); break;
+        case ATTN_FORM_W4: launch_attn<T, NT, 4, 64>(p, stream); break;
+        default: launch_attn<T, NT, 8, 64>(p, stream); break;
+    }
+    return form;
+}
+
+int launch_attention(int prec, const AttnParams& p, hipStream_t stream) {
+    int form = -1;
+    AMX_DISPATCH(prec, form = (launch_attn_any<T16, NT>(p, stream)));
+    return form;
 }
 
 }  // namespace amx

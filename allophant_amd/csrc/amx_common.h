@@ -378,7 +378,18 @@ struct AttnParams {
     const int* order;  // packed rows only, may be null: utterance indices, longest first (workgroups are dispatched in this order)
     unsigned long long* stamps;  // developer diagnostic (-DAMX_ATTN_STAMP builds of tools/attn_bench.hip), else null
 };
-void launch_attention(int prec, const AttnParams& p, hipStream_t stream);
+// The form launch_attention runs `p` in on the current device (amx_pass_info: AMX_PASS_INFO_ATTENTION) -- the one place that
+// decides it, from N, H, T, dh, dhp and the device's CU count: launch_attention switches on this value.
+enum AttnForm {
+    ATTN_FORM_W8 = 0,         // attn_kernel, 256-query workgroups of 8 waves
+    ATTN_FORM_W4 = 1,         // ... 128-query workgroups of 4 waves
+    ATTN_FORM_W4_KS2 = 2,     // ... 4 query waves x 2 key halves (KS = 2)
+    ATTN_FORM_LONG = 3,       // attn2_kernel: 64 queries per wave, long key loops on a full chip
+    ATTN_FORM_DH_OTHER = 4,   // head_dim != 64, rows of 64 columns
+    ATTN_FORM_DH_WIDE = 5,    // head_dim != 64, rows of 128 columns
+};
+int attention_form(const AttnParams& p);
+int launch_attention(int prec, const AttnParams& p, hipStream_t stream);  // returns the form it launched
 
 // ---------------------------------------------------------------------------------------------------------------
 // row-wise / elementwise kernels (amx_rowops.hip)

@@ -834,7 +834,9 @@ class Estimator:
     def pass_info(self) -> Dict[str, int]:
         """Which optional forms the last ``predict`` took (``amx_pass_info``): ``ln_fold`` 1 = LayerNorm folded into the encoder
         products, ``packed`` 0 / 1 / 2 = padded rows / packed layers / packed from the feature projection on, ``graph`` 0 / 1 / 2
-        = eager / recorded / replayed, ``rows`` = frames the encoder layers worked on."""
+        = eager / recorded / replayed, ``rows`` = frames the encoder layers worked on, ``id`` = number of the pass, ``attention`` = the
+        form of the attention kernels (0 / 1: 8- / 4-wave workgroups, 2: 4 waves with the key split, 3: the long-key kernel, 4 / 5:
+        a head dimension other than 64 on 64- / 128-wide rows)."""
         if _lib.AMX_ABI_VERSION < 6:
             return {}
         n = len(_lib.PASS_INFO)

@@ -209,7 +209,12 @@ int amx_graph_info(amx_handle h, int64_t* captures, int64_t* replays);
 #define AMX_PASS_INFO_ROWS 3      /* rows (frames) the encoder layers worked on */
 #define AMX_PASS_INFO_ID 4        /* number of the pass among the amx_forward calls of this handle (from 1; low 31 bits): an AMX_ERANGE
                                      report names the offending pass by this number */
-#define AMX_PASS_INFO_COUNT 5
+#define AMX_PASS_INFO_ATTENTION 5 /* the form the attention of the encoder layers ran in (appended: a caller that asks for 5 values is
+                                     unaffected).  0: 256-query workgroups of 8 waves; 1: 128-query workgroups of 4 waves; 2: 4 waves with
+                                     the key tiles split over two wave groups; 3: the long-key kernel (64 queries per wave); 4 / 5: a head
+                                     dimension other than 64, on rows of 64 / 128 columns; -1: an encoder without layers.  Which one a
+                                     batch takes depends on its geometry and on the device's CU count */
+#define AMX_PASS_INFO_COUNT 6
 int amx_pass_info(amx_handle h, int32_t* info, int n);
 
 /* Range check of the last amx_forward on `stream` (no upstream counterpart: the reference computes in fp32).  The 16-bit
