@@ -10,21 +10,16 @@ The path is the Viterbi path of the CTC trellis with ties going to the smaller m
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
 
-from . import lib as _lib
+from . import ctc as _ctc, lib as _lib
+from .ctc import frame_stride, pack_targets  # noqa: F401  (part of this module's interface)
 from .phonetic import BLANK_OFFSET, IPA_LAYERS
 
 ALIGN_MAX_TARGET = _lib.ALIGN_MAX_TARGET
-
-
-def frame_stride(spec: Dict[str, Any]) -> int:
-    """Samples per output frame: the product of the spec's convolution strides."""
-    return math.prod(int(s) for s in spec["conv_stride"])
 
 
 class Alignment(NamedTuple):
@@ -89,18 +84,6 @@ class Aligned(NamedTuple):
         return result
 
 
-def pack_targets(rows: Sequence[Sequence[int]]) -> Tuple[Tensor, Tensor, List[int]]:
-    """Target rows as the C ABI takes them: int32 offsets ``[R + 1]``, int32 ids, and the rows' lengths (host tensors)."""
-    counts = [len(row) for row in rows]
-    if counts and max(counts) > ALIGN_MAX_TARGET:
-        raise ValueError(f"at most {ALIGN_MAX_TARGET} targets per row on the device, got {max(counts)}")
-    offsets = torch.zeros(len(rows) + 1, dtype=torch.int32)
-    if rows:
-        offsets[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0).to(torch.int32)
-    ids = torch.tensor([int(v) for row in rows for v in row], dtype=torch.int32)
-    return offsets, ids, counts
-
-
 class _Buffers(NamedTuple):
     workspace: Tensor
     size: int
@@ -121,7 +104,7 @@ def allocate(lib, rows: int, T: int, max_target: int, device) -> _Buffers:
     """The workspace and outputs of ``rows`` rows of ``T`` frames (at least one element each, so every pointer is valid)."""
     size = C.c_size_t()
     _lib.check(lib, None, lib.amx_ctc_align_workspace(rows, T, max_target, C.byref(size)))
-    empty = lambda *shape, dtype: torch.empty(max(1, math.prod(shape)), dtype=dtype, device=device)[:math.prod(shape)].view(*shape)  # noqa: E731
+    empty = lambda *shape, dtype: _ctc.empty(*shape, dtype=dtype, device=device)  # noqa: E731
     return _Buffers(torch.empty(max(1, size.value), dtype=torch.uint8, device=device), size.value,
                     empty(rows, T, dtype=torch.int32), empty(rows, T, dtype=torch.float32),
                     empty(rows, max_target, 2, dtype=torch.int32), empty(rows, max_target, dtype=torch.float32),
@@ -135,39 +118,23 @@ def ctc_forced_align(log_emissions: Tensor, lengths: Optional[Tensor],
     with a unit class stride, read in place) via ``amx_ctc_align_emissions``.  ``targets``: one int sequence per row, or a
     padded ``[N, max_len]`` tensor with its lengths ``(padded, target_lengths)``.  Per row an ``Alignment``, or ``None`` where
     no alignment exists (too few frames, or ``-inf`` emissions on every path); ``ValueError`` names a malformed row."""
-    if log_emissions.dim() != 3:
-        raise ValueError("log_emissions must be [N, T, C]")
-    if log_emissions.device.type != "cuda":
-        raise RuntimeError("allophant_amd aligns on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "aligns")
     lib = _lib.load()
     device = log_emissions.device
-    if log_emissions.dtype != torch.float32:
-        log_emissions = log_emissions.float()
-    if log_emissions.stride(2) != 1:
-        log_emissions = log_emissions.contiguous()
-    N, T, Cn = log_emissions.shape
     if isinstance(targets, tuple) and len(targets) == 2 and isinstance(targets[0], Tensor):
         padded, target_lengths = targets[0].cpu().tolist(), [int(v) for v in targets[1].cpu().tolist()]
         targets = [row[:k] for row, k in zip(padded, target_lengths)]
     if len(targets) != N:
         raise ValueError(f"{len(targets)} target rows for {N} emission rows")
-    if Cn < 2:
-        raise ValueError("alignment needs at least 2 classes")
-    if not 0 <= blank_index < Cn:
-        raise ValueError("blank_index out of range")
+    _ctc.check_classes(Cn, blank_index, "alignment")
     if N == 0:
         return []
     offsets, ids, counts = pack_targets(targets)
     max_target = max(counts)
     with torch.cuda.device(device):
-        if lengths is None:
-            frame_lengths = torch.full((N,), T, dtype=torch.int32, device=device)
-        else:
-            frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        frame_lengths, index, stream = _ctc.frame(log_emissions, lengths)
         meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(device)  # (never an empty tensor)
         b = allocate(lib, N, T, max_target, device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        index = device.index if device.index is not None else torch.cuda.current_device()
         code = lib.amx_ctc_align_emissions(
             index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
             C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, C.c_void_p(meta.data_ptr()),

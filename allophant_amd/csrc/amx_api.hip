@@ -2214,6 +2214,41 @@ static int upload_frame_lengths(amx_handle h, const int64_t* frame_lengths, int 
     return AMX_OK;
 }
 
+// ---- the call frame that the CTC entry points share ----
+static int check_workspace(amx_handle h, const char* what, size_t need, const void* workspace, size_t bytes) {
+    if (bytes < need || (need && !workspace))
+        return fail(h, AMX_EINVAL, std::string(what) + " workspace too small: " + std::to_string(need) + " bytes needed");
+    return AMX_OK;
+}
+// the launch of either form of a call: the handle form (h) keeps HIP's own error text
+static int ctc_launched(amx_handle h, const char* what) {
+    if (!h) return hipGetLastError() == hipSuccess ? AMX_OK : fail(nullptr, AMX_EHIP, std::string(what) + " kernel launch failed");
+    HIPCHK(h, hipGetLastError());
+    return AMX_OK;
+}
+// The emission source of an alignment or scoring call, the first half of its CtcRows.  Of a handle: every output block of
+// `out` under the layout of (N, L), one row each, blank 0; its frame lengths are on the host, and ctc_rows_begin uploads them once the
+// other arguments are checked.  Of a tensor: as the caller describes it, one row per utterance; ctc_rows_begin selects its
+// device.
+static int rows_of_handle(amx_handle h, const float* out, int N, int64_t L, CtcRows* c) {
+    if (int rc = compute_layout(h, N, L)) return rc;
+    *c = CtcRows{};
+    c->emissions = out, c->descs = cur_inv(h).out_all_dev, c->N = N, c->T = (int)h->layout_T;
+    c->rows = (int64_t)h->out_all.size() * N;
+    return AMX_OK;
+}
+static CtcRows rows_of_tensor(const float* emissions, int64_t stride_n, int64_t stride_t, const int32_t* frame_lengths, int N, int64_t T,
+                              int C, int blank) {
+    CtcRows c{};
+    c.emissions = emissions, c.stride_n = stride_n, c.stride_t = stride_t, c.frame_lengths = frame_lengths;
+    c.rows = N, c.N = N, c.T = (int)T, c.C = C, c.blank = blank;
+    return c;
+}
+static int ctc_rows_begin(amx_handle h, int device, const int64_t* host_lengths, CtcRows* c, hipStream_t s) {
+    if (h) return upload_frame_lengths(h, host_lengths, c->N, c->T, s, &c->frame_lengths);
+    return hipSetDevice(device) == hipSuccess ? AMX_OK : fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+}
+
 extern "C" int amx_greedy_ctc(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
                               int64_t* tokens, int64_t* timesteps, int32_t* counts, float* scores, void* stream) {
     if (!h || !out || !frame_lengths || !tokens || !timesteps || !counts || !scores) return AMX_EINVAL;
@@ -2225,8 +2260,7 @@ extern "C" int amx_greedy_ctc(amx_handle h, const float* out, const int64_t* fra
     const int* d_fl;
     if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
     launch_greedy_ctc(cur_inv(h).out_all_dev, (int)h->out_all.size(), out, d_fl, N, T, tokens, timesteps, counts, scores, s);
-    HIPCHK(h, hipGetLastError());
-    return AMX_OK;
+    return ctc_launched(h, "greedy CTC");
 }
 
 extern "C" int amx_greedy_ctc_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
@@ -2237,8 +2271,7 @@ extern "C" int amx_greedy_ctc_emissions(int device, const float* emissions, int6
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_greedy_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, tokens, timesteps, counts,
                                 scores, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "greedy CTC kernel launch failed");
-    return AMX_OK;
+    return ctc_launched(nullptr, "greedy CTC");
 }
 
 // =================================================================================================================
@@ -2284,14 +2317,12 @@ extern "C" int amx_beam_ctc(amx_handle h, const float* out, const int64_t* frame
     const int64_t rows = (int64_t)h->out_all.size() * N;
     size_t need = 0;
     amx_beam_ctc_workspace(beam_width, rows, T, &need);
-    if (workspace_bytes < need || (need && !workspace))
-        return fail(h, AMX_EINVAL, "beam-search workspace too small: " + std::to_string(need) + " bytes needed");
+    if ((rc = check_workspace(h, "beam-search", need, workspace, workspace_bytes))) return rc;
     const int* d_fl;
     if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
     launch_beam_ctc(cur_inv(h).out_all_dev, (int)h->out_all.size(), out, d_fl, N, T, beam_width, n_best,
                     (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores, hyp_counts, s);
-    HIPCHK(h, hipGetLastError());
-    return AMX_OK;
+    return ctc_launched(h, "beam-search");
 }
 
 extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
@@ -2308,14 +2339,12 @@ extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_
         return fail(nullptr, AMX_EINVAL, "null buffer");
     size_t need = 0;
     amx_beam_ctc_workspace(beam_width, N, T, &need);
-    if (workspace_bytes < need || (need && !workspace))
-        return fail(nullptr, AMX_EINVAL, "beam-search workspace too small: " + std::to_string(need) + " bytes needed");
+    if (int rc = check_workspace(nullptr, "beam-search", need, workspace, workspace_bytes)) return rc;
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_beam_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, beam_width, n_best,
                               (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores,
                               hyp_counts, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "beam-search kernel launch failed");
-    return AMX_OK;
+    return ctc_launched(nullptr, "beam-search");
 }
 
 // =================================================================================================================
@@ -2335,12 +2364,21 @@ int align_check_classes(amx_handle h, int C, int blank) {
     if (blank < 0 || blank >= C) return fail(h, AMX_EINVAL, "blank_index out of range");
     return AMX_OK;
 }
-int align_check_workspace(amx_handle h, int64_t rows, int64_t T, int64_t max_target, const void* workspace, size_t workspace_bytes) {
+// amx_ctc_align / amx_ctc_align_emissions from the workspace check on: `c` holds the emission source and the row count
+int align_rows(amx_handle h, int device, CtcRows c, const int64_t* host_lengths, const int32_t* target_offsets,
+               const int32_t* target_ids, int64_t max_target, void* workspace, size_t workspace_bytes, int32_t* paths,
+               float* frame_scores, int32_t* spans, float* span_scores, float* totals, int32_t* status, hipStream_t s) {
     size_t need = 0;
-    if (!ctc_align_workspace_bytes(rows, T, max_target, &need)) return fail(h, AMX_EINVAL, "alignment workspace size not representable");
-    if (workspace_bytes < need || (need && !workspace))
-        return fail(h, AMX_EINVAL, "alignment workspace too small: " + std::to_string(need) + " bytes needed");
-    return AMX_OK;
+    if (!ctc_align_workspace_bytes(c.rows, c.T, max_target, &need)) return fail(h, AMX_EINVAL, "alignment workspace size not representable");
+    if (int rc = check_workspace(h, "alignment", need, workspace, workspace_bytes)) return rc;
+    if (int rc = ctc_rows_begin(h, device, host_lengths, &c, s)) return rc;
+    c.target_offsets = target_offsets, c.target_ids = target_ids, c.max_target = (int)max_target;
+    AlignArgs a{};
+    static_cast<CtcRows&>(a) = c;
+    a.workspace = (uint4*)workspace;
+    a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
+    launch_ctc_align(a, s);
+    return ctc_launched(h, "alignment");
 }
 }  // namespace
 
@@ -2362,17 +2400,9 @@ extern "C" int amx_ctc_align_emissions(int device, const float* emissions, int64
     if (!frame_lengths || !target_offsets || !totals || !status || (T && (!emissions || !paths || !frame_scores)) ||
         (max_target && (!target_ids || !spans || !span_scores)))
         return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (int rc = align_check_workspace(nullptr, N, T, max_target, workspace, workspace_bytes)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
-    AlignArgs a{};
-    a.emissions = emissions, a.stride_n = stride_n, a.stride_t = stride_t, a.descs = nullptr;
-    a.frame_lengths = frame_lengths, a.target_offsets = target_offsets, a.target_ids = target_ids;
-    a.rows = N, a.N = N, a.T = (int)T, a.C = C, a.blank = blank_index, a.max_target = (int)max_target;
-    a.workspace = (uint4*)workspace;
-    a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
-    launch_ctc_align(a, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "alignment kernel launch failed");
-    return AMX_OK;
+    const CtcRows c = rows_of_tensor(emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    return align_rows(nullptr, device, c, nullptr, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths,
+                      frame_scores, spans, span_scores, totals, status, (hipStream_t)stream);
 }
 
 extern "C" int amx_ctc_align(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
@@ -2384,27 +2414,15 @@ extern "C" int amx_ctc_align(amx_handle h, const float* out, const int64_t* fram
         (max_target > 0 && (!target_ids || !spans || !span_scores)))
         return fail(h, AMX_EINVAL, "null buffer");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    int rc = compute_layout(h, N, L);
+    CtcRows c;
+    int rc = rows_of_handle(h, out, N, L, &c);
     if (rc) return rc;
-    const int T = (int)h->layout_T;
-    const int64_t rows = (int64_t)h->out_all.size() * N;
-    if ((rc = align_check(h, rows, T, max_target))) return rc;
-    if (rows == 0) return AMX_OK;
+    if ((rc = align_check(h, c.rows, c.T, max_target))) return rc;
+    if (c.rows == 0) return AMX_OK;
     for (const OutDesc& d : h->out_all)
         if ((rc = align_check_classes(h, d.C, 0))) return rc;
-    if ((rc = align_check_workspace(h, rows, T, max_target, workspace, workspace_bytes))) return rc;
-    const int* d_fl;
-    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
-    AlignArgs a{};
-    a.emissions = out, a.descs = cur_inv(h).out_all_dev;
-    a.frame_lengths = d_fl, a.target_offsets = target_offsets, a.target_ids = target_ids;
-    a.rows = rows, a.N = N, a.T = T, a.max_target = (int)max_target;
-    a.workspace = (uint4*)workspace;
-    a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
-    launch_ctc_align(a, s);
-    HIPCHK(h, hipGetLastError());
-    return AMX_OK;
+    return align_rows(h, 0, c, frame_lengths, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths, frame_scores,
+                      spans, span_scores, totals, status, (hipStream_t)stream);
 }
 
 // =================================================================================================================
@@ -2417,12 +2435,24 @@ int score_rows(amx_handle h, int64_t rows, int candidates, int64_t* out) {
     if (__builtin_mul_overflow(rows, (int64_t)candidates, out)) return fail(h, AMX_EINVAL, "rows * T must be below 2^31");
     return AMX_OK;
 }
-int score_check_workspace(amx_handle h, int64_t rows, int64_t T, int64_t max_target, const void* workspace, size_t workspace_bytes) {
+
+// amx_ctc_score / amx_ctc_score_emissions from the workspace check on: `c` holds the emission source and the row count
+int score_rows_run(amx_handle h, int device, CtcRows c, const int64_t* host_lengths, int candidates, const int32_t* target_offsets,
+                   const int32_t* target_ids, int64_t max_target, void* workspace, size_t workspace_bytes, float* log_likelihood,
+                   float* occupancy, float* position_sums, float* score_sums, float* posteriors, int32_t* status, hipStream_t s) {
     size_t need = 0;
-    if (!ctc_score_workspace_bytes(rows, T, max_target, &need)) return fail(h, AMX_EINVAL, "scoring workspace size not representable");
-    if (workspace_bytes < need || (need && !workspace))
-        return fail(h, AMX_EINVAL, "scoring workspace too small: " + std::to_string(need) + " bytes needed");
-    return AMX_OK;
+    if (!ctc_score_workspace_bytes(c.rows, c.T, max_target, &need)) return fail(h, AMX_EINVAL, "scoring workspace size not representable");
+    if (int rc = check_workspace(h, "scoring", need, workspace, workspace_bytes)) return rc;
+    if (int rc = ctc_rows_begin(h, device, host_lengths, &c, s)) return rc;
+    c.target_offsets = target_offsets, c.target_ids = target_ids, c.max_target = (int)max_target;
+    ScoreArgs a{};
+    static_cast<CtcRows&>(a) = c;
+    a.candidates = candidates;
+    a.workspace = (float*)workspace;
+    a.log_likelihood = log_likelihood, a.occupancy = occupancy, a.position_sums = position_sums, a.score_sums = score_sums;
+    a.posteriors = posteriors, a.status = status;
+    launch_ctc_score(a, s);
+    return ctc_launched(h, "scoring");
 }
 }  // namespace
 
@@ -2438,26 +2468,16 @@ extern "C" int amx_ctc_score_emissions(int device, const float* emissions, int64
                                        const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
                                        size_t workspace_bytes, float* log_likelihood, float* occupancy, float* position_sums,
                                        float* score_sums, float* posteriors, int32_t* status, void* stream) {
-    int64_t rows = 0;
-    if (int rc = score_rows(nullptr, N, candidates, &rows)) return rc;
-    if (int rc = align_check(nullptr, rows, T, max_target)) return rc;
+    CtcRows c = rows_of_tensor(emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    if (int rc = score_rows(nullptr, N, candidates, &c.rows)) return rc;
+    if (int rc = align_check(nullptr, c.rows, T, max_target)) return rc;
     if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
     if (N == 0) return AMX_OK;
     if (!frame_lengths || !target_offsets || !log_likelihood || !status || (T && !emissions) ||
         (max_target && (!target_ids || !occupancy || !position_sums || !score_sums)))
         return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (int rc = score_check_workspace(nullptr, rows, T, max_target, workspace, workspace_bytes)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
-    ScoreArgs a{};
-    a.emissions = emissions, a.stride_n = stride_n, a.stride_t = stride_t, a.descs = nullptr;
-    a.frame_lengths = frame_lengths, a.target_offsets = target_offsets, a.target_ids = target_ids;
-    a.rows = rows, a.N = N, a.T = (int)T, a.C = C, a.blank = blank_index, a.max_target = (int)max_target, a.candidates = candidates;
-    a.workspace = (float*)workspace;
-    a.log_likelihood = log_likelihood, a.occupancy = occupancy, a.position_sums = position_sums, a.score_sums = score_sums;
-    a.posteriors = posteriors, a.status = status;
-    launch_ctc_score(a, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "scoring kernel launch failed");
-    return AMX_OK;
+    return score_rows_run(nullptr, device, c, nullptr, candidates, target_offsets, target_ids, max_target, workspace, workspace_bytes,
+                          log_likelihood, occupancy, position_sums, score_sums, posteriors, status, (hipStream_t)stream);
 }
 
 extern "C" int amx_ctc_score(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L, int candidates,
@@ -2469,29 +2489,16 @@ extern "C" int amx_ctc_score(amx_handle h, const float* out, const int64_t* fram
         (max_target > 0 && (!target_ids || !occupancy || !position_sums || !score_sums)))
         return fail(h, AMX_EINVAL, "null buffer");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    int rc = compute_layout(h, N, L);
+    CtcRows c;
+    int rc = rows_of_handle(h, out, N, L, &c);
     if (rc) return rc;
-    const int T = (int)h->layout_T;
-    int64_t rows = 0;
-    if ((rc = score_rows(h, (int64_t)h->out_all.size() * N, candidates, &rows))) return rc;
-    if ((rc = align_check(h, rows, T, max_target))) return rc;
-    if (rows == 0) return AMX_OK;
+    if ((rc = score_rows(h, c.rows, candidates, &c.rows))) return rc;
+    if ((rc = align_check(h, c.rows, c.T, max_target))) return rc;
+    if (c.rows == 0) return AMX_OK;
     for (const OutDesc& d : h->out_all)
         if ((rc = align_check_classes(h, d.C, 0))) return rc;
-    if ((rc = score_check_workspace(h, rows, T, max_target, workspace, workspace_bytes))) return rc;
-    const int* d_fl;
-    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
-    ScoreArgs a{};
-    a.emissions = out, a.descs = cur_inv(h).out_all_dev;
-    a.frame_lengths = d_fl, a.target_offsets = target_offsets, a.target_ids = target_ids;
-    a.rows = rows, a.N = N, a.T = T, a.max_target = (int)max_target, a.candidates = candidates;
-    a.workspace = (float*)workspace;
-    a.log_likelihood = log_likelihood, a.occupancy = occupancy, a.position_sums = position_sums, a.score_sums = score_sums;
-    a.posteriors = posteriors, a.status = status;
-    launch_ctc_score(a, s);
-    HIPCHK(h, hipGetLastError());
-    return AMX_OK;
+    return score_rows_run(h, 0, c, frame_lengths, candidates, target_offsets, target_ids, max_target, workspace, workspace_bytes,
+                          log_likelihood, occupancy, position_sums, score_sums, posteriors, status, (hipStream_t)stream);
 }
 
 // =================================================================================================================
@@ -2530,8 +2537,7 @@ extern "C" int amx_ctc_search_emissions(int device, const float* emissions, int6
         return fail(nullptr, AMX_EINVAL, "null buffer");
     size_t need = 0;
     if (!ctc_search_workspace_bytes(N, T, &need)) return fail(nullptr, AMX_EINVAL, "search workspace size not representable");
-    if (workspace_bytes < need || (need && !workspace))
-        return fail(nullptr, AMX_EINVAL, "search workspace too small: " + std::to_string(need) + " bytes needed");
+    if (int rc = check_workspace(nullptr, "search", need, workspace, workspace_bytes)) return rc;
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     SearchArgs a{};
     a.emissions = emissions, a.stride_n = stride_n, a.stride_t = stride_t;
@@ -2540,8 +2546,7 @@ extern "C" int amx_ctc_search_emissions(int device, const float* emissions, int6
     a.frame_max = (float*)workspace;
     a.best_scores = best_scores, a.best_spans = best_spans, a.status = status, a.end_scores = end_scores, a.end_starts = end_starts;
     launch_ctc_search(a, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "search kernel launch failed");
-    return AMX_OK;
+    return ctc_launched(nullptr, "search");
 }
 
 // =================================================================================================================

@@ -507,20 +507,28 @@ void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t
                                int blank, int beam, int n_best, int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps,
                                int* counts, double* scores, int* hyp_counts, hipStream_t s);
 
-// CTC forced alignment (amx_ctc_align.hip), one workgroup per row: contract in include/allophant_amx_align.h.  With `descs`
-// the rows are o * N + n over every output block of `emissions` (the output buffer; blank 0), else the N utterances of one
-// [N, T, C] tensor read with element strides (stride_n, stride_t, 1).  The launcher fills the workspace geometry: per row
-// `strips` strips of 64 states, each holding t_pad 16-byte move words.  Limits (checked by the callers): 2 <= C,
-// 0 <= max_target <= 4095, rows * T < 2^31.
+// The call frame that CTC forced alignment and forward-backward scoring share (device half in amx_ctc_row.inc): where the
+// emissions lie and which target rows are run over them.  With `descs` the emissions are every output block of the output
+// buffer (blank 0), else the N utterances of one [N, T, C] tensor read with element strides (stride_n, stride_t, 1).  Row r
+// has the targets target_ids[target_offsets[r] .. target_offsets[r + 1]); its S = 2 * targets + 1 states are cut into strips
+// of one wave.  Limits (checked by the callers): 2 <= C, 0 <= max_target <= 4095, rows * T < 2^31.
+constexpr int CTC_WAVE = 64;  // wave size, states per strip
 constexpr int ALIGN_MAX_WAVES = 16;
-struct AlignArgs {
+constexpr int64_t ctc_strips(int64_t max_target) { return (2 * max_target + 1 + CTC_WAVE - 1) / CTC_WAVE; }
+struct CtcRows {
     const float* emissions;
     int64_t stride_n, stride_t;
     const OutDesc* descs;
     const int32_t *frame_lengths, *target_offsets, *target_ids;
     int64_t rows;
     int N, T, C, blank, max_target;
-    int strips;
+    int strips;  // ctc_strips(max_target), filled by the launcher
+};
+
+// CTC forced alignment (amx_ctc_align.hip), one workgroup per row o * N + n (with `descs`) or n: contract in
+// include/allophant_amx_align.h.  The launcher fills the workspace geometry: per row `strips` strips, each holding t_pad
+// 16-byte move words.
+struct AlignArgs : CtcRows {
     int64_t t_pad;
     uint4* workspace;
     int32_t* paths;
@@ -533,18 +541,11 @@ struct AlignArgs {
 bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
 void launch_ctc_align(AlignArgs a, hipStream_t s);
 
-// CTC forward-backward scoring (amx_ctc_score.hip), one workgroup per row: contract in include/allophant_amx_score.h.  Rows
-// are (o * N + n) * G + g with `descs` (every output block of `emissions`, blank 0), else n * G + g over one [N, T, C] tensor
-// read with element strides (stride_n, stride_t, 1); G = candidates.  The launcher fills `strips`: the workspace holds per
-// row and frame strips * 64 forward values.  Limits as for the alignment, on rows = (O *) N * G.
-struct ScoreArgs {
-    const float* emissions;
-    int64_t stride_n, stride_t;
-    const OutDesc* descs;
-    const int32_t *frame_lengths, *target_offsets, *target_ids;
-    int64_t rows;
-    int N, T, C, blank, max_target, candidates;
-    int strips;
+// CTC forward-backward scoring (amx_ctc_score.hip), one workgroup per row (o * N + n) * G + g (with `descs`) or n * G + g,
+// G = candidates: contract in include/allophant_amx_score.h.  The workspace holds per row and frame strips * 64 forward
+// values.  The limits are the alignment's, on rows = (O *) N * G.
+struct ScoreArgs : CtcRows {
+    int candidates;
     float* workspace;
     float *log_likelihood, *occupancy, *position_sums, *score_sums, *posteriors;  // posteriors may be null
     int32_t* status;

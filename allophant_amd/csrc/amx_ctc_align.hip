@@ -23,43 +23,26 @@ namespace amx {
 
 namespace {
 
-constexpr int AW = 64;  // wave size, states per strip
+#include "amx_ctc_row.inc"
 
 template <int SPW, int PF, bool STAGED>
-__global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignArgs a) {
+__global__ __launch_bounds__(ALIGN_MAX_WAVES * CTC_WAVE) void ctc_align_kernel(AlignArgs a) {
     extern __shared__ float state_rows[];  // two rows of a.strips * 64 states; later the span bounds
     const int64_t r = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & (AW - 1), wave = tid / AW, waves = blockDim.x / AW;
+    const int tid = threadIdx.x, lane = tid & (CTC_WAVE - 1), wave = tid / CTC_WAVE, waves = blockDim.x / CTC_WAVE;
     const float neg_inf = -INFINITY;
 
-    // the row's emissions, lp[t][c] at lp[t * st + c]
-    const float* lp;
-    int64_t st;
-    int C, blank, n;
-    if (a.descs) {
-        const OutDesc d = a.descs[r / a.N];
-        n = (int)(r % a.N);
-        lp = a.emissions + (int64_t)a.T * a.N * d.prefix + (int64_t)n * d.C;
-        st = (int64_t)a.N * d.C, C = d.C, blank = 0;
-    } else {
-        n = (int)r;
-        lp = a.emissions + r * a.stride_n;
-        st = a.stride_t, C = a.C, blank = a.blank;
-    }
-    const int len = a.frame_lengths[n];
-    const int lb = a.target_offsets[r], le = a.target_offsets[r + 1], id_count = a.target_offsets[a.rows];
-    const bool malformed = len < 0 || len > a.T || lb < 0 || le < lb || le > id_count || le - lb > a.max_target;
-    const int L = malformed ? 0 : le - lb;
-    const int32_t* y = a.target_ids + lb;
-    int wrong = 0;
-    for (int l = tid; l < L; l += blockDim.x) {
-        const int v = y[l];
-        wrong |= v < 0 || v >= C || v == blank;
-    }
-    if (__syncthreads_or(malformed || wrong)) {
+    int64_t n = r, block = 0;  // utterance r of one tensor, or row o * N + n over the output blocks
+    if (a.descs) n = (int)(r % a.N), block = r / a.N;
+    CtcRow row;
+    if (!ctc_open_row(a, r, n, block, row)) {
         if (tid == 0) a.status[r] = -2;
         return;
     }
+    const float* lp = row.lp;
+    const int64_t st = row.st;
+    const int blank = row.blank, len = row.len, L = row.L;
+    const int32_t* y = row.y;
     int32_t* paths = a.paths + r * a.T;
     if (len == 0) {
         if (L == 0)
@@ -73,7 +56,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignAr
 
     const int S = 2 * L + 1;
     float* row0 = state_rows;
-    float* row1 = state_rows + a.strips * AW;
+    float* row1 = state_rows + a.strips * CTC_WAVE;
     uint4* moves = a.workspace + r * a.strips * a.t_pad;
 
     bool live[SPW], skip[SPW];
@@ -82,9 +65,9 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignAr
     uint4 word[STAGED ? SPW : 1];  // STAGED: lane c holds the strip's moves of frame 64 q + c until 64 frames are stored at once
 #pragma unroll
     for (int k = 0; k < SPW; ++k) {
-        const int strip = k * waves + wave, i = strip * AW + lane;
-        live[k] = strip * AW < S;  // wave-uniform
-        const bool mine = i < S;   // the lanes past S compute cells nobody reads
+        const int strip = k * waves + wave, i = strip * CTC_WAVE + lane;
+        live[k] = strip * CTC_WAVE < S;  // wave-uniform
+        const bool mine = i < S;         // the lanes past S compute cells nobody reads
         lab[k] = blank, skip[k] = false, x0[k] = neg_inf;
         if (STAGED) word[k] = make_uint4(0, 0, 0, 0);
 #pragma unroll
@@ -110,11 +93,11 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignAr
             if (t < len) {
                 const float* prev = (t & 1) ? row0 : row1;
                 float* cur = (t & 1) ? row1 : row0;
-                const int c = t & (AW - 1);
+                const int c = t & (CTC_WAVE - 1);
 #pragma unroll
                 for (int k = 0; k < SPW; ++k) {
                     if (live[k]) {
-                        const int strip = k * waves + wave, i = strip * AW + lane;
+                        const int strip = k * waves + wave, i = strip * CTC_WAVE + lane;
                         const float x1 = i >= 1 ? prev[i - 1] : neg_inf;
                         const float x2 = skip[k] ? prev[i - 2] : neg_inf;
                         float best = x0[k];
@@ -128,7 +111,8 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignAr
                         const uint4 both = make_uint4((uint32_t)b1, (uint32_t)(b1 >> 32), (uint32_t)b2, (uint32_t)(b2 >> 32));
                         if (STAGED) {
                             if (lane == c) word[k] = both;
-                            if ((c == AW - 1 || t == len - 1) && lane <= c) moves[strip * a.t_pad + (t - c) + lane] = word[k];
+                            if ((c == CTC_WAVE - 1 || t == len - 1) && lane <= c)
+                                moves[strip * a.t_pad + (t - c) + lane] = word[k];
                         } else if (lane == c) {
                             moves[strip * a.t_pad + t] = both;
                         }
@@ -158,8 +142,8 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignAr
     __syncthreads();
     if (wave == 0) {
         int after_block = -1;  // the state of the frame after the 64 being walked
-        for (int tb = (len - 1) & ~(AW - 1); tb >= 0; tb -= AW) {
-            const int hi = min(len - 1, tb + AW - 1);
+        for (int tb = (len - 1) & ~(CTC_WAVE - 1); tb >= 0; tb -= CTC_WAVE) {
+            const int hi = min(len - 1, tb + CTC_WAVE - 1);
             int mine = -1, loaded = -1;
             uint4 w = make_uint4(0, 0, 0, 0);
             for (int t = hi; t >= tb; --t) {
@@ -212,7 +196,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * AW) void ctc_align_kernel(AlignAr
 }  // namespace
 
 bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
-    const size_t strips = (size_t)((2 * max_target + 1 + AW - 1) / AW), t_pad = (size_t)((T + AW - 1) / AW * AW);
+    const size_t strips = (size_t)ctc_strips(max_target), t_pad = (size_t)((T + CTC_WAVE - 1) / CTC_WAVE * CTC_WAVE);
     size_t total = 0;
     if (__builtin_mul_overflow((size_t)rows, strips, &total) || __builtin_mul_overflow(total, t_pad, &total) ||
         __builtin_mul_overflow(total, sizeof(uint4), &total))
@@ -222,20 +206,10 @@ bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size
 }
 
 void launch_ctc_align(AlignArgs a, hipStream_t s) {
-    a.strips = (2 * a.max_target + 1 + AW - 1) / AW;
-    a.t_pad = ((int64_t)a.T + AW - 1) / AW * AW;
-    const int waves = min(ALIGN_MAX_WAVES, a.strips);
-    const int per_wave = (a.strips + waves - 1) / waves;
-    const dim3 grid((unsigned)a.rows), block(waves * AW);
-    const size_t lds = (size_t)a.strips * AW * 2 * sizeof(float);
-    if (per_wave <= 1)
-        hipLaunchKernelGGL((ctc_align_kernel<1, 4, true>), grid, block, lds, s, a);
-    else if (per_wave <= 2)
-        hipLaunchKernelGGL((ctc_align_kernel<2, 4, true>), grid, block, lds, s, a);
-    else if (per_wave <= 4)
-        hipLaunchKernelGGL((ctc_align_kernel<4, 2, true>), grid, block, lds, s, a);
-    else
-        hipLaunchKernelGGL((ctc_align_kernel<8, 1, false>), grid, block, lds, s, a);
+    a.strips = (int)ctc_strips(a.max_target);
+    a.t_pad = ((int64_t)a.T + CTC_WAVE - 1) / CTC_WAVE * CTC_WAVE;
+    ctc_launch_rows(a, s, ctc_align_kernel<1, 4, true>, ctc_align_kernel<2, 4, true>, ctc_align_kernel<4, 2, true>,
+                    ctc_align_kernel<8, 1, false>);
 }
 
 }  // namespace amx

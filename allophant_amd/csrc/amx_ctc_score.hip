@@ -23,7 +23,7 @@ namespace amx {
 
 namespace {
 
-constexpr int SW = 64;  // wave size, states per strip
+#include "amx_ctc_row.inc"
 
 // log(exp(x0) + exp(x1) + exp(x2)); -inf when all three are (the maximum is replaced by 0, so nothing subtracts -inf from -inf)
 __device__ __forceinline__ float lse3(float x0, float x1, float x2) {
@@ -33,39 +33,21 @@ __device__ __forceinline__ float lse3(float x0, float x1, float x2) {
 }
 
 template <int SPW, int PF>
-__global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreArgs a) {
+__global__ __launch_bounds__(ALIGN_MAX_WAVES * CTC_WAVE) void ctc_score_kernel(ScoreArgs a) {
     extern __shared__ float state_rows[];  // two rows of a.strips * 64 states
     const int64_t r = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & (SW - 1), wave = tid / SW, waves = blockDim.x / SW;
+    const int tid = threadIdx.x, lane = tid & (CTC_WAVE - 1), wave = tid / CTC_WAVE, waves = blockDim.x / CTC_WAVE;
     const float neg_inf = -INFINITY;
 
-    // the row's emissions, lp[t][c] at lp[t * st + c]
-    const float* lp;
-    int64_t st;
-    int C, blank;
-    const int n = (int)((r / a.candidates) % a.N);
-    if (a.descs) {
-        const OutDesc d = a.descs[r / ((int64_t)a.N * a.candidates)];
-        lp = a.emissions + (int64_t)a.T * a.N * d.prefix + (int64_t)n * d.C;
-        st = (int64_t)a.N * d.C, C = d.C, blank = 0;
-    } else {
-        lp = a.emissions + n * a.stride_n;
-        st = a.stride_t, C = a.C, blank = a.blank;
-    }
-    const int len = a.frame_lengths[n];
-    const int lb = a.target_offsets[r], le = a.target_offsets[r + 1], id_count = a.target_offsets[a.rows];
-    const bool malformed = len < 0 || len > a.T || lb < 0 || le < lb || le > id_count || le - lb > a.max_target;
-    const int L = malformed ? 0 : le - lb;
-    const int32_t* y = a.target_ids + lb;
-    int wrong = 0;
-    for (int l = tid; l < L; l += blockDim.x) {
-        const int v = y[l];
-        wrong |= v < 0 || v >= C || v == blank;
-    }
-    if (__syncthreads_or(malformed || wrong)) {
+    CtcRow row;  // row (o * N + n) * G + g over the output blocks, or n * G + g over one tensor
+    if (!ctc_open_row(a, r, (int)((r / a.candidates) % a.N), r / ((int64_t)a.N * a.candidates), row)) {
         if (tid == 0) a.status[r] = -2;
         return;
     }
+    const float* lp = row.lp;
+    const int64_t st = row.st;
+    const int len = row.len, L = row.L;
+    const int32_t* y = row.y;
     if (len == 0) {
         if (tid == 0) {
             a.log_likelihood[r] = L ? neg_inf : 0.0f;
@@ -74,7 +56,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
         return;
     }
 
-    const int S = 2 * L + 1, W = a.strips * SW;
+    const int S = 2 * L + 1, W = a.strips * CTC_WAVE;
     float* row0 = state_rows;
     float* row1 = state_rows + W;
     float* forward = a.workspace + r * a.T * W;  // a[t][i] at forward[t * W + i]
@@ -84,10 +66,10 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
     float own[SPW], ahead[SPW][PF];
 #pragma unroll
     for (int k = 0; k < SPW; ++k) {
-        const int strip = k * waves + wave, i = strip * SW + lane;
-        live[k] = strip * SW < S;  // wave-uniform
-        mine[k] = i < S;           // the lanes past S compute cells nobody reads
-        lab[k] = blank, skip[k] = false, own[k] = i == 0 ? 0.0f : neg_inf;
+        const int strip = k * waves + wave, i = strip * CTC_WAVE + lane;
+        live[k] = strip * CTC_WAVE < S;  // wave-uniform
+        mine[k] = i < S;                 // the lanes past S compute cells nobody reads
+        lab[k] = row.blank, skip[k] = false, own[k] = i == 0 ? 0.0f : neg_inf;
 #pragma unroll
         for (int j = 0; j < PF; ++j) ahead[k][j] = 0.0f;
         if (live[k]) {
@@ -113,7 +95,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
 #pragma unroll
                 for (int k = 0; k < SPW; ++k) {
                     if (live[k]) {
-                        const int i = (k * waves + wave) * SW + lane;
+                        const int i = (k * waves + wave) * CTC_WAVE + lane;
                         const float x1 = i >= 1 ? prev[i - 1] : neg_inf;
                         const float x2 = skip[k] ? prev[i - 2] : neg_inf;
                         own[k] = lse3(own[k], x1, x2) + ahead[k][j];
@@ -144,7 +126,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
     float occupancy[SPW], position[SPW], score[SPW];
 #pragma unroll
     for (int k = 0; k < SPW; ++k) {
-        const int i = (k * waves + wave) * SW + lane;
+        const int i = (k * waves + wave) * CTC_WAVE + lane;
         own[k] = i == S - 1 ? 0.0f : neg_inf;
         occupancy[k] = position[k] = score[k] = 0.0f;
         // from here `skip` is the backward skip, to state i + 2
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
 #pragma unroll
                 for (int k = 0; k < SPW; ++k) {
                     if (live[k]) {
-                        const int i = (k * waves + wave) * SW + lane;
+                        const int i = (k * waves + wave) * CTC_WAVE + lane;
                         const float x1 = i + 1 < S ? next[i + 1] : neg_inf;
                         const float x2 = skip[k] ? next[i + 2] : neg_inf;
                         const float e = ahead[k][j], av = before[k][j];
@@ -201,7 +183,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
 
 #pragma unroll
     for (int k = 0; k < SPW; ++k) {
-        const int i = (k * waves + wave) * SW + lane;
+        const int i = (k * waves + wave) * CTC_WAVE + lane;
         if (mine[k] && (i & 1)) {
             const int64_t at = r * a.max_target + (i >> 1);
             a.occupancy[at] = occupancy[k];
@@ -218,7 +200,7 @@ __global__ __launch_bounds__(ALIGN_MAX_WAVES * SW) void ctc_score_kernel(ScoreAr
 }  // namespace
 
 bool ctc_score_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
-    const size_t states = (size_t)((2 * max_target + 1 + SW - 1) / SW * SW);
+    const size_t states = (size_t)(ctc_strips(max_target) * CTC_WAVE);
     size_t total = 0;
     if (__builtin_mul_overflow((size_t)rows, (size_t)T, &total) || __builtin_mul_overflow(total, states, &total) ||
         __builtin_mul_overflow(total, sizeof(float), &total))
@@ -228,19 +210,8 @@ bool ctc_score_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size
 }
 
 void launch_ctc_score(ScoreArgs a, hipStream_t s) {
-    a.strips = (2 * a.max_target + 1 + SW - 1) / SW;
-    const int waves = min(ALIGN_MAX_WAVES, a.strips);
-    const int per_wave = (a.strips + waves - 1) / waves;
-    const dim3 grid((unsigned)a.rows), block(waves * SW);
-    const size_t lds = (size_t)a.strips * SW * 2 * sizeof(float);
-    if (per_wave <= 1)
-        hipLaunchKernelGGL((ctc_score_kernel<1, 4>), grid, block, lds, s, a);
-    else if (per_wave <= 2)
-        hipLaunchKernelGGL((ctc_score_kernel<2, 4>), grid, block, lds, s, a);
-    else if (per_wave <= 4)
-        hipLaunchKernelGGL((ctc_score_kernel<4, 2>), grid, block, lds, s, a);
-    else
-        hipLaunchKernelGGL((ctc_score_kernel<8, 1>), grid, block, lds, s, a);
+    a.strips = (int)ctc_strips(a.max_target);
+    ctc_launch_rows(a, s, ctc_score_kernel<1, 4>, ctc_score_kernel<2, 4>, ctc_score_kernel<4, 2>, ctc_score_kernel<8, 1>);
 }
 
 }  // namespace amx

@@ -22,7 +22,7 @@ namespace amx {
 
 namespace {
 
-constexpr int SW = 64;           // wave size, states per strip
+constexpr int SW = CTC_WAVE;     // wave size, states per strip
 constexpr int SEARCH_WAVES = 4;  // rows (consecutive queries of one utterance) per workgroup
 
 // wave_shr:1 -- lane l receives lane l - 1's `v`, lane 0 receives `lane0`

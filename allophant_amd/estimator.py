@@ -27,6 +27,7 @@ import torch
 from torch import Tensor
 
 from . import alignment as _alignment
+from . import ctc as _ctc
 from . import lib as _lib
 from . import scoring as _scoring
 from . import search as _search
@@ -571,29 +572,52 @@ class Estimator:
             outputs[d.name.decode()] = flat[d.offset: d.offset + T.value * N * c].view(T.value, N, c)
         return Predictions(outputs, out_lengths.to(batch.lengths.device), flat, (N, L), self._inventory)
 
-    def greedy_decode_device(self, predictions: Predictions) -> "Decoded":
-        """On-device ``GreedyCTCDecoder`` over every output of ``predictions`` (reference predictions.py:194-207 applied
-        per classifier as in run.py:767-774); the result stays in HBM (``Decoded``: no host copy, no synchronisation), which
-        is what the data-parallel path gathers instead of log-probabilities (``parallel.gather_decoded``)."""
+    def _predictions_call(self, predictions: Predictions):
+        """What every call over the output buffer of ``predictions`` starts with: selects their inventory and returns the
+        output names, ``N``, ``L``, ``T``, ``O``, the host int64 frame lengths with their pointer, and the stream."""
         if predictions._flat is None or predictions._geometry is None:
             raise ValueError("predictions were not produced by this estimator")
         N, L = predictions._geometry
         if predictions._inventory is not None:
-            # the block layout depends on the inventory size: decode under the inventory of THESE predictions, whatever
+            # the block layout depends on the inventory size: run under the inventory of THESE predictions, whatever
             # later predict() calls selected (a cached inventory is re-selected without device work)
             self._set_inventory(predictions._inventory)
         names = list(predictions.outputs.keys())
         T = next(iter(predictions.outputs.values())).shape[0]
+        frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
+        return (names, N, L, T, len(names), frame_lengths, C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)),
+                torch.cuda.current_stream(self._device).cuda_stream)
+
+    @staticmethod
+    def _target_rows(predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]], names: List[str], N: int,
+                     verb: str) -> List[Sequence[int]]:
+        """``targets`` (output name -> one row per utterance) as rows ``o * N + n``, empty for an output without an entry;
+        ``verb`` is what the caller does with them ("align", "score")."""
+        unknown = [name for name in targets if name not in predictions.outputs]
+        if unknown:
+            raise ValueError(f"targets name the outputs {unknown}, the predictions hold {names}")
+        rows: List[Sequence[int]] = []
+        for name in names:
+            per_utterance = targets.get(name)
+            if per_utterance is not None and len(per_utterance) != N:
+                raise ValueError(f"output {name!r}: {len(per_utterance)} target rows for {N} utterances")
+            rows += [[] for _ in range(N)] if per_utterance is None else list(per_utterance)
+        if N == 0:
+            raise ValueError(f"predictions hold no utterances: nothing to {verb}")
+        return rows
+
+    def greedy_decode_device(self, predictions: Predictions) -> "Decoded":
+        """On-device ``GreedyCTCDecoder`` over every output of ``predictions`` (reference predictions.py:194-207 applied
+        per classifier as in run.py:767-774); the result stays in HBM (``Decoded``: no host copy, no synchronisation), which
+        is what the data-parallel path gathers instead of log-probabilities (``parallel.gather_decoded``)."""
+        names, N, L, T, O, _, lengths_pointer, stream = self._predictions_call(predictions)
         with torch.cuda.device(self._device):
-            tokens = torch.empty(len(names), N, T, dtype=torch.int64, device=self._device)
+            tokens = torch.empty(O, N, T, dtype=torch.int64, device=self._device)
             timesteps = torch.empty_like(tokens)
-            counts = torch.empty(len(names), N, dtype=torch.int32, device=self._device)
-            scores = torch.empty(len(names), N, dtype=torch.float32, device=self._device)
-            stream = torch.cuda.current_stream(self._device).cuda_stream
-            frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
+            counts = torch.empty(O, N, dtype=torch.int32, device=self._device)
+            scores = torch.empty(O, N, dtype=torch.float32, device=self._device)
             code = self._lib.amx_greedy_ctc(
-                self._handle, C.c_void_p(predictions._flat.data_ptr()),
-                C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)), N, L, C.c_void_p(tokens.data_ptr()),
+                self._handle, C.c_void_p(predictions._flat.data_ptr()), lengths_pointer, N, L, C.c_void_p(tokens.data_ptr()),
                 C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(scores.data_ptr()),
                 C.c_void_p(stream))
             _lib.check(self._lib, self._handle, code)
@@ -609,15 +633,8 @@ class Estimator:
         """On-device ``BeamCTCDecoder`` (reference predictions.py:210-235) over every output of ``predictions``, as the
         reference's decode loop applies it per classifier (run.py:767-785).  ``exp_emissions`` (default, like upstream's
         ``log_emissions.exp()``) adds probabilities; False adds the log-probabilities as given.  The result stays in HBM."""
-        if predictions._flat is None or predictions._geometry is None:
-            raise ValueError("predictions were not produced by this estimator")
+        names, N, L, T, O, _, lengths_pointer, stream = self._predictions_call(predictions)
         _check_beam(beam_width, n_best)
-        N, L = predictions._geometry
-        if predictions._inventory is not None:
-            self._set_inventory(predictions._inventory)  # decode under the inventory of THESE predictions (greedy_decode_device)
-        names = list(predictions.outputs.keys())
-        T = next(iter(predictions.outputs.values())).shape[0]
-        O = len(names)
         with torch.cuda.device(self._device):
             size = C.c_size_t()
             _lib.check(self._lib, None, self._lib.amx_beam_ctc_workspace(beam_width, O * N, T, C.byref(size)))
@@ -627,11 +644,8 @@ class Estimator:
             counts = torch.empty(O, N, n_best, dtype=torch.int32, device=self._device)
             scores = torch.empty(O, N, n_best, dtype=torch.float64, device=self._device)
             hyp_counts = torch.empty(O, N, dtype=torch.int32, device=self._device)
-            stream = torch.cuda.current_stream(self._device).cuda_stream
-            frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
             code = self._lib.amx_beam_ctc(
-                self._handle, C.c_void_p(predictions._flat.data_ptr()),
-                C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)), N, L, beam_width, n_best,
+                self._handle, C.c_void_p(predictions._flat.data_ptr()), lengths_pointer, N, L, beam_width, n_best,
                 _lib.BEAM_EXP_EMISSIONS if exp_emissions else 0, C.c_void_p(workspace.data_ptr()), size.value,
                 C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()),
                 C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
@@ -647,36 +661,15 @@ class Estimator:
         """On-device CTC forced alignment (``amx_ctc_align``) of every output of ``predictions`` against ``targets``: output
         name -> one class-index sequence per utterance (``alignment.label_targets`` builds them from labels).  An output
         without an entry is aligned against nothing and left out of ``Aligned.present``.  The result stays in HBM."""
-        if predictions._flat is None or predictions._geometry is None:
-            raise ValueError("predictions were not produced by this estimator")
-        N, L = predictions._geometry
-        if predictions._inventory is not None:
-            self._set_inventory(predictions._inventory)  # align under the inventory of THESE predictions (greedy_decode_device)
-        names = list(predictions.outputs.keys())
-        unknown = [name for name in targets if name not in predictions.outputs]
-        if unknown:
-            raise ValueError(f"targets name the outputs {unknown}, the predictions hold {names}")
-        rows: List[Sequence[int]] = []
-        for name in names:
-            per_utterance = targets.get(name)
-            if per_utterance is not None and len(per_utterance) != N:
-                raise ValueError(f"output {name!r}: {len(per_utterance)} target rows for {N} utterances")
-            rows += [[] for _ in range(N)] if per_utterance is None else list(per_utterance)
-        if N == 0:
-            raise ValueError("predictions hold no utterances: nothing to align")
-        offsets, ids, counts = _alignment.pack_targets(rows)
+        names, N, L, T, O, frame_lengths, lengths_pointer, stream = self._predictions_call(predictions)
+        offsets, ids, counts = _alignment.pack_targets(self._target_rows(predictions, targets, names, N, "align"))
         max_target = max(counts)
-        T = next(iter(predictions.outputs.values())).shape[0]
-        O = len(names)
         with torch.cuda.device(self._device):
             meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(self._device)
             b = _alignment.allocate(self._lib, O * N, T, max_target, self._device)
-            stream = torch.cuda.current_stream(self._device).cuda_stream
-            frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
             code = self._lib.amx_ctc_align(
-                self._handle, C.c_void_p(predictions._flat.data_ptr()), C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)),
-                N, L, C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 4 * (O * N + 1)), max_target, *b.pointers(),
-                C.c_void_p(stream))
+                self._handle, C.c_void_p(predictions._flat.data_ptr()), lengths_pointer, N, L, C.c_void_p(meta.data_ptr()),
+                C.c_void_p(meta.data_ptr() + 4 * (O * N + 1)), max_target, *b.pointers(), C.c_void_p(stream))
             _lib.check(self._lib, self._handle, code)
         return _alignment.Aligned(names, [name for name in names if name in targets], b.paths.view(O, N, T),
                                   b.frame_scores.view(O, N, T), b.spans.view(O, N, max_target, 2),
@@ -689,22 +682,18 @@ class Estimator:
         alignment exists)."""
         return self.align_device(predictions, targets).alignments()
 
-    def _score_call(self, predictions: Predictions, candidates: int, meta: Tensor, max_target: int, posteriors: bool):
-        """``amx_ctc_score`` over every output of ``predictions``: ``meta`` holds the device int32 offsets
-        ``[O * N * candidates + 1]`` followed by the ids.  Returns the buffers, the host frame lengths and (O, N, T)."""
-        N, L = predictions._geometry
-        T = next(iter(predictions.outputs.values())).shape[0]
-        O = len(predictions.outputs)
+    def _score_call(self, call, predictions: Predictions, candidates: int, meta: Tensor, max_target: int, posteriors: bool):
+        """``amx_ctc_score`` over every output of ``predictions`` (``call`` is their ``_predictions_call``): ``meta`` holds the
+        device int32 offsets ``[O * N * candidates + 1]`` followed by the ids.  Returns the buffers."""
+        _, N, L, T, O, _, lengths_pointer, stream = call
         rows = O * N * candidates
         b = _scoring.allocate(self._lib, rows, T, max_target, self._device, posteriors)
-        stream = torch.cuda.current_stream(self._device).cuda_stream
-        frame_lengths = predictions.lengths.detach().to("cpu", torch.int64).contiguous()
         code = self._lib.amx_ctc_score(
-            self._handle, C.c_void_p(predictions._flat.data_ptr()), C.cast(frame_lengths.data_ptr(), C.POINTER(C.c_int64)),
-            N, L, candidates, C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 4 * (rows + 1)), max_target,
-            *b.pointers(), C.c_void_p(stream))
+            self._handle, C.c_void_p(predictions._flat.data_ptr()), lengths_pointer, N, L, candidates,
+            C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 4 * (rows + 1)), max_target, *b.pointers(),
+            C.c_void_p(stream))
         _lib.check(self._lib, self._handle, code)
-        return b, frame_lengths.tolist(), (O, N, T)
+        return b
 
     def score_device(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]],
                      posteriors: bool = False) -> "_scoring.Scored":
@@ -713,29 +702,14 @@ class Estimator:
         occupancy, position and score sums (with ``posteriors`` also the state posteriors of every frame).  An output without
         an entry is scored against nothing and left out of ``Scored.present``.  The result stays in HBM, leading shape
         ``[O, N, 1]``."""
-        if predictions._flat is None or predictions._geometry is None:
-            raise ValueError("predictions were not produced by this estimator")
-        N, _ = predictions._geometry
-        if predictions._inventory is not None:
-            self._set_inventory(predictions._inventory)  # score under the inventory of THESE predictions (greedy_decode_device)
-        names = list(predictions.outputs.keys())
-        unknown = [name for name in targets if name not in predictions.outputs]
-        if unknown:
-            raise ValueError(f"targets name the outputs {unknown}, the predictions hold {names}")
-        rows: List[Sequence[int]] = []
-        for name in names:
-            per_utterance = targets.get(name)
-            if per_utterance is not None and len(per_utterance) != N:
-                raise ValueError(f"output {name!r}: {len(per_utterance)} target rows for {N} utterances")
-            rows += [[] for _ in range(N)] if per_utterance is None else list(per_utterance)
-        if N == 0:
-            raise ValueError("predictions hold no utterances: nothing to score")
-        offsets, ids, counts = _scoring.pack_targets(rows)
+        call = names, N, _, T, O, frame_lengths, _, _ = self._predictions_call(predictions)
+        offsets, ids, counts = _scoring.pack_targets(self._target_rows(predictions, targets, names, N, "score"))
         max_target = max(counts)
         with torch.cuda.device(self._device):
             meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(self._device)
-            b, lengths, (O, _, T) = self._score_call(predictions, 1, meta, max_target, posteriors)
-        return _scoring.scored(b, (O, N, 1), T, max_target, names, [name for name in names if name in targets], lengths, counts)
+            b = self._score_call(call, predictions, 1, meta, max_target, posteriors)
+        return _scoring.scored(b, (O, N, 1), T, max_target, names, [name for name in names if name in targets],
+                               frame_lengths.tolist(), counts)
 
     def score(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]], posteriors: bool = False
               ) -> Dict[str, List[Optional["_scoring.Score"]]]:
@@ -747,12 +721,8 @@ class Estimator:
         """The exact log P(hypothesis | emissions) of every hypothesis of ``beam_decoded`` (``beam_decode_device`` of these
         predictions), whose own scores are those of a pruned search, and the softmax over each n-best list.  The targets are
         packed on the device from ``tokens`` / ``counts``; the host synchronises once, for their sizes."""
-        if predictions._flat is None or predictions._geometry is None:
-            raise ValueError("predictions were not produced by this estimator")
-        N, _ = predictions._geometry
-        if predictions._inventory is not None:
-            self._set_inventory(predictions._inventory)
-        names = list(predictions.outputs.keys())
+        call = self._predictions_call(predictions)
+        names, N = call[:2]
         O, Nb, B, T = beam_decoded.tokens.shape
         if beam_decoded.names != names or Nb != N or N == 0:
             raise ValueError("beam_decoded does not belong to these predictions")
@@ -768,7 +738,7 @@ class Estimator:
             ids = beam_decoded.tokens.reshape(-1, T)[row, at - (ends - counts)[row]]
             meta = torch.cat([torch.zeros(1, dtype=torch.int64, device=self._device), ends, ids,
                               torch.zeros(1, dtype=torch.int64, device=self._device)]).to(torch.int32)
-            b, _, _ = self._score_call(predictions, B, meta, max_target, False)
+            b = self._score_call(call, predictions, B, meta, max_target, False)
             ll = torch.where(present, b.log_likelihood.view(O, N, B), torch.full((), -math.inf, device=self._device))
             return _scoring.Rescored(names, ll, torch.nan_to_num(torch.softmax(ll, -1), nan=0.0), b.status.view(O, N, B))
 
@@ -905,29 +875,18 @@ class GreedyCTCDecoder:
 
 def greedy_ctc_decode(log_emissions: Tensor, lengths: Tensor, blank_index: int = 0) -> List[List[CTCHypothesis]]:
     """``GreedyCTCDecoder.__call__`` (reference predictions.py:194-207) through ``amx_greedy_ctc_emissions``."""
-    if log_emissions.dim() != 3:
-        raise ValueError("log_emissions must be [N, T, C]")
-    if log_emissions.device.type != "cuda":
-        raise RuntimeError("allophant_amd decodes on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "decodes")
     lib = _lib.load()
     device = log_emissions.device
-    if log_emissions.dtype != torch.float32:
-        log_emissions = log_emissions.float()
-    if log_emissions.stride(2) != 1:
-        log_emissions = log_emissions.contiguous()
-    N, T, Cn = log_emissions.shape
-    if not 0 <= blank_index < Cn:
-        raise ValueError("blank_index out of range")
+    _ctc.check_classes(Cn, blank_index)
     if N == 0:
         return []
     with torch.cuda.device(device):
-        frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        frame_lengths, index, stream = _ctc.frame(log_emissions, lengths.detach())  # (the lengths are required here)
         tokens = torch.empty(N, T, dtype=torch.int64, device=device)
         timesteps = torch.empty_like(tokens)
         counts = torch.empty(N, dtype=torch.int32, device=device)
         scores = torch.empty(N, dtype=torch.float32, device=device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        index = device.index if device.index is not None else torch.cuda.current_device()
         code = lib.amx_greedy_ctc_emissions(
             index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
             C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, C.c_void_p(tokens.data_ptr()),
@@ -981,27 +940,15 @@ def beam_ctc_decode(log_emissions: Tensor, lengths: Optional[Tensor], beam_width
                     exp_emissions: bool = True) -> List[List[CTCHypothesis]]:
     """``BeamCTCDecoder.__call__`` (reference predictions.py:231-233) through ``amx_beam_ctc_emissions``; ``exp_emissions``
     False adds the values as given instead of their exponentials."""
-    if log_emissions.dim() != 3:
-        raise ValueError("log_emissions must be [N, T, C]")
-    if log_emissions.device.type != "cuda":
-        raise RuntimeError("allophant_amd decodes on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "decodes")
     _check_beam(beam_width, n_best)
     lib = _lib.load()
     device = log_emissions.device
-    if log_emissions.dtype != torch.float32:
-        log_emissions = log_emissions.float()
-    if log_emissions.stride(2) != 1:
-        log_emissions = log_emissions.contiguous()
-    N, T, Cn = log_emissions.shape
-    if not 0 <= blank_index < Cn:
-        raise ValueError("blank_index out of range")
+    _ctc.check_classes(Cn, blank_index)
     if N == 0:
         return []
     with torch.cuda.device(device):
-        if lengths is None:
-            frame_lengths = torch.full((N,), T, dtype=torch.int32, device=device)
-        else:
-            frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        frame_lengths, index, stream = _ctc.frame(log_emissions, lengths)
         size = C.c_size_t()
         _lib.check(lib, None, lib.amx_beam_ctc_workspace(beam_width, N, T, C.byref(size)))
         workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
@@ -1010,8 +957,6 @@ def beam_ctc_decode(log_emissions: Tensor, lengths: Optional[Tensor], beam_width
         counts = torch.empty(N, n_best, dtype=torch.int32, device=device)
         scores = torch.empty(N, n_best, dtype=torch.float64, device=device)
         hyp_counts = torch.empty(N, dtype=torch.int32, device=device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        index = device.index if device.index is not None else torch.cuda.current_device()
         code = lib.amx_beam_ctc_emissions(
             index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
             C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, beam_width, n_best,

@@ -17,8 +17,8 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import torch
 from torch import Tensor
 
-from . import lib as _lib
-from .alignment import frame_stride
+from . import ctc as _ctc, lib as _lib
+from .ctc import frame_stride, pack_targets  # noqa: F401  (part of this module's interface)
 
 SCORE_MAX_TARGET = _lib.SCORE_MAX_TARGET
 
@@ -117,24 +117,6 @@ class Rescored(NamedTuple):
     status: Tensor
 
 
-def pack_targets(rows: Sequence[Sequence[int]], utterances: Optional[int] = None, candidates: int = 1
-                 ) -> Tuple[Tensor, Tensor, List[int]]:
-    """Target rows as the C ABI takes them: int32 offsets ``[R + 1]``, int32 ids, and the rows' lengths (host tensors).  With
-    ``utterances`` the row count must be ``utterances * candidates`` (row ``n * candidates + g``)."""
-    if candidates < 1:
-        raise ValueError("candidates must be at least 1")
-    if utterances is not None and len(rows) != utterances * candidates:
-        raise ValueError(f"{len(rows)} target rows for {utterances} emission rows x {candidates} candidates")
-    counts = [len(row) for row in rows]
-    if counts and max(counts) > SCORE_MAX_TARGET:
-        raise ValueError(f"at most {SCORE_MAX_TARGET} targets per row on the device, got {max(counts)}")
-    offsets = torch.zeros(len(rows) + 1, dtype=torch.int32)
-    if rows:
-        offsets[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0).to(torch.int32)
-    ids = torch.tensor([int(v) for row in rows for v in row], dtype=torch.int32)
-    return offsets, ids, counts
-
-
 class _Buffers(NamedTuple):
     workspace: Tensor
     size: int
@@ -155,11 +137,11 @@ def allocate(lib, rows: int, T: int, max_target: int, device, posteriors: bool =
     """The workspace and outputs of ``rows`` rows of ``T`` frames (at least one element each, so every pointer is valid)."""
     size = C.c_size_t()
     _lib.check(lib, None, lib.amx_ctc_score_workspace(rows, T, max_target, C.byref(size)))
-    empty = lambda *shape: torch.empty(max(1, math.prod(shape)), dtype=torch.float32, device=device)[:math.prod(shape)].view(*shape)  # noqa: E731
+    empty = lambda *shape: _ctc.empty(*shape, dtype=torch.float32, device=device)  # noqa: E731
     return _Buffers(torch.empty(max(1, size.value), dtype=torch.uint8, device=device), size.value, empty(rows),
                     empty(rows, max_target), empty(rows, max_target), empty(rows, max_target),
                     empty(rows, T, 2 * max_target + 1) if posteriors else None,
-                    torch.empty(max(1, rows), dtype=torch.int32, device=device)[:rows])
+                    _ctc.empty(rows, dtype=torch.int32, device=device))
 
 
 def scored(b: _Buffers, leading: Tuple[int, ...], T: int, max_target: int, names, present, lengths, counts) -> Scored:
@@ -176,36 +158,20 @@ def ctc_score(log_emissions: Tensor, lengths: Optional[Tensor], targets: Union[S
     strides with a unit class stride, read in place) via ``amx_ctc_score_emissions``.  ``targets``: one int sequence per row
     ``n * candidates + g``, or a padded ``[N * candidates, max_len]`` tensor with its lengths ``(padded, target_lengths)``.
     Returns the device form (leading shape ``[N, candidates]``); ``Scored.scores()`` fetches it."""
-    if log_emissions.dim() != 3:
-        raise ValueError("log_emissions must be [N, T, C]")
-    if log_emissions.device.type != "cuda":
-        raise RuntimeError("allophant_amd scores on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "scores")
     lib = _lib.load()
     device = log_emissions.device
-    if log_emissions.dtype != torch.float32:
-        log_emissions = log_emissions.float()
-    if log_emissions.stride(2) != 1:
-        log_emissions = log_emissions.contiguous()
-    N, T, Cn = log_emissions.shape
     if isinstance(targets, tuple) and len(targets) == 2 and isinstance(targets[0], Tensor):
         padded, target_lengths = targets[0].cpu().tolist(), [int(v) for v in targets[1].cpu().tolist()]
         targets = [row[:k] for row, k in zip(padded, target_lengths)]
-    if Cn < 2:
-        raise ValueError("scoring needs at least 2 classes")
-    if not 0 <= blank_index < Cn:
-        raise ValueError("blank_index out of range")
+    _ctc.check_classes(Cn, blank_index, "scoring")
     offsets, ids, counts = pack_targets(targets, N, candidates)
     max_target = max(counts, default=0)
     with torch.cuda.device(device):
-        if lengths is None:
-            frame_lengths = torch.full((N,), T, dtype=torch.int32, device=device)
-        else:
-            frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        frame_lengths, index, stream = _ctc.frame(log_emissions, lengths)
         b = allocate(lib, N * candidates, T, max_target, device, posteriors)
         if N:
             meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(device)  # (never an empty tensor)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            index = device.index if device.index is not None else torch.cuda.current_device()
             code = lib.amx_ctc_score_emissions(
                 index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
                 C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, candidates, C.c_void_p(meta.data_ptr()),

@@ -11,15 +11,15 @@ the same frames: at most 0, and 0 exactly when the argmax path over the span rea
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from . import lib as _lib
-from .alignment import frame_stride, output_targets
+from . import ctc as _ctc, lib as _lib
+from .alignment import output_targets
+from .ctc import frame_stride
 
 SEARCH_MAX_QUERY = _lib.SEARCH_MAX_QUERY
 
@@ -107,11 +107,7 @@ def pack_queries(queries: Sequence[Sequence[int]], classes: int, blank_index: in
         for v in query:
             if not 0 <= int(v) < classes or int(v) == blank_index:
                 raise ValueError(f"query {q}: id {int(v)} is the blank or outside the {classes} classes")
-    offsets = torch.zeros(len(queries) + 1, dtype=torch.int32)
-    if queries:
-        offsets[1:] = torch.cumsum(torch.tensor([len(query) for query in queries], dtype=torch.int64), 0).to(torch.int32)
-    ids = torch.tensor([int(v) for query in queries for v in query], dtype=torch.int32)
-    return offsets, ids
+    return _ctc.pack_targets(queries)[:2]
 
 
 def ctc_search(log_emissions: Tensor, lengths: Optional[Tensor], queries: Sequence[Sequence[int]], blank_index: int = 0,
@@ -120,33 +116,19 @@ def ctc_search(log_emissions: Tensor, lengths: Optional[Tensor], queries: Sequen
     stride, read in place) for every query (a sequence of class indices) via ``amx_ctc_search_emissions``.  With ``curves``
     the result also holds, per frame, the best score of an occurrence ending there and its start (``Found.hits``).
     ``ValueError`` names a malformed query."""
-    if log_emissions.dim() != 3:
-        raise ValueError("log_emissions must be [N, T, C]")
-    if log_emissions.device.type != "cuda":
-        raise RuntimeError("allophant_amd searches on an MI355X only (log_emissions must be a cuda tensor); there is no CPU fallback")
+    log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "searches")
     lib = _lib.load()
     device = log_emissions.device
-    if log_emissions.dtype != torch.float32:
-        log_emissions = log_emissions.float()
-    if log_emissions.stride(2) != 1:
-        log_emissions = log_emissions.contiguous()
-    N, T, Cn = log_emissions.shape
-    if Cn < 2:
-        raise ValueError("the search needs at least 2 classes")
-    if not 0 <= blank_index < Cn:
-        raise ValueError("blank_index out of range")
+    _ctc.check_classes(Cn, blank_index, "the search")
     offsets, ids = pack_queries(queries, Cn, blank_index)
     Q = len(queries)
     if N * Q * T >= 2 ** 31:
         raise ValueError(f"utterances x queries x frames must be below 2^31, got {N} x {Q} x {T}")
     with torch.cuda.device(device):
-        if lengths is None:
-            frame_lengths = torch.full((N,), T, dtype=torch.int32, device=device)
-        else:
-            frame_lengths = lengths.detach().to(device=device, dtype=torch.int32).contiguous()
-            if frame_lengths.shape != (N,):
-                raise ValueError(f"{frame_lengths.numel()} lengths for {N} emission rows")
-        empty = lambda *shape, dtype: torch.empty(max(1, math.prod(shape)), dtype=dtype, device=device)[:math.prod(shape)].view(*shape)  # noqa: E731
+        frame_lengths, index, stream = _ctc.frame(log_emissions, lengths)
+        if frame_lengths.shape != (N,):
+            raise ValueError(f"{frame_lengths.numel()} lengths for {N} emission rows")
+        empty = lambda *shape, dtype: _ctc.empty(*shape, dtype=dtype, device=device)  # noqa: E731
         scores, spans, status = empty(N, Q, dtype=torch.float32), empty(N, Q, 2, dtype=torch.int32), empty(N, Q, dtype=torch.int32)
         end_scores = empty(N, Q, T, dtype=torch.float32) if curves else None
         end_starts = empty(N, Q, T, dtype=torch.int32) if curves else None
@@ -161,8 +143,6 @@ def ctc_search(log_emissions: Tensor, lengths: Optional[Tensor], queries: Sequen
         _lib.check(lib, None, lib.amx_ctc_search_workspace(N, Q, T, max_query, C.byref(size)))
         workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
         meta = torch.cat([offsets, ids]).to(device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        index = device.index if device.index is not None else torch.cuda.current_device()
         pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         code = lib.amx_ctc_search_emissions(
             index, pointer(log_emissions), log_emissions.stride(0), log_emissions.stride(1), pointer(frame_lengths), N, T, Cn,
