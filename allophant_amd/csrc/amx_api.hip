@@ -6,6 +6,7 @@
 #include "../../include/allophant_amx_align.h"
 #include "../../include/allophant_amx_score.h"
 #include "../../include/allophant_amx_search.h"
+#include "../../include/allophant_amx_restrict.h"
 #include "../../include/allophant_amx_resample.h"
 #include "../../include/allophant_amx_edit.h"
 #include "amx_common.h"
@@ -2547,6 +2548,45 @@ extern "C" int amx_ctc_search_emissions(int device, const float* emissions, int6
     a.best_scores = best_scores, a.best_spans = best_spans, a.status = status, a.end_scores = end_scores, a.end_starts = end_starts;
     launch_ctc_search(a, (hipStream_t)stream);
     return ctc_launched(nullptr, "search");
+}
+
+// =================================================================================================================
+// restriction of a union-inventory output to each utterance's language
+// =================================================================================================================
+namespace {
+// false when the offset of the last element of a [T, N, C] tensor with these strides is not below 2^63
+bool restrict_extent(int64_t T, int64_t N, int64_t C, int64_t stride_t, int64_t stride_n) {
+    int64_t a = 0, b = 0;
+    return !__builtin_mul_overflow(T - 1, stride_t, &a) && !__builtin_mul_overflow(N - 1, stride_n, &b) &&
+           !__builtin_add_overflow(a, b, &a) && !__builtin_add_overflow(a, C - 1, &a);
+}
+}  // namespace
+
+extern "C" int amx_restrict_outputs(int device, const float* src, int64_t stride_t, int64_t stride_n, int C,
+                                    const int32_t* frame_lengths, const int32_t* language_ids, const uint64_t* member_bits,
+                                    int n_lang, int N, int64_t T, uint32_t flags, float* out, int64_t out_stride_t,
+                                    int64_t out_stride_n, int32_t* status, void* stream) {
+    if (C < 2 || C > AMX_RESTRICT_MAX_CLASSES)
+        return fail(nullptr, AMX_EINVAL, "classes must be 2 to " + std::to_string(AMX_RESTRICT_MAX_CLASSES) + ", got " + std::to_string(C));
+    if (n_lang < 1) return fail(nullptr, AMX_EINVAL, "n_lang must be at least 1, got " + std::to_string(n_lang));
+    if (flags & ~AMX_RESTRICT_NORMALIZE) return fail(nullptr, AMX_EINVAL, "unknown restriction flags");
+    if (N < 0 || T < 0 || stride_t < 0 || stride_n < 0 || out_stride_t < 0 || out_stride_n < 0)
+        return fail(nullptr, AMX_EINVAL, "negative restriction geometry");
+    if (N == 0 || T == 0) return AMX_OK;
+    int64_t rows = 0;
+    if (__builtin_mul_overflow((int64_t)N, T, &rows) || rows > (int64_t)UINT32_MAX)
+        return fail(nullptr, AMX_EINVAL, "N * T must be below 2^32");
+    if (!restrict_extent(T, N, C, stride_t, stride_n) || !restrict_extent(T, N, C, out_stride_t, out_stride_n))
+        return fail(nullptr, AMX_EINVAL, "restriction tensor extent must be below 2^63");
+    if (!src || !out || !frame_lengths || !language_ids || !member_bits || !status) return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    RestrictArgs a{};
+    a.src = src, a.stride_t = stride_t, a.stride_n = stride_n;
+    a.out = out, a.out_stride_t = out_stride_t, a.out_stride_n = out_stride_n;
+    a.frame_lengths = frame_lengths, a.language_ids = language_ids, a.member_bits = member_bits, a.status = status;
+    a.T = T, a.N = N, a.C = C, a.n_lang = n_lang, a.normalize = (flags & AMX_RESTRICT_NORMALIZE) != 0;
+    launch_restrict(a, (hipStream_t)stream);
+    return ctc_launched(nullptr, "restriction");
 }
 
 // =================================================================================================================

@@ -572,6 +572,23 @@ struct SearchArgs {
 bool ctc_search_workspace_bytes(int64_t N, int64_t T, size_t* bytes);
 void launch_ctc_search(SearchArgs a, hipStream_t s);
 
+// Restriction of a union-inventory output to each utterance's language (amx_restrict.hip), one wave per (t, n) row of a
+// [T, N, C] tensor read and written with element strides (stride_t, stride_n, 1): contract in
+// include/allophant_amx_restrict.h.  Limits (checked by the caller): 2 <= C <= 65535, n_lang >= 1, 0 < N * T < 2^32.
+struct RestrictArgs {
+    const float* src;
+    int64_t stride_t, stride_n;
+    float* out;  // may be `src`, with equal strides
+    int64_t out_stride_t, out_stride_n;
+    const int32_t *frame_lengths, *language_ids;
+    const uint64_t* member_bits;  // [n_lang, (C + 63) / 64]
+    int32_t* status;
+    int64_t T;
+    int N, C, n_lang;
+    bool normalize;
+};
+void launch_restrict(RestrictArgs a, hipStream_t s);
+
 // allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
 // strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]
 // of ent_p / ent_w and the accumulator start col_init[l * Q1 + q]; language_ids int32 [N] in [0, n_lang)

@@ -98,6 +98,9 @@ class Predictions:
     # assembled by parallel.gather_flat_predictions: one status word per rank (device tensor; non-zero = that rank reported a
     # range error -- AMX_ERANGE -- with its shard).  Left on the device so that the gather never synchronises the host.
     _status: Optional[Tensor] = dataclasses.field(default=None, repr=False, compare=False)
+    # set by Estimator.predict_languages: (int32 device language id per utterance, the LanguageInventories); the composed
+    # output is then the union inventory's, each utterance restricted to its own language (-inf elsewhere)
+    _languages: Optional[Tuple[Tensor, Any]] = dataclasses.field(default=None, repr=False, compare=False)
 
     def __len__(self) -> int:
         return len(self.lengths)
@@ -572,6 +575,50 @@ class Estimator:
             outputs[d.name.decode()] = flat[d.offset: d.offset + T.value * N * c].view(T.value, N, c)
         return Predictions(outputs, out_lengths.to(batch.lengths.device), flat, (N, L), self._inventory)
 
+    def predict_languages(self, batch: Batch, inventories, languages: Optional[Sequence] = None, log_probabilities: bool = True,
+                          _no_graph: bool = False) -> Predictions:
+        """``predict`` for a batch that mixes languages (composition models; upstream splits such a batch by language and
+        predicts each part under its own inventory, run.py:712-713, 742-753): ONE pass under ``inventories.union_tfi``, then
+        ``amx_restrict_outputs`` in place on the composed output (``"phoneme"``; ``"phone"`` shares its block) on the same
+        stream.  ``inventories`` is a ``LanguageInventories``; ``languages`` holds one name (or dense id) per utterance, and
+        left as ``None``, ``batch.language_ids`` are dense indices into ``inventories.languages``.
+
+        For utterance ``n`` of language ``l`` the composed output then holds, at the union classes ``inventories.columns(l)``,
+        what upstream's ``predict(part, tfi_l)`` holds (the log-softmax over the language's own classes, or with
+        ``log_probabilities=False`` the raw logits), and -inf at every other class; frames beyond ``lengths`` are 0 as ever,
+        and every other output is untouched.  ``greedy_decode``, ``align``, ``score``, ``rescore_device``, ``search``,
+        ``Evaluator`` (with the union as its inventory) and ``hypothesis_symbols`` (with ``union_symbols``) take such
+        predictions unchanged and speak union class indices (``LanguageInventories.to_language_indices`` gives upstream's);
+        ``beam_decode`` decodes each language over its own classes.  Not covered: the data-parallel gather of such
+        predictions."""
+        if not self._spec.get("embedding_size"):
+            raise ValueError("model has no embedding composition layer")
+        if not hasattr(self._lib, "amx_restrict_outputs"):
+            raise RuntimeError(f"{_lib.LIB_PATH} predates per-utterance inventories (amx_restrict_outputs): rebuild it")
+        ids = inventories.language_ids(batch.language_ids if languages is None else languages)
+        if ids.numel() != len(batch):
+            raise ValueError(f"{ids.numel()} languages for {len(batch)} utterances")
+        predictions = self.predict(batch, inventories.union_tfi, log_probabilities, _no_graph=_no_graph)
+        block = predictions.outputs[_spec.PHONEME]
+        T, N, classes = block.shape
+        if classes != inventories.classes:
+            raise ValueError(f"the composed output has {classes} classes, the union inventory {inventories.classes}")
+        with torch.cuda.device(self._device):
+            meta = torch.cat([predictions.lengths.detach().to("cpu", torch.int32), ids]).to(self._device)
+            status = torch.empty(max(1, N), dtype=torch.int32, device=self._device)
+            bits = inventories.device_bits(self._device)
+            code = self._lib.amx_restrict_outputs(
+                self._index, C.c_void_p(block.data_ptr()), block.stride(0), block.stride(1), classes,
+                C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 4 * N), C.c_void_p(bits.data_ptr()),
+                len(inventories.languages), N, T, _lib.RESTRICT_NORMALIZE if log_probabilities else 0,
+                C.c_void_p(block.data_ptr()), block.stride(0), block.stride(1), C.c_void_p(status.data_ptr()),
+                C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream))
+            _lib.check(self._lib, None, code)
+            stream = torch.cuda.current_stream(self._device)
+            meta.record_stream(stream), status.record_stream(stream)
+        predictions._languages = (meta[N:], inventories)
+        return predictions
+
     def _predictions_call(self, predictions: Predictions):
         """What every call over the output buffer of ``predictions`` starts with: selects their inventory and returns the
         output names, ``N``, ``L``, ``T``, ``O``, the host int64 frame lengths with their pointer, and the stream."""
@@ -650,7 +697,38 @@ class Estimator:
                 C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()),
                 C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
             _lib.check(self._lib, self._handle, code)
-        return BeamDecoded(names, tokens, timesteps, counts, scores, hyp_counts)
+        decoded = BeamDecoded(names, tokens, timesteps, counts, scores, hyp_counts)
+        if predictions._languages is not None:
+            decoded = self._beam_decode_languages(predictions, decoded, beam_width, n_best, exp_emissions)
+        return decoded
+
+    def _beam_decode_languages(self, predictions: Predictions, decoded: "BeamDecoded", beam_width: int, n_best: int,
+                               exp_emissions: bool) -> "BeamDecoded":
+        """The rest of ``beam_decode_device`` for ``predict_languages`` predictions.  Upstream hands the decoder probabilities as
+        scores, so a class of probability 0 is still a candidate, while upstream's per-language decoder does not have the
+        class at all: the composed outputs are decoded again per language, over the language's utterances and its own columns
+        of the restricted block (the emissions path), the tokens mapped back to union ids, and the rows of ``decoded``
+        replaced."""
+        ids, inventories = predictions._languages
+        ids_host = ids.cpu().tolist()
+        with torch.cuda.device(self._device):
+            lengths = predictions.lengths.to(self._device)
+            for o, name in enumerate(decoded.names):
+                if name not in (_spec.PHONEME, _spec.PHONE):
+                    continue
+                block = predictions.outputs[name]  # [T, N, C]
+                for language in sorted(set(ids_host)):
+                    columns = inventories.columns(language).to(self._device)
+                    if columns.numel() < 2:
+                        raise ValueError(f"beam search needs a phoneme in the inventory of {inventories.languages[language]!r}")
+                    own = torch.tensor([n for n, l in enumerate(ids_host) if l == language], dtype=torch.int64, device=self._device)
+                    compact = block.index_select(1, own).index_select(2, columns).transpose(0, 1).contiguous()
+                    tokens, *rest = _beam_ctc_rows(compact, lengths[own], beam_width, n_best, 0, exp_emissions)
+                    # per-language ids -> union ids (the entries past `counts` are not tokens: clamped into the table)
+                    decoded.tokens[o, own] = columns[tokens.clamp_(0, columns.numel() - 1)]
+                    for whole, piece in zip(decoded[2:], rest):
+                        whole[o, own] = piece
+        return decoded
 
     def beam_decode(self, predictions: Predictions, beam_width: int, n_best: int = 1,
                     exp_emissions: bool = True) -> Dict[str, List[List[CTCHypothesis]]]:
@@ -940,13 +1018,24 @@ def beam_ctc_decode(log_emissions: Tensor, lengths: Optional[Tensor], beam_width
                     exp_emissions: bool = True) -> List[List[CTCHypothesis]]:
     """``BeamCTCDecoder.__call__`` (reference predictions.py:231-233) through ``amx_beam_ctc_emissions``; ``exp_emissions``
     False adds the values as given instead of their exponentials."""
+    log_emissions, N, _, Cn = _ctc.emissions(log_emissions, "decodes")
+    _check_beam(beam_width, n_best)
+    _lib.load()
+    _ctc.check_classes(Cn, blank_index)
+    if N == 0:
+        return []
+    return _beam_hypotheses(*_beam_ctc_rows(log_emissions, lengths, beam_width, n_best, blank_index, exp_emissions))
+
+
+def _beam_ctc_rows(log_emissions: Tensor, lengths: Optional[Tensor], beam_width: int, n_best: int, blank_index: int,
+                   exp_emissions: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``amx_beam_ctc_emissions`` over ``[N, T, C]`` emissions, ``N >= 1``: the device tensors ``tokens`` / ``timesteps``
+    ``[N, n_best, T]``, ``counts`` / ``scores`` ``[N, n_best]`` and ``hyp_counts`` ``[N]``."""
     log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "decodes")
     _check_beam(beam_width, n_best)
     lib = _lib.load()
     device = log_emissions.device
     _ctc.check_classes(Cn, blank_index)
-    if N == 0:
-        return []
     with torch.cuda.device(device):
         frame_lengths, index, stream = _ctc.frame(log_emissions, lengths)
         size = C.c_size_t()
@@ -964,7 +1053,7 @@ def beam_ctc_decode(log_emissions: Tensor, lengths: Optional[Tensor], beam_width
             C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()),
             C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
         _lib.check(lib, None, code)
-        return _beam_hypotheses(tokens, timesteps, counts, scores, hyp_counts)
+        return tokens, timesteps, counts, scores, hyp_counts
 
 
 def _ctc_decoder(categories, beam_width: int = 1, n_best: int = 1):

@@ -63,6 +63,10 @@ SCORE_MAX_TARGET = 4095  # AMX_SCORE_MAX_TARGET
 # the CTC search entry points (include/allophant_amx_search.h; added to ABI 6, detected by name)
 SEARCH_EXPORTS = ["amx_ctc_search_workspace", "amx_ctc_search_emissions"]
 SEARCH_MAX_QUERY = 256  # AMX_SEARCH_MAX_QUERY
+# the inventory-restriction entry point (include/allophant_amx_restrict.h; added to ABI 6, detected by name)
+RESTRICT_EXPORTS = ["amx_restrict_outputs"]
+RESTRICT_NORMALIZE = 1  # AMX_RESTRICT_NORMALIZE
+RESTRICT_MAX_CLASSES = 65535  # AMX_RESTRICT_MAX_CLASSES
 
 
 def dep_output_layer(i: int) -> int:
@@ -207,6 +211,9 @@ def load() -> C.CDLL:
         lib.amx_ctc_search_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, vp, vp, i32, i64, vp, C.c_size_t, vp, vp, vp,
                                                  vp, vp, vp]
         lib.amx_ctc_search_emissions.restype = i32
+    if hasattr(lib, "amx_restrict_outputs"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_restrict_outputs.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, i32, i32, i64, C.c_uint32, vp, i64, i64, vp, vp]
+        lib.amx_restrict_outputs.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
