@@ -11,7 +11,8 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "levensthein_statistics", "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations",
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
            "levensthein_matrix", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "Score", "Scored",
-           "Rescored", "ctc_score", "Found", "Hit", "ctc_search", "pick_hits", "query_targets"]
+           "Rescored", "ctc_score", "Found", "Hit", "ctc_search", "pick_hits", "query_targets", "LongPlan", "plan_windows",
+           "gather_windows", "stitch_windows"]
 __version__ = "0.1.0"
 
 
@@ -40,4 +41,8 @@ def __getattr__(name):
         from . import search
 
         return getattr(search, name)
+    if name in ("LongPlan", "plan_windows", "gather_windows", "stitch_windows"):
+        from . import longform
+
+        return getattr(longform, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -7,6 +7,7 @@
 #include "../../include/allophant_amx_score.h"
 #include "../../include/allophant_amx_search.h"
 #include "../../include/allophant_amx_restrict.h"
+#include "../../include/allophant_amx_long.h"
 #include "../../include/allophant_amx_resample.h"
 #include "../../include/allophant_amx_edit.h"
 #include "amx_common.h"
@@ -2587,6 +2588,57 @@ extern "C" int amx_restrict_outputs(int device, const float* src, int64_t stride
     a.T = T, a.N = N, a.C = C, a.n_lang = n_lang, a.normalize = (flags & AMX_RESTRICT_NORMALIZE) != 0;
     launch_restrict(a, (hipStream_t)stream);
     return ctc_launched(nullptr, "restriction");
+}
+
+// =================================================================================================================
+// long recordings as windows: the plan, the gather of the windows' audio, the stitch of their kept frames
+// =================================================================================================================
+extern "C" int amx_long_plan(const int64_t* lengths, int R, int64_t window, int32_t context, const int32_t* conv_kernel,
+                             const int32_t* conv_stride, int n_conv, amx_long_window* windows, int64_t capacity,
+                             int64_t* n_windows, int64_t* frames) {
+    const std::string err = long_plan(lengths, R, window, context, conv_kernel, conv_stride, n_conv, windows, capacity, n_windows, frames);
+    return err.empty() ? AMX_OK : fail(nullptr, AMX_EINVAL, err);
+}
+
+extern "C" int amx_long_gather(int device, const float* audio, int64_t stride, const int64_t* lengths, int R,
+                               const amx_long_window* windows, int n, int64_t hop, int64_t L_out, float* batch,
+                               int32_t* status, void* stream) {
+    int64_t extent = 0;
+    if (n < 0 || R < 0 || L_out < 0 || stride < 0) return fail(nullptr, AMX_EINVAL, "negative gather geometry");
+    if (hop < 1 || hop >= ((int64_t)1 << 31)) return fail(nullptr, AMX_EINVAL, "hop must be 1 to 2^31 - 1 samples");
+    if (__builtin_mul_overflow((int64_t)R, stride, &extent) || __builtin_mul_overflow((int64_t)n, L_out, &extent))
+        return fail(nullptr, AMX_EINVAL, "gather extent must be below 2^63");
+    if (n == 0) return AMX_OK;
+    if (!audio || !lengths || !windows || !batch || !status) return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_long_gather(audio, stride, lengths, R, windows, n, hop, L_out, batch, status, (hipStream_t)stream);
+    return ctc_launched(nullptr, "gather");
+}
+
+extern "C" int amx_long_stitch(int device, const float* src, int64_t src_T, int n, const amx_long_window* windows,
+                               const amx_long_block* blocks, int n_blocks, float* dst, int R, int64_t dst_T,
+                               int32_t* status, void* stream) {
+    if (n < 0 || R < 0 || src_T < 0 || dst_T < 0 || n_blocks < 0) return fail(nullptr, AMX_EINVAL, "negative stitch geometry");
+    if (n_blocks > AMX_LONG_MAX_BLOCKS)
+        return fail(nullptr, AMX_EINVAL, "at most " + std::to_string(AMX_LONG_MAX_BLOCKS) + " blocks per call, got " + std::to_string(n_blocks));
+    if (n_blocks > 0 && !blocks) return fail(nullptr, AMX_EINVAL, "null buffer");
+    const int64_t LIMIT = (int64_t)1 << 62;
+    for (int b = 0; b < n_blocks; ++b) {
+        const amx_long_block& k = blocks[b];
+        if (k.classes < 1 || k.src_offset < 0 || k.dst_offset < 0) return fail(nullptr, AMX_EINVAL, "a block needs classes >= 1 and offsets >= 0");
+        if (src_T >= ((int64_t)1 << 31) || src_T * k.classes >= ((int64_t)1 << 31))
+            return fail(nullptr, AMX_EINVAL, "src_T * classes must be below 2^31");
+        int64_t a = 0, d = 0;
+        if (__builtin_mul_overflow(src_T * k.classes, (int64_t)n, &a) ||
+            __builtin_add_overflow(a, k.src_offset, &a) || a >= LIMIT || __builtin_mul_overflow(dst_T, (int64_t)R * k.classes, &d) ||
+            __builtin_add_overflow(d, k.dst_offset, &d) || d >= LIMIT)
+            return fail(nullptr, AMX_EINVAL, "stitch block extent must be below 2^62 floats");
+    }
+    if (n == 0 || n_blocks == 0) return AMX_OK;
+    if (!src || !windows || !dst || !status) return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_long_stitch(src, src_T, n, windows, blocks, n_blocks, dst, R, dst_T, status, (hipStream_t)stream);
+    return ctc_launched(nullptr, "stitch");
 }
 
 // =================================================================================================================

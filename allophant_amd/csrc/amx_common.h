@@ -7,6 +7,8 @@
 
 struct amx_resample_geometry;  // include/allophant_amx_resample.h
 struct amx_resample_row;
+struct amx_long_window;  // include/allophant_amx_long.h
+struct amx_long_block;
 
 namespace amx {
 
@@ -588,6 +590,17 @@ struct RestrictArgs {
     bool normalize;
 };
 void launch_restrict(RestrictArgs a, hipStream_t s);
+
+// Long recordings as windows (amx_long.hip): contract in include/allophant_amx_long.h.  long_plan is host code ("" or the
+// reason the arguments are refused; *n_windows is written either way); the launchers expect checked arguments: n >= 1 rows,
+// hop < 2^31, and for the stitch 1 <= n_blocks <= 64, classes >= 1 and src_T * classes < 2^31 in every block.
+std::string long_plan(const int64_t* lengths, int R, int64_t window, int32_t context, const int32_t* conv_kernel,
+                      const int32_t* conv_stride, int n_conv, amx_long_window* windows, int64_t capacity, int64_t* n_windows,
+                      int64_t* frames);
+void launch_long_gather(const float* audio, int64_t stride, const int64_t* lengths, int R, const amx_long_window* windows, int n,
+                        int64_t hop, int64_t L_out, float* batch, int32_t* status, hipStream_t s);
+void launch_long_stitch(const float* src, int64_t src_T, int n, const amx_long_window* windows, const amx_long_block* blocks,
+                        int n_blocks, float* dst, int R, int64_t dst_T, int32_t* status, hipStream_t s);
 
 // allophone layer (amx_allophone.hip): language-specific phoneme outputs [T, N, Q1] from phone outputs [T, N, P1] read with element
 // strides (stride_t, stride_n, 1); per (language, q) column the unmasked entries col_ptr[l * Q1 + q] .. col_ptr[l * Q1 + q + 1]

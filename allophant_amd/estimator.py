@@ -472,6 +472,30 @@ class Estimator:
         _lib.check(self._lib, self._handle, code)
         self._inventory = tfi_cpu
 
+    def _select_inventory(self, target_feature_indices: Optional[Tensor]) -> None:
+        """What ``predict`` does with its ``target_feature_indices``: a composition model runs under them, or under the training
+        inventory when there are none."""
+        if self._spec.get("embedding_size"):
+            if target_feature_indices is None:
+                if self._training_inventory is None:
+                    raise ValueError(
+                        "composition models need `target_feature_indices`: the training inventory table is a "
+                        "non-persistent buffer upstream (acoustic_model.py:214-221); restore the estimator from a checkpoint "
+                        "that embeds its attribute table, or call set_training_inventory()")
+                target_feature_indices = self._training_inventory
+            self._set_inventory(target_feature_indices)
+
+    def _output_layout(self, N: int, L: int):
+        """``amx_output_layout`` of a batch of ``N`` rows padded to ``L`` samples under the selected inventory: the output
+        descriptors, the frames ``T`` and the floats of the flat buffer."""
+        n_out, T, total = C.c_int(), C.c_int64(), C.c_int64()
+        code = self._lib.amx_output_layout(self._handle, N, L, None, C.byref(n_out), C.byref(T), C.byref(total))
+        _lib.check(self._lib, self._handle, code)
+        descs = (_lib.AmxOutputDesc * n_out.value)()
+        code = self._lib.amx_output_layout(self._handle, N, L, descs, C.byref(n_out), C.byref(T), C.byref(total))
+        _lib.check(self._lib, self._handle, code)
+        return descs, int(T.value), int(total.value)
+
     def predict(self, batch: Batch, target_feature_indices: Optional[Tensor] = None, log_probabilities: bool = True,
                 _keep_hidden: bool = False, _timing: bool = False, _no_pack: bool = False, _no_graph: bool = False,
                 _out: Optional[Tensor] = None) -> Predictions:
@@ -482,15 +506,7 @@ class Estimator:
         Safe by default: the reference computes in fp32; here an activation beyond the range of the fp16 planes turns into
         non-finite logits.  Such a batch raises ``FloatingPointError`` from the first ``predict`` / ``synchronize`` issued after
         the offending pass has finished on the GPU (no host synchronisation is added: see ``amx_forward``)."""
-        if self._spec.get("embedding_size"):
-            if target_feature_indices is None:
-                if self._training_inventory is None:
-                    raise ValueError(
-                        "composition models need `target_feature_indices`: the training inventory table is a "
-                        "non-persistent buffer upstream (acoustic_model.py:214-221); restore the estimator from a checkpoint "
-                        "that embeds its attribute table, or call set_training_inventory()")
-                target_feature_indices = self._training_inventory
-            self._set_inventory(target_feature_indices)
+        self._select_inventory(target_feature_indices)
         audio = batch.audio_features
         if audio.dim() != 2:
             raise ValueError("audio_features must be [N, L]")
@@ -503,20 +519,13 @@ class Estimator:
         if N > 0 and int(lengths.max()) != L and not (padded and int(lengths.max()) <= L):
             raise ValueError("the batch must be padded to exactly max(lengths) (reference utils.py:62-63, acoustic_model.py:765-767)")
         with torch.cuda.device(self._device):
-            n_out = C.c_int()
-            T = C.c_int64()
-            total = C.c_int64()
-            code = self._lib.amx_output_layout(self._handle, N, L, None, C.byref(n_out), C.byref(T), C.byref(total))
-            _lib.check(self._lib, self._handle, code)
-            descs = (_lib.AmxOutputDesc * n_out.value)()
-            code = self._lib.amx_output_layout(self._handle, N, L, descs, C.byref(n_out), C.byref(T), C.byref(total))
-            _lib.check(self._lib, self._handle, code)
+            descs, T, total = self._output_layout(N, L)
             if _out is not None:
-                if _out.dtype != torch.float32 or _out.device != self._device or _out.numel() < total.value or not _out.is_contiguous():
+                if _out.dtype != torch.float32 or _out.device != self._device or _out.numel() < total or not _out.is_contiguous():
                     raise ValueError("_out must be a contiguous fp32 buffer on the estimator's device with room for every output")
-                flat = _out.view(-1)[: total.value]
+                flat = _out.view(-1)[: total]
             else:
-                flat = torch.empty(total.value, dtype=torch.float32, device=self._device)
+                flat = torch.empty(total, dtype=torch.float32, device=self._device)
             out_lengths = torch.empty(N, dtype=torch.int64)
             flags = 0 if log_probabilities else _lib.FLAG_RAW_LOGITS
             if _keep_hidden:
@@ -548,7 +557,7 @@ class Estimator:
                 for lo in range(0, N, n_max):
                     hi = min(N, lo + n_max)
                     n = hi - lo
-                    part_total = sum(T.value * n * c for c in blocks.values())
+                    part_total = sum(T * n * c for c in blocks.values())
                     part = torch.empty(part_total, dtype=torch.float32, device=self._device)
                     part_lengths = torch.empty(n, dtype=torch.int64)
                     slice_lengths = lengths[lo:hi].contiguous()  # named: must outlive the call that reads its storage
@@ -561,19 +570,99 @@ class Estimator:
                     out_lengths[lo:hi] = part_lengths
                     src = 0
                     for offset, c in blocks.items():  # blocks in output order: offsets ascend with the part's own
-                        flat[offset: offset + T.value * N * c].view(T.value, N, c)[:, lo:hi] = \
-                            part[src: src + T.value * n * c].view(T.value, n, c)
-                        src += T.value * n * c
+                        flat[offset: offset + T * N * c].view(T, N, c)[:, lo:hi] = \
+                            part[src: src + T * n * c].view(T, n, c)
+                        src += T * n * c
                     part.record_stream(torch.cuda.current_stream(self._device))
             # keep `audio` alive until the asynchronous kernels have consumed it
             flat.record_stream(torch.cuda.current_stream(self._device))
             audio.record_stream(torch.cuda.current_stream(self._device))
-        self._geom = (N, int(T.value))
+        self._geom = (N, T)
         outputs: Dict[str, Tensor] = {}
         for d in descs:
             c = d.classes
-            outputs[d.name.decode()] = flat[d.offset: d.offset + T.value * N * c].view(T.value, N, c)
+            outputs[d.name.decode()] = flat[d.offset: d.offset + T * N * c].view(T, N, c)
         return Predictions(outputs, out_lengths.to(batch.lengths.device), flat, (N, L), self._inventory)
+
+    def predict_long(self, batch: Batch, target_feature_indices: Optional[Tensor] = None, log_probabilities: bool = True,
+                     window_seconds: float = 10.0, context_seconds: float = 1.0, batch_windows: int = 32,
+                     _no_graph: bool = False) -> Predictions:
+        """``predict`` for recordings of any length up to 2^20 frames (5.8 h), as HF's CTC pipeline does it with
+        ``chunk_length_s`` / ``stride_length_s``: every recording of the padded batch ``[R, Lmax]`` is cut into windows of
+        ``int(window_seconds * sample_rate)`` samples that overlap by twice the context of
+        ``int(context_seconds * sample_rate) // hop`` frames (``longform.plan_windows``; the last window of a recording is
+        right-aligned, not short).  The windows of all recordings run through ``predict`` in slices of at most ``batch_windows``
+        rows, and each window's frames between its contexts -- at the ends of a recording, up to the end -- are copied into the
+        recording's output.  A slice is gathered (``amx_long_gather``), predicted and stitched (``amx_long_stitch``) on the
+        current stream without a host synchronisation, in one fixed pair of device buffers: equal slices replay one recorded
+        graph.
+
+        The result is an ordinary ``Predictions`` of the whole batch (layout of ``amx_output_layout(R, Lmax)``, ``lengths`` the
+        recordings' frames, zeros beyond them; a recording below the receptive field has length 0): ``greedy_decode``,
+        ``beam_decode``, ``align``, ``score``, ``search`` and ``Evaluator`` take it unchanged (``search`` keeps its
+        ``N * Q * T < 2^31`` limit).  Recordings that each fit one window, at most ``batch_windows`` of them, give the bits of
+        ``predict(batch)``.
+
+        What a window cannot see: ``do_normalize`` normalises each window on its own samples, as it does each utterance the
+        model was trained on; a time-layer head attends within its window; and a model that is sensitive to padding (group-norm
+        extractor, no attention mask) sees less than one hop of it, in a recording's last window only.  The defaults are HF's
+        customary proportions, not a measurement.  Not covered: the data-parallel gather of such predictions and
+        ``predict_languages`` on long rows."""
+        from . import longform
+
+        self._select_inventory(target_feature_indices)
+        audio = batch.audio_features
+        if audio.dim() != 2:
+            raise ValueError("audio_features must be [N, L]")
+        audio = audio.to(self._device, torch.float32).contiguous()
+        lengths = batch.lengths.detach().to("cpu", torch.int64).contiguous()
+        R, Lmax = audio.shape
+        if lengths.numel() != R:
+            raise ValueError("lengths must have one entry per utterance")
+        if R > 0 and int(lengths.max()) != Lmax and not (getattr(batch, "_padded", False) and int(lengths.max()) <= Lmax):
+            raise ValueError("the batch must be padded to exactly max(lengths) (reference utils.py:62-63, acoustic_model.py:765-767)")
+        if batch_windows < 1:
+            raise ValueError(f"batch_windows must be at least 1, got {batch_windows}")
+        window = int(window_seconds * self.sample_rate)
+        plan = longform.plan_windows(lengths.tolist(), self._spec, window, int(context_seconds * self.sample_rate) // math.prod(
+            self._spec["conv_stride"]))
+        W = len(plan)
+        with torch.cuda.device(self._device):
+            descs, T, total = self._output_layout(R, Lmax)  # (raises for a batch without a frame, and past 2^20 frames)
+            if W == 0:  # (a padded batch: Lmax holds a frame, no recording does)
+                raise ValueError("utterances are shorter than the receptive field of the feature extractor")
+            rows = min(int(batch_windows), int(self._lib.amx_max_utterances(self._handle, window)))
+            if rows < 1:
+                raise ValueError(f"windows of {window} samples are too long for one forward pass")
+            rows = min(rows, W)
+            samples = torch.from_numpy(plan.windows[:, longform.SAMPLES].astype("int64"))
+            longest = int(samples.max())
+            flat = torch.zeros(total, dtype=torch.float32, device=self._device)
+            window_audio = torch.empty(rows * longest, dtype=torch.float32, device=self._device)
+            window_out = torch.empty(self._output_layout(rows, longest)[2], dtype=torch.float32, device=self._device)
+            windows = torch.from_numpy(plan.windows).to(self._device)
+            device_lengths = lengths.to(self._device)
+            status = torch.empty(2, W, dtype=torch.int32, device=self._device)
+            where = {d.name: d.offset for d in descs}
+            for lo in range(0, W, rows):
+                hi = min(W, lo + rows)
+                part = Batch(window_audio[: (hi - lo) * int(samples[lo:hi].max())].view(hi - lo, -1), samples[lo:hi].contiguous(),
+                             torch.zeros(hi - lo, dtype=torch.long))
+                part._padded = True
+                longform.gather_windows(audio, device_lengths, windows[lo:hi], plan.hop, part.audio_features, status[0, lo:hi])
+                piece = self.predict(part, target_feature_indices, log_probabilities, _no_graph=_no_graph, _out=window_out)
+                # the blocks of the slice against those of the batch, by name ("phone" shares the block of "phoneme")
+                blocks = {(o.storage_offset(), where[name.encode()], o.shape[2]) for name, o in piece.outputs.items()}
+                src_T = next(iter(piece.outputs.values())).shape[0]
+                longform.stitch_windows(window_out, src_T, windows[lo:hi], sorted(blocks), flat, R, T, status[1, lo:hi])
+            stream = torch.cuda.current_stream(self._device)
+            for t in (audio, window_audio, window_out, windows, device_lengths, status):
+                t.record_stream(stream)
+        outputs: Dict[str, Tensor] = {}
+        for d in descs:
+            outputs[d.name.decode()] = flat[d.offset: d.offset + T * R * d.classes].view(T, R, d.classes)
+        frames = torch.from_numpy(plan.frames.copy()).to(batch.lengths.device)
+        return Predictions(outputs, frames, flat, (R, Lmax), self._inventory)
 
     def predict_languages(self, batch: Batch, inventories, languages: Optional[Sequence] = None, log_probabilities: bool = True,
                           _no_graph: bool = False) -> Predictions:

@@ -67,6 +67,11 @@ SEARCH_MAX_QUERY = 256  # AMX_SEARCH_MAX_QUERY
 RESTRICT_EXPORTS = ["amx_restrict_outputs"]
 RESTRICT_NORMALIZE = 1  # AMX_RESTRICT_NORMALIZE
 RESTRICT_MAX_CLASSES = 65535  # AMX_RESTRICT_MAX_CLASSES
+# the long-recording entry points (include/allophant_amx_long.h; added to ABI 6, detected by name)
+LONG_EXPORTS = ["amx_long_plan", "amx_long_gather", "amx_long_stitch"]
+LONG_MAX_BLOCKS = 64  # AMX_LONG_MAX_BLOCKS
+# amx_long_window: six int32 fields, held by the binding as an int32 [W, 6] array in this order
+LONG_WINDOW_FIELDS = ("recording", "index", "start", "keep_lo", "keep_hi", "samples")
 
 
 def dep_output_layer(i: int) -> int:
@@ -98,6 +103,10 @@ class AmxTensor(C.Structure):
 
 class AmxOutputDesc(C.Structure):
     _fields_ = [("name", C.c_char * AMX_NAME_LEN), ("classes", C.c_int32), ("offset", C.c_int64)]
+
+
+class AmxLongBlock(C.Structure):
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("classes", C.c_int32)]
 
 
 class AmxResampleGeometry(C.Structure):
@@ -214,6 +223,14 @@ def load() -> C.CDLL:
     if hasattr(lib, "amx_restrict_outputs"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_restrict_outputs.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, i32, i32, i64, C.c_uint32, vp, i64, i64, vp, vp]
         lib.amx_restrict_outputs.restype = i32
+    if hasattr(lib, "amx_long_plan"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_long_plan.argtypes = [C.POINTER(i64), i32, i64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp, i64,
+                                      C.POINTER(i64), C.POINTER(i64)]
+        lib.amx_long_plan.restype = i32
+        lib.amx_long_gather.argtypes = [i32, vp, i64, vp, i32, vp, i32, i64, i64, vp, vp, vp]
+        lib.amx_long_gather.restype = i32
+        lib.amx_long_stitch.argtypes = [i32, vp, i64, i32, vp, C.POINTER(AmxLongBlock), i32, vp, i32, i64, vp, vp]
+        lib.amx_long_stitch.restype = i32
     lib.amx_check_finite.argtypes = [vp, vp, C.POINTER(i64)]
     lib.amx_check_finite.restype = i32
     lib.amx_greedy_ctc.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp]
