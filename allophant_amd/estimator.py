@@ -926,7 +926,9 @@ class Estimator:
         return self.search_device(predictions, queries, output).best()
 
     def debug_fetch(self, what: str, index: int = 0) -> Tensor:
-        """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors."""
+        """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors.  Without the flag a pass
+        still hands out ``"hidden"`` i where a classifier reads ``OUTPUT_i`` and, for the pre-LN encoder, the final one, in the
+        [N, T] layout whatever rows the pass ran on (frames beyond an utterance of rows packed early: zeros)."""
         code_of = {"conv": 0, "hidden": 1, "logits": 2}
         n_t = self._last_geometry()
         if what == "conv":

@@ -14,6 +14,8 @@ oracle.  The oracle's dtype-generic helpers are used as they are.
                                                                     hidden_states[layers] does) and post-LN
   heads   hidden[layers] (+ hidden[i])   -> logits, log-probs       projections, composition, dependency concatenation with
                                                                     softmax, time-layer heads, log-softmax
+  entry   audio [N, L]                   -> hidden[0]               normalisation + conv + front   } what a pass without the keep
+  tail    hidden[layers - 1] (+ taps)    -> logits, log-probs       the last layer + heads         } flag leaves to look at
 
 Products (the names ``Evaluation(drop=(name, "lo_x" | "lo_w"))`` takes): ``conv1`` .. ``conv6`` and ``pos_conv`` as implicit
 GEMMs, ``feature_projection``, per layer ``q_proj k_proj v_proj qk pv out_proj ffn1 ffn2``, per classifier ``<name>.linear``,
@@ -300,6 +302,23 @@ def heads_stage(hidden: Dict[int, Tensor], frame_lengths: Tensor, state: Dict[st
     return logits, {k: F.log_softmax(v, -1) for k, v in logits.items()}
 
 
+# ----------------------------------------------------------------------------------------------------------------------------
+# combined stages: what a pass WITHOUT the keep flag leaves to look at (tests/test_gpu_stage_production.py)
+# ----------------------------------------------------------------------------------------------------------------------------
+def entry_stage(audio: Tensor, lengths: Tensor, frame_lengths: Tensor, state: Dict[str, Tensor], spec: Dict[str, Any],
+                ev: Evaluation) -> Tensor:
+    """audio [N, L] -> hidden[0]: normalisation, conv and front in one (such a pass does not keep the conv output)"""
+    return front_stage(conv_stage(normalize(audio, lengths, spec, ev), state, spec, ev), frame_lengths, state, spec, ev)
+
+
+def tail_stage(h: Tensor, taps: Dict[int, Tensor], frame_lengths: Tensor, state: Dict[str, Tensor], spec: Dict[str, Any],
+               tfi: Optional[Tensor], category_offsets: Optional[Tensor], ev: Evaluation) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
+    """hidden[layers - 1] -> (logits, log-probabilities): the last encoder layer and the heads in one, for the post-LN encoder,
+    whose hidden[layers] such a pass does not keep.  ``taps``: the other hidden states the heads read (``OUTPUT_i``, i < layers)."""
+    last = layer_stage(h, frame_lengths, state, spec, ev, spec["layers"] - 1)
+    return heads_stage({**taps, spec["layers"]: last}, frame_lengths, state, spec, tfi, category_offsets, ev)
+
+
 def hidden_inputs(spec: Dict[str, Any]) -> List[int]:
     """the hidden states the heads read: ``layers`` (``OUTPUT``) and every ``OUTPUT_i`` named by a class"""
     wanted = {spec["layers"]}
@@ -325,8 +344,51 @@ def heads_case_spec(dependency_blanks: bool) -> Dict[str, Any]:
     return spec
 
 
+def tapped_spec(encoder: Dict[str, Any], **heads: int) -> Dict[str, Any]:
+    """The two-layer hierarchical model of the production cases: ``syllabic`` reads ``OUTPUT_0`` and the phoneme head reads
+    ``cat(OUTPUT, softmax(syllabic), softmax(long), OUTPUT_1)``, so a pass keeps every hidden state a classifier reads and
+    ``debug_fetch("hidden", i)`` hands them out without the keep flag."""
+    enc = dict(encoder, layers=2)
+    spec = S.hierarchical_spec(enc, ["syllabic", "long"], **heads)
+    spec["classes"][0]["dependencies"] = ["OUTPUT_0"]
+    spec["classes"][-1]["dependencies"] = ["OUTPUT", "syllabic", "long", "OUTPUT_1"]
+    S.validate(spec)
+    return spec
+
+
+def post_ln_tapped_spec() -> Dict[str, Any]:
+    """``tapped_spec`` at wav2vec2-base width with the post-LN encoder and the attention mask.  12 groups in the positional
+    convolution instead of 16: 64 channels per group is what the window kernel takes, and the post-LN encoder packs its rows
+    only behind that kernel."""
+    enc = S.wav2vec2_base_encoder()
+    enc.update(use_attention_mask=True, pos_groups=12)
+    return tapped_spec(enc, embedding_size=64, train_phonemes=9, n_features=5)
+
+
 def against(got, truth, frame_lengths: Sequence[int]) -> float:
     """``max_abs_valid`` of a stage's output (a tensor, or name -> tensor for the heads) against its truth"""
     if isinstance(truth, dict):
         return max(max_abs_valid(got[k], truth[k], frame_lengths) for k in truth)
     return max_abs_valid(got, truth, frame_lengths)
+
+
+def shortest_longest_and(lengths: Tensor, more: int) -> List[int]:
+    """utterance indices for the truth of a large batch: the shortest, the longest and ``more`` spread between them by length"""
+    order = torch.argsort(lengths).tolist()
+    inner = [order[(j + 1) * (len(order) - 1) // (more + 1)] for j in range(more)]
+    return sorted({order[0], order[-1], *inner})
+
+
+def judged(run, device_out, frame_lengths: Sequence[int], precision: str) -> Tuple[float, float]:
+    """One stage of a GPU case: ``run(ev)`` evaluates it from the device's input; returns (the device's error, e_emu of
+    ``precision``), both against the float64 truth over the valid frames."""
+    with torch.inference_mode():
+        truth = run(Evaluation("truth"))
+        e_emu = against(run(Evaluation(precision)), truth, frame_lengths)
+        return against(device_out, truth, frame_lengths), e_emu
+
+
+def report(name: str, precision: str, found: Dict[str, Tuple[float, float]]) -> None:
+    """the ``[stage-local]`` lines of a GPU case: per stage the device's error, e_emu and their ratio"""
+    for stage, (error, e_emu) in found.items():
+        print(f"[stage-local] {name} {precision} {stage}: device {error:.3g}  e_emu {e_emu:.3g}  ratio {error / e_emu:.2f}")
