@@ -21,7 +21,9 @@ The cases are the smallest geometries that reach each family of kernels; ``pass_
 Every case here runs ``_keep_hidden``, i.e. padded and eager, with the conv stage in its two-pass form.  What a pass without the
 flag takes instead -- packed rows, the conv extractor's per-utterance tiles, the fused pass behind the last conv layer, the
 recorded graph -- is held to the same gate by tests/test_gpu_stage_production.py (packed and padded rows are the same bits only on
-the tiny model, so the budget does not carry over by itself).
+the tiny model, so the budget does not carry over by itself).  The XLS-R 1B / 2B widths and head dimensions other than 64, whose
+attention, row-kernel, fold and positional-convolution instances no case here reaches, are held to it by
+tests/test_gpu_stage_widths.py.
 
 Not covered: the single-plane modes (``f16``, ``bf16``): no cross terms to lose; they keep their own bounds.
 """

@@ -10,7 +10,11 @@ Three things per stage (conv, front, each encoder layer, heads), from the oracle
   For XLS-R width the encoder layers are also taken the way a pass with the LayerNorm fold runs them (``layerN/fold``).
 
 Cases: XLS-R width (hidden 1024, 16 heads, FFN 4096, two layers, 2 x 3 s ragged), a tiny post-LN / group-norm model, and the tiny
-hierarchical model with time-layer heads that the GPU heads case runs.
+hierarchical model with time-layer heads that the GPU heads case runs.  For tests/test_gpu_stage_widths.py: the XLS-R 1B and 2B
+widths (``xlsr_1b``, ``xlsr_2b``: hidden 1280 / 1920, heads of 80 / 120 columns, built like the XLS-R case) and the tiny models with
+head dimensions 40, 8, 96 and 128 (``dh40`` ...: ``stage_util.HEAD_DIM_MODELS``, 5 ragged utterances of <= 1.5 s).  A (case, mode,
+stage) whose weakest lost term is below 5.0 x e_emu -- ``LISTED_FLOOR`` plus 10 % for the summation order of the BLAS -- is not
+claimed, here or on the GPU: ``stage_util.NOT_CLAIMED``.
 
 The same three things for the two combined stages that tests/test_gpu_stage_production.py judges a pass without the keep flag by:
 ``entry`` (audio -> hidden[0]) on the XLS-R and the tiny post-LN case, ``tail`` (last layer + heads of a post-LN encoder) at
@@ -49,6 +53,52 @@ NOT_DETECTABLE = {
     ("post_ln_base", "bf16x3", "tail", "q_proj", "lo_x"): 7.8,
     ("post_ln_base", "bf16x3", "tail", "q_proj", "lo_w"): 7.7,
     ("post_ln_base", "bf16x3", "tail", "k_proj", "lo_x"): 7.7,
+    # XLS-R 1B / 2B width (hidden 1280 / 1920, heads of 80 / 120 columns).  With K = 1280 / 1920 and an FFN of 5120 / 7680, e_emu
+    # of a layer on fp16 planes is 4.2e-6 ... 6.0e-6 (hidden 1024: 2.2e-6 ... 3.0e-6) while a cross term lost from a score product
+    # costs about what it did, so the attention-score products of the layers -- again only ``q_proj`` / ``k_proj`` / ``qk`` --
+    # come out at 6.0 ... 7.9 instead of 8.9 and up.  On bf16 planes the unfolded layers are at >= 20; the first folded one is at
+    # 6.0 ... 7.7, and the second folded one is not claimed at all (``stage_util.NOT_CLAIMED``).  Entries from 7.5 to 7.9 are
+    # within rounding of the condition and are listed for the same reason as the two above.
+    ("xlsr_1b", "f16x3", "layer0", "k_proj", "lo_w"): 7.6,
+    ("xlsr_1b", "f16x3", "layer0/fold", "k_proj", "lo_w"): 7.8,
+    ("xlsr_1b", "f16x3", "layer1", "q_proj", "lo_x"): 7.1,
+    ("xlsr_1b", "f16x3", "layer1", "q_proj", "lo_w"): 7.0,
+    ("xlsr_1b", "f16x3", "layer1", "k_proj", "lo_x"): 7.7,
+    ("xlsr_1b", "f16x3", "layer1", "k_proj", "lo_w"): 6.5,
+    ("xlsr_1b", "f16x3", "layer1", "qk", "lo_x"): 7.6,
+    ("xlsr_1b", "f16x3", "layer1/fold", "q_proj", "lo_x"): 7.3,
+    ("xlsr_1b", "f16x3", "layer1/fold", "q_proj", "lo_w"): 7.1,
+    ("xlsr_1b", "f16x3", "layer1/fold", "k_proj", "lo_x"): 7.9,
+    ("xlsr_1b", "f16x3", "layer1/fold", "k_proj", "lo_w"): 6.6,
+    ("xlsr_1b", "f16x3", "layer1/fold", "qk", "lo_x"): 7.7,
+    ("xlsr_1b", "bf16x3", "layer0/fold", "q_proj", "lo_x"): 7.0,
+    ("xlsr_1b", "bf16x3", "layer0/fold", "q_proj", "lo_w"): 6.1,
+    ("xlsr_1b", "bf16x3", "layer0/fold", "k_proj", "lo_w"): 6.7,
+    ("xlsr_1b", "bf16x3", "layer0/fold", "qk", "lo_x"): 7.7,
+    ("xlsr_1b", "bf16x3", "layer0/fold", "qk", "lo_w"): 7.6,
+    ("xlsr_2b", "f16x3", "layer0", "q_proj", "lo_w"): 7.5,
+    ("xlsr_2b", "f16x3", "layer0", "qk", "lo_x"): 7.2,
+    ("xlsr_2b", "f16x3", "layer0/fold", "q_proj", "lo_w"): 7.5,
+    ("xlsr_2b", "f16x3", "layer0/fold", "k_proj", "lo_x"): 7.9,
+    ("xlsr_2b", "f16x3", "layer0/fold", "qk", "lo_x"): 7.1,
+    ("xlsr_2b", "f16x3", "layer1", "q_proj", "lo_x"): 7.0,
+    ("xlsr_2b", "f16x3", "layer1", "q_proj", "lo_w"): 6.5,
+    ("xlsr_2b", "f16x3", "layer1", "k_proj", "lo_x"): 7.9,
+    ("xlsr_2b", "f16x3", "layer1", "k_proj", "lo_w"): 6.2,
+    ("xlsr_2b", "f16x3", "layer1", "qk", "lo_x"): 6.8,
+    ("xlsr_2b", "f16x3", "layer1", "qk", "lo_w"): 7.3,
+    ("xlsr_2b", "f16x3", "layer1/fold", "q_proj", "lo_x"): 6.8,
+    ("xlsr_2b", "f16x3", "layer1/fold", "q_proj", "lo_w"): 6.3,
+    ("xlsr_2b", "f16x3", "layer1/fold", "k_proj", "lo_x"): 7.6,
+    ("xlsr_2b", "f16x3", "layer1/fold", "k_proj", "lo_w"): 6.0,
+    ("xlsr_2b", "f16x3", "layer1/fold", "qk", "lo_x"): 6.8,
+    ("xlsr_2b", "f16x3", "layer1/fold", "qk", "lo_w"): 7.1,
+    ("xlsr_2b", "bf16x3", "layer0/fold", "q_proj", "lo_x"): 6.0,
+    ("xlsr_2b", "bf16x3", "layer0/fold", "q_proj", "lo_w"): 6.2,
+    ("xlsr_2b", "bf16x3", "layer0/fold", "k_proj", "lo_x"): 6.8,
+    ("xlsr_2b", "bf16x3", "layer0/fold", "k_proj", "lo_w"): 6.5,
+    ("xlsr_2b", "bf16x3", "layer0/fold", "qk", "lo_x"): 7.2,
+    ("xlsr_2b", "bf16x3", "layer0/fold", "qk", "lo_w"): 7.4,
 }
 LISTABLE_IN_COMBINED = ("q_proj", "k_proj", "qk")
 LISTED_FLOOR = 4.5  # 1.5 x the GPU gate's factor: a listed product's lost term is still caught there
@@ -84,7 +134,32 @@ def post_ln_base_case():
     return spec, synthetic.make_state_dict(spec, seed=23), synthetic.make_inventory(spec, 11, seed=23), audio, lengths
 
 
-CASES = {"xlsr": xlsr_case, "post_ln": post_ln_case, "heads": heads_case, "post_ln_base": post_ln_base_case}
+def width_case(encoder):
+    """``xlsr_case`` at another released width: the encoder's own hidden / heads / FFN / positional groups on two layers"""
+    enc = dict(encoder, layers=2)
+    spec = S.multitask_spec(enc, ["syllabic", "long"], allophone_layer=True)
+    spec["shared_phones"] = 80
+    audio, lengths = synthetic.make_audio(2, 48000, seed=1234, ragged=True)
+    return spec, synthetic.make_state_dict(spec, seed=0), synthetic.make_inventory(spec, 27, seed=0), audio, lengths
+
+
+def head_dim_case(hidden, heads, groups):
+    return lambda: SU.head_dim_model(hidden, heads, groups) + synthetic.make_audio(5, 24000, seed=hidden, ragged=True)
+
+
+class Recipe:
+    """a case: how it is built and which stages it gets beyond conv / front / layers / heads.  ``fold``: every layer also the way
+    a pass with the LayerNorm fold runs it; ``entry``: audio -> hidden[0] in one; ``tail_only``: that combined stage alone"""
+
+    def __init__(self, build, fold=False, entry=False, tail_only=False):
+        self.build, self.fold, self.entry, self.tail_only = build, fold, entry, tail_only
+
+
+CASES = {"xlsr": Recipe(xlsr_case, fold=True, entry=True), "post_ln": Recipe(post_ln_case, entry=True), "heads": Recipe(heads_case),
+         "post_ln_base": Recipe(post_ln_base_case, tail_only=True),
+         "xlsr_1b": Recipe(lambda: width_case(S.xlsr_1b_encoder()), fold=True, entry=True),
+         "xlsr_2b": Recipe(lambda: width_case(S.xlsr_2b_encoder()), fold=True, entry=True),
+         **{f"dh{hidden // heads}": Recipe(head_dim_case(hidden, heads, groups)) for hidden, heads, groups in SU.HEAD_DIM_MODELS}}
 
 
 def _named(logits, logp, transpose=False):
@@ -144,10 +219,11 @@ class Case:
         from oracle import allophant_oracle as O
 
         self.name = name
-        spec, state, tfi, audio, lengths = CASES[name]()
+        recipe = CASES[name]
+        spec, state, tfi, audio, lengths = recipe.build()
         offsets = synthetic.category_offsets(spec)
         self._measured = {}
-        if name == "post_ln_base":
+        if recipe.tail_only:
             with torch.inference_mode():
                 ref, frames, inter = O.predict(audio, lengths, state, spec, tfi, offsets, keep_intermediates=True)
                 hidden = inter["hidden_states"]
@@ -174,13 +250,13 @@ class Case:
                        Stage("front", lambda ev: SU.front_stage(inter["conv_out"], frames, state, spec, ev), hidden[0], frames)]
         for i in range(spec["layers"]):
             self.stages.append(Stage(f"layer{i}", lambda ev, i=i: SU.layer_stage(hidden[i], frames, state, spec, ev, i), hidden[i + 1], frames))
-            if name == "xlsr":  # the same layer as a pass with the LayerNorm fold runs it: the stream rounded to planes
+            if recipe.fold:  # the same layer as a pass with the LayerNorm fold runs it: the stream rounded to planes
                 self.stages.append(Stage(f"layer{i}/fold", lambda ev, i=i: SU.layer_stage(hidden[i], frames, state, spec, ev, i, fold=True),
                                          hidden[i + 1], frames))
         heads_in = {i: hidden[i] for i in SU.hidden_inputs(spec)}
         self.stages.append(Stage("heads", lambda ev: _named(*SU.heads_stage(heads_in, frames, state, spec, tfi, offsets, ev)),
                                  _named(raw, ref, transpose=True), frames))
-        if name in ("xlsr", "post_ln"):
+        if recipe.entry:
             # audio -> hidden[0] in one.  The positional convolution reaches 64 frames either way, so the truncated audio of the
             # conv stage needs an oracle run of its own: the first second of every utterance as a batch
             cut = x.shape[1]
@@ -263,6 +339,8 @@ def test_every_lost_cross_term_is_separated(case, mode):
     failures, listed = [], set()
     with torch.inference_mode():
         for stage in case.stages:
+            if (case.name, mode, stage.name) in SU.NOT_CLAIMED:
+                continue
             truth, errors, products = case.measured(stage)
             e_emu = errors[mode]
             for product in products:
