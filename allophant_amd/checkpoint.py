@@ -42,12 +42,15 @@ MODEL_ID_ENCODERS = {
     "facebook/wav2vec2-large-xlsr-53": _spec.xlsr_300m_encoder,        # same shape and variant (layer norm, pre-LN, mask)
     "facebook/wav2vec2-large-lv60": _spec.xlsr_300m_encoder,
     "facebook/mms-300m": _spec.xlsr_300m_encoder,                      # the MMS pre-trained models keep the XLS-R architectures
-    "facebook/mms-1b": _spec.xlsr_1b_encoder,                          # (their fine-tuned ASR heads add `adapter_attn_dim`: refused)
+    "facebook/mms-1b": _spec.xlsr_1b_encoder,
+    "facebook/mms-1b-all": _spec.mms_1b_adapter_encoder,               # the fine-tuned MMS encoders: a Wav2Vec2AttnAdapterLayer of
+    "facebook/mms-1b-fl102": _spec.mms_1b_adapter_encoder,             # width 16 behind every layer (`adapter_attn_dim`; read from the
+    "facebook/mms-1b-l1107": _spec.mms_1b_adapter_encoder,             # weights where they are present)
     "facebook/wav2vec2-base": _spec.wav2vec2_base_encoder,             # group norm, post-LN, return_attention_mask=False
     "facebook/wav2vec2-large": _large_groupnorm_encoder,
 }
 ENCODER_KEYS = ("conv_dim", "conv_kernel", "conv_stride", "hidden", "layers", "heads", "ffn", "pos_kernel", "pos_groups", "eps",
-                "do_normalize", "feat_extract_norm", "conv_bias", "stable_layer_norm", "use_attention_mask")
+                "do_normalize", "feat_extract_norm", "conv_bias", "stable_layer_norm", "use_attention_mask", "adapter_attn_dim")
 
 
 def _time_config(c: Dict[str, Any]) -> Optional[Dict[str, Any]]:
@@ -145,7 +148,8 @@ _ENCODER = "_acoustic_model._model.encoder."
 def check_encoder_against_state(encoder: Dict[str, Any], state: Dict[str, torch.Tensor], source: str) -> None:
     """Cross-checks an encoder description (a ``MODEL_ID_ENCODERS`` entry is written from memory) against what the weights
     themselves say: a wrong ``conv_bias`` would silently drop the biases, a wrong ``feat_extract_norm`` the norms.  Checked:
-    conv biases, the per-layer conv norms, layer and conv counts, hidden / ffn / conv widths and kernels.
+    conv biases, the per-layer conv norms, layer and conv counts, hidden / ffn / conv widths and kernels, and the attention
+    adapters (``adapter_attn_dim`` is READ from ``linear_1.weight`` where the layers carry them: the weights win).
     ``stable_layer_norm`` and ``use_attention_mask`` leave NO trace in the weights (both encoder variants own the same
     tensors; the mask is a preprocessor setting) -- they cannot be verified here and rest on the table alone."""
     def has(key: str) -> bool:
@@ -184,6 +188,26 @@ def check_encoder_against_state(encoder: Dict[str, Any], state: Dict[str, torch.
         f = tuple(state[f"{_ENCODER}layers.0.feed_forward.intermediate_dense.weight"].shape)
         if q[0] != encoder["hidden"] or f[0] != encoder["ffn"]:
             problems.append(f"hidden / ffn described as {encoder['hidden']} / {encoder['ffn']}, the weights are {q[0]} / {f[0]}")
+    # attention adapters (`adapter_attn_dim`, Wav2Vec2AttnAdapterLayer behind every pre-LN layer): the width is what the weights
+    # say (linear_1.weight is [A, hidden]); a description that names another one, or post-LN layers -- which transformers builds
+    # without adapters --, does not belong to these weights
+    first = f"{_ENCODER}layers.0.adapter_layer.linear_1.weight"
+    described = int(encoder.get("adapter_attn_dim") or 0)
+    if has(first):
+        width = int(tuple(state[first].shape)[0])
+        if not encoder.get("stable_layer_norm", True):
+            problems.append(f"the state dict holds attention adapters (adapter_layer, width {width}), which post-LN layers "
+                            "(stable_layer_norm=False) do not have")
+        elif described and described != width:
+            problems.append(f"adapter_attn_dim described as {described}, layers.0.adapter_layer.linear_1.weight is "
+                            f"{tuple(state[first].shape)}")
+        else:
+            encoder["adapter_attn_dim"] = width
+        with_adapter = sum(has(f"{_ENCODER}layers.{i}.adapter_layer.linear_1.weight") for i in range(layers))
+        if with_adapter != layers:
+            problems.append(f"{with_adapter} of {layers} encoder layers carry an attention adapter")
+    elif described and encoder.get("stable_layer_norm", True) and layers:
+        problems.append(f"adapter_attn_dim={described} but the state dict has no layers.0.adapter_layer tensors")
     # wav2vec 2.0 adapters (`add_adapter`): the reference runs them and reads nothing of their output (spec.validate), so their
     # weights are simply not uploaded -- unless the adapter changes the width the classifiers were built for, which the reference
     # itself cannot run (acoustic_model.py:822 sizes them by `output_hidden_size`, the states keep `hidden_size`)

@@ -36,6 +36,9 @@ struct Layer {
     // pre-LN layers: the LayerNorm in front of QKV / FFN1 is folded into those products (GemmParams.row_coef): wqkv / w1 hold
     // gamma (.) W, bqkv / b1 hold d = W beta + b, and c = W gamma (row sums of the folded weights) is what the mean term multiplies
     float *c_qkv = nullptr, *c_1 = nullptr;
+    // attention adapter (amx_config.adapter_attn_dim = A > 0, pre-LN layers; launch_adapter): W1 diag(gamma) [A, D] and
+    // b1 + W1 beta [A] -- the adapter's LayerNorm folded in --, W2 transposed [A, D], b2 [D]; fp32
+    float *ad_w1 = nullptr, *ad_b1 = nullptr, *ad_w2t = nullptr, *ad_b2 = nullptr;
 };
 
 // One GEMM (or GEMM pair for the composition head) of the hierarchical projection
@@ -84,6 +87,7 @@ struct amx_handle_s {
     bool gn = false;         // feat_extract_norm == "group": GroupNorm over time behind conv layer 0, no norm behind layers 1..
     bool stable = true;      // do_stable_layer_norm: pre-LN layers + final LayerNorm; false: post-LN layers
     bool masked = true;      // the model is called with the attention mask of the lengths; false: attention_mask=None
+    int adapter = 0;         // width of the attention adapter behind every pre-LN layer (0: none; always 0 for post-LN layers)
     float* conv_b[AMX_MAX_CONV] = {};
     float* conv_g[AMX_MAX_CONV] = {};
     float* conv_be[AMX_MAX_CONV] = {};
@@ -466,6 +470,8 @@ static int check_config(const amx_config* cfg, int n_classes) {
     if (cfg->feat_extract_norm != AMX_NORM_LAYER && cfg->feat_extract_norm != AMX_NORM_GROUP)
         return fail(nullptr, AMX_EINVAL, "`feat_extract_norm` has to be one of ['group', 'layer']");
     if (cfg->embedding_size % 8) return fail(nullptr, AMX_EINVAL, "embedding_size must be a multiple of 8");
+    if (cfg->adapter_attn_dim < 0 || cfg->adapter_attn_dim > ADAPTER_MAX_DIM)
+        return fail(nullptr, AMX_EINVAL, "adapter_attn_dim must be 0 (no attention adapters) or 1 .. " + std::to_string(ADAPTER_MAX_DIM));
     if (n_classes < 1) return fail(nullptr, AMX_EINVAL, "Each model needs at least one classifier");
     return AMX_OK;
 }
@@ -614,6 +620,42 @@ static int create_projection(amx_handle h, const TensorMap& tm, float* staging) 
     return AMX_OK;
 }
 
+// The attention adapter of layer l (Wav2Vec2AttnAdapterLayer: norm, linear_1, ReLU, linear_2).  Its LayerNorm is folded into
+// linear_1 like the layer's other norms (fold_layer_norm), linear_2 is stored transposed: both matrices are then [A, D], read by
+// column block.  A model without adapters (or a post-LN one, which upstream builds without them) must not carry their tensors:
+// they are refused, never dropped.
+static int create_adapter(amx_handle h, const TensorMap& tm, int l) {
+    const int D = h->cfg.hidden, A = h->adapter;
+    const std::string p = AM + "encoder.layers." + std::to_string(l) + ".adapter_layer.";
+    if (A == 0) {
+        auto it = tm.m.lower_bound(p);
+        if (it != tm.m.end() && it->first.compare(0, p.size(), p) == 0)
+            return fail(h, AMX_EINVAL, "tensor " + it->first + " belongs to an attention adapter, but " +
+                                           (h->cfg.adapter_attn_dim ? "post-LN encoder layers (do_stable_layer_norm = false) have none"
+                                                                    : "adapter_attn_dim is 0"));
+        return AMX_OK;
+    }
+    const amx_tensor* t[6];
+    const char* names[6] = {"norm.weight", "norm.bias", "linear_1.weight", "linear_1.bias", "linear_2.weight", "linear_2.bias"};
+    const int64_t numel[6] = {D, D, (int64_t)A * D, A, (int64_t)D * A, D};
+    for (int i = 0; i < 6; ++i) {
+        t[i] = tm.get(p + names[i]);
+        if (!t[i]) return fail(h, AMX_EINVAL, "missing tensor in state_dict: " + p + names[i] + " (adapter_attn_dim = " + std::to_string(A) + ")");
+        if (t[i]->numel != numel[i])
+            return fail(h, AMX_EINVAL, "tensor " + p + names[i] + " has " + std::to_string(t[i]->numel) + " elements, expected " +
+                                           std::to_string(numel[i]) + " (adapter_attn_dim = " + std::to_string(A) + ")");
+    }
+    std::vector<float> w1((size_t)A * D), c(A), b1(A), w2t((size_t)A * D);
+    fold_layer_norm(t[2]->data, t[3]->data, t[0]->data, t[1]->data, A, D, 1.f, w1.data(), c.data(), b1.data());
+    for (int d = 0; d < D; ++d)
+        for (int a = 0; a < A; ++a) w2t[(size_t)a * D + d] = t[4]->data[(size_t)d * A + a];
+    Layer& ly = h->layers[l];
+    TRY(dev_upload(h, &ly.ad_w1, w1.data(), w1.size() * 4));
+    TRY(dev_upload(h, &ly.ad_b1, b1.data(), b1.size() * 4));
+    TRY(dev_upload(h, &ly.ad_w2t, w2t.data(), w2t.size() * 4));
+    return upload_f32(h, tm, p + "linear_2.bias", D, &ly.ad_b2);
+}
+
 // encoder layer l: Q / K / V as one product, the out-projection, the FFN
 static int create_layer(amx_handle h, const TensorMap& tm, int l, float* staging) {
     const int D = h->cfg.hidden, F = h->cfg.ffn;
@@ -684,7 +726,8 @@ static int create_layer(amx_handle h, const TensorMap& tm, int l, float* staging
     }
     TRY(linear("attention.out_proj", D, D, ly.wo, ly.r_o, &ly.bo));
     if (!h->stable) TRY(linear("feed_forward.intermediate_dense", F, D, ly.w1, ly.r_1, &ly.b1));
-    return linear("feed_forward.output_dense", D, F, ly.w2, ly.r_2, &ly.b2);
+    TRY(linear("feed_forward.output_dense", D, F, ly.w2, ly.r_2, &ly.b2));
+    return create_adapter(h, tm, l);
 }
 
 // the hierarchical projection: one HeadStep per classifier in evaluation order (direct-output classifiers stacked), then their
@@ -841,6 +884,8 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
     h->gn = cfg->feat_extract_norm == AMX_NORM_GROUP;
     h->stable = cfg->stable_layer_norm != 0;
     h->masked = cfg->use_attention_mask != 0;
+    // (the post-LN layer class builds no adapter even when the config names one: the field has no effect there, as upstream)
+    h->adapter = h->stable ? cfg->adapter_attn_dim : 0;
     // (hidden too -- round 6: the residual-stream planes [M, hidden] are GEMM operands like the others; a hidden size off the
     // 32-element blocks -- 240 = 2 heads of 120 -- ran interleaved planes through kernels that assume block-aligned rows)
     h->il = h->NT > 1 && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
@@ -1669,7 +1714,9 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     }
     // LayerNorm fold: decided on the products as they will be launched
     P.stream_in_planes = NT == 2;
-    if (P.stable && c.layers > 0 && D % 64 == 0 && D <= 2048) {
+    // (not with attention adapters: the adapter would have to sit inside the fold's producer / consumer chain -- FFN2 leaves planes
+    // and statistics of a stream the adapter then changes.  Adapter models keep the row passes, the adapter writing one of them.)
+    if (P.stable && c.layers > 0 && D % 64 == 0 && D <= 2048 && !h->adapter) {
         WS("ln_rowps", (size_t)P.Mrows * 16, P.ln_rowps);
         WS("ln_coef", (size_t)P.Mrows * 8, P.ln_coef);
         WS("ln_partial", (size_t)P.Mrows * (D / 64) * 8, P.ln_partial);
@@ -1910,8 +1957,9 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
                 launch_ln_rowprep(prec, (const float*)hbuf, D, P.Mrows, D, c.eps, P.xp, P.xp_plane, D, (float4*)P.ln_rowps, (float2*)P.ln_coef,
                                   fold_frames, T, s);
             }
-        } else if (P.stable) {
-            stream_norm(h->unit_g, h->zero_b, P.Mrows, P.xp_plane, nullptr);  // (completes the previous layer's FFN2 when that was deferred)
+        } else if (P.stable && !(h->adapter && l > 0)) {
+            // (completes the previous layer's FFN2 when that was deferred; behind an attention adapter the planes are there already)
+            stream_norm(h->unit_g, h->zero_b, P.Mrows, P.xp_plane, nullptr);
         }
         if (P.saved[l]) {
             // a classifier reads hidden state l (OUTPUT_l, acoustic_model.py:478-483): padded layout; with packed rows the padded
@@ -1948,7 +1996,16 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
             if (!last) ln_finalize();
         } else {
             // (the last layer of a packed batch is followed by the unpacking, not by a LayerNorm of these rows)
-            residual_gemm(P.ffn2_params(h, ly), !P.fold && !(P.packed && !P.packed_early && l == c.layers - 1));
+            // (nor is the FFN2 of an adapter layer: the adapter needs finished rows)
+            residual_gemm(P.ffn2_params(h, ly), !P.fold && !h->adapter && !(P.packed && !P.packed_early && l == c.layers - 1));
+        }
+        if (h->adapter) {
+            // attention adapter, in place on the stream; every layer but the last: also the planes of the next layer's first
+            // LayerNorm (the last layer is followed by the final LayerNorm of the fp32 rows, after unpacking where rows are packed)
+            Timed t_(h, AMX_KC_ROWNORM);
+            const bool last = l + 1 == c.layers;
+            launch_adapter(prec, (float*)hbuf, P.Mrows, D, h->adapter, ly.ad_w1, ly.ad_b1, ly.ad_w2t, ly.ad_b2, c.eps, last ? nullptr : P.xp,
+                           P.xp_plane, s);
         }
         if (!P.stable) stream_norm(ly.ln2_g, ly.ln2_b, P.Mrows, P.xp_plane, ln_inplace);  // `final_layer_norm` closes the post-LN layer
     }

@@ -159,6 +159,26 @@ __device__ __forceinline__ void split16x2(f32x2 y, typename Vec2<T>::type& hi, t
     }
 }
 
+// Four adjacent columns of a row onto the 16-bit planes: `o` is the logical element offset row * ld + column (a multiple of 4) in
+// either plane layout.  THE plane writer of the row kernels (rownorm_kernel, the attention adapter): what a product reads as its A
+// operand is split and laid out here and nowhere else.
+template <typename T, int NT>
+__device__ __forceinline__ void store_planes4(T* __restrict__ out_p, int64_t out_plane, int64_t o, float4 v) {
+    T hi[4], lo[4];
+    split16<T, NT>(v.x, hi[0], lo[0]);
+    split16<T, NT>(v.y, hi[1], lo[1]);
+    split16<T, NT>(v.z, hi[2], lo[2]);
+    split16<T, NT>(v.w, hi[3], lo[3]);
+    T* dst = out_p + pidx(o, plane_is_il<NT>(out_plane));
+    typedef typename Vec4<T>::type V4;
+    V4 hv = {hi[0], hi[1], hi[2], hi[3]};
+    *(V4*)dst = hv;
+    if (NT > 1) {
+        V4 lv = {lo[0], lo[1], lo[2], lo[3]};
+        *(V4*)(dst + out_plane) = lv;
+    }
+}
+
 // exact (erf) GELU as  gelu(x) = max(x, 0) - |x| * 2^-(|x| Q(|x|) + 1),  where  |x| Q(|x|) = -log2(erfc(|x| / sqrt 2))  and Q
 // is a degree-6 minimax fit on [0, 5.7] (weighted by the sensitivity |x|^2 erfc; beyond 5.7 the correction is < 1e-8 and
 // |x| is clamped).  One quarter-rate instruction (v_exp_f32) and 8 FMAs that pack two values per v_pk_fma_f32: the
@@ -431,6 +451,15 @@ void launch_pack_rows(const float* padded, float* packed, const int* row_off, co
 void launch_rownorm(int prec, const float* x, int64_t ldx, int64_t M, int D, const float* gamma1, const float* beta1,
                     int gelu, const float* gamma2, const float* beta2, float eps1, float eps2, void* out_p,
                     int64_t out_plane, int64_t ldp, float* out_f32, int64_t ldo, hipStream_t s);
+// Attention adapter of a pre-LN encoder layer (transformers Wav2Vec2AttnAdapterLayer, config.adapter_attn_dim = A; amx_adapter.hip):
+// in place on the fp32 rows h [M, D] (D % 8 == 0, D <= 2048),  h += W2 relu(W1' LN0(h) + b1') + b2  with LN0 the LayerNorm without
+// affine part at ADAPTER_LN_EPS (gamma / beta live in W1' = W1 diag(gamma), b1' = b1 + W1 beta: amx_create), w1 = W1' [A, D] and
+// w2t = W2 transposed [A, D], fp32.  out_p != null: also the planes of LayerNorm(h') without affine part at `eps` -- what
+// launch_rownorm(unit gamma, zero beta) would write for the next layer's QKV product, through the same plane writer.
+constexpr float ADAPTER_LN_EPS = 1e-5f;  // nn.LayerNorm's default: the adapter's norm does not take config.layer_norm_eps
+constexpr int ADAPTER_MAX_DIM = 64;
+void launch_adapter(int prec, float* h, int64_t M, int D, int A, const float* w1, const float* b1, const float* w2t, const float* b2,
+                    float eps, void* out_p, int64_t out_plane, hipStream_t s);
 // LayerNorm fold (GemmParams.ln_partial / row_coef): the FIRST norm of the encoder stack, from the fp32 stream itself: exact row
 // statistics (two passes over the row in registers, like launch_rownorm) -> planes of u = (x - mu) * s with s the power of two
 // that puts 2 / sigma ... 1 / sigma into it, rowps[m] = (mu, s, mu, s), coef[m] = (rstd / s, 0).  frame_len (may be null: no

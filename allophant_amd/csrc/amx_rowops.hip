@@ -898,21 +898,7 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* x, int64_t ld
         int c = (i * 64 + lane) * 4;
         if (c < D) {
             if (out_f32) *(float4*)(out_f32 + row * ldo + c) = v[i];
-            if (out_p) {
-                T hi[4], lo[4];
-                split16<T, NT>(v[i].x, hi[0], lo[0]);
-                split16<T, NT>(v[i].y, hi[1], lo[1]);
-                split16<T, NT>(v[i].z, hi[2], lo[2]);
-                split16<T, NT>(v[i].w, hi[3], lo[3]);
-                T* dst = out_p + pidx(row * ldp + c, plane_is_il<NT>(out_plane));
-                typedef typename Vec4<T>::type V4;
-                V4 hv = {hi[0], hi[1], hi[2], hi[3]};
-                *(V4*)dst = hv;
-                if (NT > 1) {
-                    V4 lv = {lo[0], lo[1], lo[2], lo[3]};
-                    *(V4*)(dst + out_plane) = lv;
-                }
-            }
+            if (out_p) store_planes4<T, NT>(out_p, out_plane, row * ldp + c, v[i]);
         }
     }
 }

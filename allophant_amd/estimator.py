@@ -221,6 +221,7 @@ def _spec_to_structs(spec: Dict[str, Any], precision: str):
     cfg.conv_bias = int(bool(spec.get("conv_bias", True)))
     cfg.stable_layer_norm = int(bool(spec.get("stable_layer_norm", True)))
     cfg.use_attention_mask = int(bool(spec.get("use_attention_mask", True)))
+    cfg.adapter_attn_dim = int(spec.get("adapter_attn_dim") or 0)
 
     classes = spec["classes"]
     index = {c["name"]: i for i, c in enumerate(classes)}

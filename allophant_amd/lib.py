@@ -10,8 +10,10 @@ import os
 from typing import Optional
 
 # AMX_ABI_OVERRIDE: developer switch for same-box A/B runs against a library built from an OLDER revision (tools/ab_build.sh):
-# ABI 5 and 6 added flags and entry points to ABI 4 without changing a struct, so an older build runs under this binding
-AMX_ABI_VERSION = int(os.environ.get("AMX_ABI_OVERRIDE") or 6)
+# ABI 5 and 6 added flags and entry points to ABI 4 without changing a struct, and ABI 7 split the last 32-bit member of amx_config
+# into use_attention_mask and adapter_attn_dim, 16 bits each (an older build reads the pair as the mask while the dimension is 0:
+# models without attention adapters only), so an older build runs under this binding
+AMX_ABI_VERSION = int(os.environ.get("AMX_ABI_OVERRIDE") or 7)
 AMX_MAX_CONV = 8
 AMX_MAX_DEPS = 64
 AMX_NAME_LEN = 48
@@ -86,7 +88,7 @@ class AmxConfig(C.Structure):
         ("pos_kernel", C.c_int32), ("pos_groups", C.c_int32), ("eps", C.c_float), ("do_normalize", C.c_int32),
         ("dependency_blanks", C.c_int32), ("embedding_size", C.c_int32), ("allophone_layer", C.c_int32),
         ("precision", C.c_int32), ("feat_extract_norm", C.c_int32), ("conv_bias", C.c_int32),
-        ("stable_layer_norm", C.c_int32), ("use_attention_mask", C.c_int32),
+        ("stable_layer_norm", C.c_int32), ("use_attention_mask", C.c_int16), ("adapter_attn_dim", C.c_int16),
     ]
 
 

@@ -9,7 +9,9 @@ A *spec* is a plain dict (JSON-serialisable) carrying exactly the fields of the 
   (``allophant/config.py:624-712``, ``allophant/attribute_graph.py:17-41``),
 * ``embedding_size`` of the compositional phoneme layer (``allophant/config.py:666-676``) or ``None``,
 * ``allophone_layer``: whether predict-mode publishes ``"phone"`` next to ``"phoneme"``
-  (``allophant/network/acoustic_model.py:161-167``).
+  (``allophant/network/acoustic_model.py:161-167``),
+* optionally ``adapter_attn_dim`` (``Wav2Vec2Config.adapter_attn_dim``, 16 for the fine-tuned MMS encoders): every pre-LN
+  encoder layer ends in a ``Wav2Vec2AttnAdapterLayer``.
 """
 from __future__ import annotations
 
@@ -89,6 +91,24 @@ def xlsr_2b_encoder() -> Dict[str, Any]:
     encoder = xlsr_300m_encoder()
     encoder.update(hidden=1920, layers=48, heads=16, ffn=7680)
     return encoder
+
+
+MAX_ADAPTER_ATTN_DIM = 64  # ADAPTER_MAX_DIM of the library
+
+
+def mms_1b_adapter_encoder() -> Dict[str, Any]:
+    """The fine-tuned MMS encoders ``facebook/mms-1b-all`` / ``-fl102`` / ``-l1107`` [memory: the XLS-R 1B shape with
+    ``adapter_attn_dim`` 16 in their published configs; ``checkpoint.check_encoder_against_state`` reads the dimension from the
+    weights, which win]."""
+    encoder = xlsr_1b_encoder()
+    encoder["adapter_attn_dim"] = 16
+    return encoder
+
+
+def adapter_attn_dim(spec: Dict[str, Any]) -> int:
+    """Width of the attention adapter the encoder layers of ``spec`` end in: 0 without one, and 0 for post-LN layers
+    (``stable_layer_norm=False``), which transformers builds without an adapter whatever the config says."""
+    return int(spec.get("adapter_attn_dim") or 0) if spec.get("stable_layer_norm", True) else 0
 
 
 def tiny_encoder(layers: int = 2) -> Dict[str, Any]:
@@ -228,6 +248,8 @@ def spec_from_reference_model(model) -> Dict[str, Any]:
     spec["conv_bias"] = bool(getattr(config, "conv_bias", True))
     spec["stable_layer_norm"] = bool(getattr(config, "do_stable_layer_norm", True))
     spec["use_attention_mask"] = bool(getattr(acoustic, "_use_attention_mask", True))  # preprocessor return_attention_mask
+    if getattr(config, "adapter_attn_dim", None):
+        spec["adapter_attn_dim"] = int(config.adapter_attn_dim)
     projection = model._projection
     dependencies = {name: [d.name for d in deps] for name, deps in projection._ordered_nodes}
     embedding_size = None
@@ -334,6 +356,10 @@ def validate(spec: Dict[str, Any]) -> None:
         if out_size not in (None, spec["hidden"]):
             raise ValueError(f"add_adapter with output_hidden_size={out_size} != hidden={spec['hidden']}: the reference sizes its classifiers "
                              "for the adapter's width but feeds them encoder states (mat1 and mat2 shapes cannot be multiplied)")
+    adapter = spec.get("adapter_attn_dim")
+    if adapter is not None and (isinstance(adapter, bool) or not isinstance(adapter, int) or not 0 <= adapter <= MAX_ADAPTER_ATTN_DIM):
+        # `Wav2Vec2Config.adapter_attn_dim`: a Wav2Vec2AttnAdapterLayer of this width behind the FFN of every pre-LN layer
+        raise ValueError(f"adapter_attn_dim must be None, 0 or 1 .. {MAX_ADAPTER_ATTN_DIM} (amx_create), not {adapter!r}")
     if spec.get("feat_extract_norm", "layer") not in ("layer", "group"):
         # transformers' own message (Wav2Vec2FeatureEncoder.__init__)
         raise ValueError(f"`config.feat_extract_norm` is {spec['feat_extract_norm']}, but has to be one of ['group', 'layer']")

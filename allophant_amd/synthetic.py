@@ -92,6 +92,17 @@ def make_state_dict(spec: Dict[str, Any], seed: int = 0, include_unused: bool = 
         put(p + "feed_forward.output_dense.bias", (D,), 0.02)
         put(p + "final_layer_norm.weight", (D,), 0.1, 1.0)
         put(p + "final_layer_norm.bias", (D,), 0.1)
+        A = _spec.adapter_attn_dim(spec)
+        if A:
+            # Wav2Vec2AttnAdapterLayer behind the FFN residual.  Weights of std 1 / sqrt(fan_in) (a fine-tuned adapter, not the zero
+            # linear_2 of a fresh one): its term is then a visible share of the stream, so a test can tell a wrong adapter from a
+            # right one; non-unit gamma and non-zero biases, so that none of them can be dropped unseen
+            put(p + "adapter_layer.norm.weight", (D,), 0.1, 1.0)
+            put(p + "adapter_layer.norm.bias", (D,), 0.1)
+            put(p + "adapter_layer.linear_1.weight", (A, D), 1.0 / math.sqrt(D))
+            put(p + "adapter_layer.linear_1.bias", (A,), 0.3)
+            put(p + "adapter_layer.linear_2.weight", (D, A), 1.0 / math.sqrt(A))
+            put(p + "adapter_layer.linear_2.bias", (D,), 0.2)
 
     if spec.get("add_adapter") and include_unused:
         # Wav2Vec2Adapter (strided Conv1d + GLU layers behind the encoder): owned by the reference's state dict, computed by its HF

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define AMX_ABI_VERSION 6
+#define AMX_ABI_VERSION 7
 
 #define AMX_MAX_CONV 8
 #define AMX_MAX_DEPS 64
@@ -112,9 +112,20 @@ typedef struct amx_config {
     int32_t stable_layer_norm;           /* config.do_stable_layer_norm: 1 = pre-LN layers + final LayerNorm
                                             (Wav2Vec2EncoderStableLayerNorm), 0 = LayerNorm behind the positional convolution and
                                             post-LN layers (Wav2Vec2Encoder) */
-    int32_t use_attention_mask;          /* preprocessor return_attention_mask (acoustic_model.py:814,842-846): 0 = the model is
+    int16_t use_attention_mask;          /* preprocessor return_attention_mask (acoustic_model.py:814,842-846): 0 = the model is
                                             called with attention_mask=None -- padded frames are neither zeroed nor masked as
                                             keys; `Predictions.lengths` are the downsampled lengths either way */
+    /* ABI 7: the last 32-bit member, until then `int32_t use_attention_mask` (0 / 1), is two 16-bit members: the struct keeps its size
+     * and the offsets of every older member, and a little-endian build of ABI <= 6 reads the pair as the mask value it expects whenever
+     * the adapter dimension is 0 -- the only models such a build runs.
+     * `Wav2Vec2Config.adapter_attn_dim` (the fine-tuned MMS encoders facebook/mms-1b-all, -fl102, -l1107: 16).  A > 0: every
+     * pre-LN encoder layer ends in a `Wav2Vec2AttnAdapterLayer` behind its FFN residual
+     * (`Wav2Vec2EncoderLayerStableLayerNorm.forward`):  h <- h + linear_2(relu(linear_1(norm(h)))),  norm = nn.LayerNorm(hidden) at
+     * torch's default eps 1e-5 (NOT layer_norm_eps), linear_1 [A, hidden], linear_2 [hidden, A]; hidden_states[i + 1] is the stream
+     * behind the adapter.  The state_dict then carries `encoder.layers.{i}.adapter_layer.{norm,linear_1,linear_2}.{weight,bias}` for
+     * every layer; with 0 such tensors are refused (AMX_EINVAL), never dropped.  1 .. 64.  Post-LN layers (stable_layer_norm = 0)
+     * have no adapter upstream whatever the config says: the field is ignored for them. */
+    int16_t adapter_attn_dim;            /* 0 = no attention adapters */
 } amx_config;
 
 /* One classifier of the hierarchical projection (`ProjectionEntryConfig` / `AttributeNode`,
