@@ -2966,6 +2966,121 @@ extern "C" int amx_edit_matrix(int device, const int32_t* expected_offsets, cons
     return AMX_OK;
 }
 
+// confusion tables
+static std::string confusion_capacity_limits(int64_t capacity) {
+    if (capacity < AMX_EDIT_CONFUSION_MIN_CAPACITY || capacity > AMX_EDIT_CONFUSION_MAX_CAPACITY || (capacity & (capacity - 1)) != 0)
+        return "a confusion table holds a power of two of " + std::to_string(AMX_EDIT_CONFUSION_MIN_CAPACITY) + " to " +
+               std::to_string(AMX_EDIT_CONFUSION_MAX_CAPACITY) + " slots";
+    return "";
+}
+
+extern "C" int amx_edit_confusion_table_bytes(int64_t capacity, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    const std::string err = confusion_capacity_limits(capacity);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    *bytes = (size_t)capacity * 2 * sizeof(uint64_t);
+    return AMX_OK;
+}
+
+// The checks and the row arguments that the two confusion entries share.  Returns AMX_OK with *rows == 0 when there is
+// nothing to launch.
+static int confusion_frame(const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O, int N, int K,
+                           int64_t T, const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets,
+                           const int32_t* label_ids, const int32_t* groups, int G, const int32_t* map_offsets,
+                           const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
+                           int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes, const int32_t* best,
+                           void* table, int64_t capacity, int32_t* row_events, uint64_t* counters, amx::EditOpsArgs& x,
+                           amx::EditConfusionOut& c, int64_t* rows) {
+    *rows = 0;
+    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
+    if (K < 1 || K > AMX_EDIT_MAX_CANDIDATES)
+        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
+    std::string err = edit_limits(max_expected, max_actual);
+    if (err.empty()) err = confusion_capacity_limits(capacity);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
+    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
+    if ((int64_t)O * N * K > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N * K must stay below 2^31");
+    size_t needed = 0;
+    if (!edit_operations_workspace_bytes((int64_t)O * N, max_expected, max_actual, &needed))
+        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
+    if ((int64_t)O * N == 0) return AMX_OK;
+    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
+        !workspace || !table || !row_events || !counters)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (workspace_bytes < needed) return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_operations_workspace");
+    amx::EditArgs& a = x.e;
+    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = stride_k, a.T = T;
+    a.O = O, a.N = N, a.K = K, a.G = G, a.H = H;
+    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
+    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
+    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
+    a.workspace = (int32_t*)workspace;
+    c.best = best, c.table = (unsigned long long*)table, c.capacity = capacity, c.row_events = row_events;
+    c.counters = (unsigned long long*)counters;
+    *rows = (int64_t)O * N;
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_confusions(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O,
+                                   int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                   const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                   const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                   const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual, void* workspace,
+                                   size_t workspace_bytes, const int32_t* best, void* table, int64_t capacity, int32_t* row_events,
+                                   uint64_t* counters, void* stream) {
+    amx::EditConfusionArgs p{};
+    int64_t rows = 0;
+    const int code = confusion_frame(tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids,
+                                     groups, G, map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace,
+                                     workspace_bytes, best, table, capacity, row_events, counters, p.x, p.c, &rows);
+    if (code != AMX_OK || rows == 0) return code;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_edit_confusions(p, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit confusions launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_weighted_confusions(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k,
+                                            int O, int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                            const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                            const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                            const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual,
+                                            void* workspace, size_t workspace_bytes, float insertion_cost, float deletion_cost,
+                                            const int64_t* cost_tables, const uint8_t* cost_table_data, const int32_t* best,
+                                            void* table, int64_t capacity, int32_t* row_events, uint64_t* counters, void* stream) {
+    const std::string err = edit_cost_limits(insertion_cost, deletion_cost);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    amx::EditWeightedConfusionArgs p{};
+    int64_t rows = 0;
+    const int code = confusion_frame(tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids,
+                                     groups, G, map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace,
+                                     workspace_bytes, best, table, capacity, row_events, counters, p.w.x, p.c, &rows);
+    if (code != AMX_OK || rows == 0) return code;
+    if (!cost_tables) return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    p.w.insertion_cost = insertion_cost, p.w.deletion_cost = deletion_cost;
+    p.w.tables = cost_tables, p.w.table_data = cost_table_data, p.w.costs = nullptr;
+    launch_edit_weighted_confusions(p, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "weighted edit confusions launch failed");
+    return AMX_OK;
+}
+
+extern "C" int amx_edit_confusion_merge(int device, const void* src, int64_t src_capacity, void* dst, int64_t dst_capacity,
+                                        uint64_t* counters, void* stream) {
+    std::string err = confusion_capacity_limits(src_capacity);
+    if (err.empty()) err = confusion_capacity_limits(dst_capacity);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (!src || !dst || !counters) return fail(nullptr, AMX_EINVAL, "null buffer");
+    const char *sb = (const char*)src, *db = (const char*)dst;
+    if (sb < db + dst_capacity * 16 && db < sb + src_capacity * 16) return fail(nullptr, AMX_EINVAL, "the tables overlap");
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_edit_confusion_merge((const unsigned long long*)src, src_capacity, (unsigned long long*)dst, dst_capacity,
+                                (unsigned long long*)counters, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "confusion merge launch failed");
+    return AMX_OK;
+}
+
 // =================================================================================================================
 // allophone layer
 // =================================================================================================================

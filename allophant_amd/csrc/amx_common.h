@@ -707,6 +707,29 @@ struct EditMatrixArgs {
 };
 void launch_edit_matrix(EditMatrixArgs a, hipStream_t s);
 
+// confusion tables (amx_edit_confusion.hip; weighted: amx_edit_weighted_confusion.hip): one wave per (output, utterance)
+// row on the operations' workspace layout, walking candidate best[o, n] (null: candidate 0) of x.e's K candidates and adding
+// every aligned pair to an open-addressed table of `capacity` (key, count) slots.
+struct EditConfusionOut {
+    const int32_t* best;          // [O, N] or null
+    unsigned long long* table;    // [capacity, 2]
+    int64_t capacity;             // a power of two
+    int32_t* row_events;          // [O, N]
+    unsigned long long* counters; // [2]: events added, events dropped
+};
+struct EditConfusionArgs {
+    EditOpsArgs x;
+    EditConfusionOut c;
+};
+struct EditWeightedConfusionArgs {
+    EditWeightedArgs w;
+    EditConfusionOut c;
+};
+void launch_edit_confusions(EditConfusionArgs a, hipStream_t s);
+void launch_edit_weighted_confusions(EditWeightedConfusionArgs a, hipStream_t s);
+void launch_edit_confusion_merge(const unsigned long long* src, int64_t src_capacity, unsigned long long* dst,
+                                 int64_t dst_capacity, unsigned long long* counters, hipStream_t s);
+
 // weight packing helpers (device side; run once at amx_create / amx_set_inventory)
 void launch_pack_matrix(int prec, const float* src, int rows, int cols, int64_t src_row_stride, int64_t src_col_stride,
                         float scale, void* dst, int64_t dst_plane, int64_t ldd, int cols_pad, hipStream_t s);

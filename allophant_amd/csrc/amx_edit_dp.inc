@@ -1,6 +1,8 @@
-// Device helpers shared by amx_edit.hip (statistics), amx_edit_ops.hip (operations) and amx_edit_weighted.hip (both under
-// feature-weighted costs): the CSR expansion of a row's ids, the anti-diagonal wavefront DP over a cost model, the path codes
-// and the walk over them, and the candidate choice.  Included inside namespace amx { namespace { ... } }.
+// Device helpers shared by amx_edit.hip (statistics), amx_edit_ops.hip (operations), amx_edit_confusion.hip (confusion
+// tables) and amx_edit_weighted.hip / amx_edit_weighted_confusion.hip (the three under feature-weighted costs): the CSR
+// expansion of a row's ids, the
+// anti-diagonal wavefront DP over a cost model, the path codes and the walks over them, the confusion table's insert, and
+// the candidate choice.  Included inside namespace amx { namespace { ... } }.
 //
 // Lane l owns expected row i = 64 s + l + 1 of strip s and the wave sweeps the hypothesis as an anti-diagonal: at step t lane
 // l computes column j = t - l, with the cell above and the diagonal arriving from lane l - 1 by a DPP wave shift.  Lane 0
@@ -249,6 +251,140 @@ __device__ __forceinline__ void walk_operations(const uint4* codes, int64_t stri
             written = k;
         }
     }
+}
+
+// Confusion tables (amx_edit_confusions and its siblings): an open-addressed table of (key, count) slots of 64 bits each, key 0
+// empty.  A key packs (g * O + o + 1, expected id + 1, actual id + 1), epsilon as 0, in GROUP / SYMBOL / SYMBOL bits.
+constexpr int CONFUSION_SYMBOL_BITS = AMX_EDIT_CONFUSION_SYMBOL_BITS;
+constexpr int CONFUSION_MAX_GROUPS = (1 << AMX_EDIT_CONFUSION_GROUP_BITS) - 1;  // G * O
+constexpr int CONFUSION_MAX_SYMBOL = (1 << CONFUSION_SYMBOL_BITS) - 2;           // the largest id
+
+// Adds `count` to `key`'s slot of table[0, mask + 1): linear probing from the key's hash, an empty slot claimed by a
+// compare-and-swap on its key.  At most mask + 1 probes: false when every slot holds another key.
+__device__ __forceinline__ bool confusion_insert(unsigned long long* table, unsigned long long mask, unsigned long long key,
+                                                 unsigned long long count) {
+    unsigned long long h = key;
+    h ^= h >> 30, h *= 0xbf58476d1ce4e5b9ull;
+    h ^= h >> 27, h *= 0x94d049bb133111ebull;
+    h ^= h >> 31;
+    h &= mask;
+    for (unsigned long long probe = 0; probe <= mask; ++probe, h = (h + 1) & mask) {
+        unsigned long long* slot = table + 2 * h;
+        unsigned long long held = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (held == 0) {
+            held = atomicCAS(slot, 0ull, key);
+            if (held == 0) held = key;
+        }
+        if (held == key) {
+            atomicAdd(slot + 1, count);
+            return true;
+        }
+    }
+    return false;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
+    return v;  // lane 0's
+}
+
+// One row's events on their way into the table: every lane adds its own staged event, so a wave issues up to 64 atomics at
+// a time; `finish` adds the row's added / dropped events to counters[0 / 1] with one atomic each.
+struct ConfusionSink {
+    unsigned long long* table;
+    unsigned long long mask;    // capacity - 1
+    unsigned long long prefix;  // (g * O + o + 1) << (2 * CONFUSION_SYMBOL_BITS)
+    unsigned int added, dropped;  // this lane's
+    __device__ __forceinline__ void add(int expected, int actual) {  // symbol ids, -1: epsilon
+        const unsigned long long key =
+            prefix | (unsigned long long)(expected + 1) << CONFUSION_SYMBOL_BITS | (unsigned long long)(actual + 1);
+        if (confusion_insert(table, mask, key, 1)) ++added;
+        else ++dropped;
+    }
+    __device__ __forceinline__ void finish(unsigned long long* counters, int lane) {
+        const unsigned long long a = wave_sum(added), d = wave_sum(dropped);
+        if (lane == 0 && a) atomicAdd(counters, a);
+        if (lane == 0 && d) atomicAdd(counters + 1, d);
+    }
+};
+
+// Every id of ids[0, count) in [0, limit]?  (wave-uniform answer)
+__device__ __forceinline__ bool symbols_within(const int32_t* ids, int count, int limit, int lane) {
+    bool bad = false;
+    for (int base = 0; base < count; base += WAVE) {
+        const int idx = base + lane;
+        if (idx < count) bad |= ids[idx] < 0 || ids[idx] > limit;
+    }
+    return !__any(bad);
+}
+
+// The candidate a confusion row walks: best[on] where `best` is given, else candidate 0.  -1: no candidate (none present, or
+// best == -1); -2: flagged (best == -2, or a best at or past the candidates present).
+__device__ __forceinline__ int confusion_candidate(const EditArgs& a, const int32_t* best, int64_t on) {
+    const int present = a.hyp_counts ? min(max(a.hyp_counts[on], 0), a.K) : a.K;
+    if (!best) return present > 0 ? 0 : -1;
+    const int k = best[on];
+    if (k < 0) return k == -1 ? -1 : -2;
+    return k < present ? k : -2;
+}
+
+// A row with an empty side: m deletions or n insertions (or nothing), 64 per step.  Returns the number of events.
+__device__ __forceinline__ int pure_confusions(const int32_t* A, int m, const int32_t* B, int nb, ConfusionSink& sink, int lane) {
+    for (int q = lane; q < m; q += WAVE) sink.add(A[q], -1);
+    for (int q = lane; q < nb; q += WAVE) sink.add(-1, B[q]);
+    return m + nb;
+}
+
+// The back-trace of walk_operations with every move an event (expected id, actual id): a diagonal move names both symbols,
+// match or substitution alike, a deletion (A[i], epsilon), an insertion (epsilon, B[j]).  `count` is the number of
+// operations, as there: after them the walk stands on a cell of cost 0, where i == j and everything below is diagonal, so the
+// pairs (A[q], B[q]), q < i, follow without code words, 64 per step.  Wave-uniform; events are staged one per lane and added
+// 64 at a time.  Returns the number of events, m + n - #diagonal.
+__device__ __forceinline__ int walk_confusions(const uint4* codes, int64_t stride, const int32_t* A, int m, const int32_t* B,
+                                               int nb, int count, ConfusionSink& sink, int lane) {
+    int i = m, j = nb, k = 0, events = 0, added = 0;
+    int win_s = -1, win_t = 0;  // the loaded window: strip win_s, steps [win_t, win_t + 64)
+    uint4 w = make_uint4(0, 0, 0, 0);
+    int ev_i = -1, ev_j = -1;  // lane q stages event added + q: its indices into A and B, -1 for epsilon
+    while (k < count && (i > 0 || j > 0)) {
+        int act = 0;  // 0: a match
+        if (i == 0) {
+            act = AMX_EDIT_INSERTION, --j;
+        } else if (j == 0) {
+            act = AMX_EDIT_DELETION, --i;
+        } else {
+            const int s = (i - 1) / WAVE, l = (i - 1) % WAVE, t = j + l;
+            if (s != win_s || t < win_t) {
+                win_s = s, win_t = max(0, t - (WAVE - 1));
+                w = codes[s * stride + win_t + lane];  // win_t + 63 <= max(t, 63) < code_stride
+            }
+            const int q = t - win_t, bit = l & 31;
+            const bool diag = ((uint32_t)lane_value(l < 32 ? w.x : w.y, q) >> bit) & 1;
+            const bool second = ((uint32_t)lane_value(l < 32 ? w.z : w.w, q) >> bit) & 1;
+            if (diag) {
+                --i, --j;
+                if (second) act = AMX_EDIT_SUBSTITUTION;
+            } else if (second) {
+                act = AMX_EDIT_DELETION, --i;
+            } else {
+                act = AMX_EDIT_INSERTION, --j;
+            }
+        }
+        if (lane == events - added) {  // the coordinates after the move
+            ev_i = act != AMX_EDIT_INSERTION ? i : -1;
+            ev_j = act != AMX_EDIT_DELETION ? j : -1;
+        }
+        ++events;
+        if (act != 0) ++k;
+        if (events - added == WAVE) {
+            sink.add(ev_i >= 0 ? A[ev_i] : -1, ev_j >= 0 ? B[ev_j] : -1);
+            added = events;
+        }
+    }
+    if (lane < events - added) sink.add(ev_i >= 0 ? A[ev_i] : -1, ev_j >= 0 ? B[ev_j] : -1);
+    const int tail = min(i, j);  // (equal wherever the loop ends)
+    for (int q = lane; q < tail; q += WAVE) sink.add(A[q], B[q]);
+    return events + tail;
 }
 
 // The candidate choice, one thread per (output, utterance) in blocks of SELECT_THREADS: the first candidate of strictly

@@ -18,6 +18,9 @@ or the category ``feature_values(name, token - 1)``; the blank expands to nothin
 ``PropertyWeighting`` is upstream's class of that name (edit_distance.rs:498-599): fp32 insertion and deletion costs and, as the
 substitution cost, the number of features in which two phonemes' rows of a property table differ, through the
 ``amx_edit_weighted_*`` / ``amx_edit_matrix`` kernels.  ``Evaluator(weighting=...)`` scores the IPA outputs under it.
+
+``Evaluator(confusions=True)`` also keeps confusion tables (confusion.py): every ``add`` hands the candidates it has just
+chosen to the ``amx_edit_confusions`` kernel, and ``Evaluator.confusions`` fetches the accumulated ``ConfusionTable``.
 """
 from __future__ import annotations
 
@@ -33,12 +36,13 @@ import torch
 from torch import Tensor
 
 from . import lib as _lib
+from .confusion import ConfusionCounts, ConfusionTable
 from .phonetic import IPA_LAYERS, AttributeTable, InventoryView, split_complex_segment
 
 __all__ = ["EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "EvaluationMaps", "Evaluator", "LabelBatch", "levensthein_statistics",
            "levensthein_statistics_batch", "unicode_replacements", "Action", "UtteranceEdits", "levensthein_operations",
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
-           "levensthein_matrix"]
+           "levensthein_matrix", "levensthein_confusions_batch"]
 
 TOTAL = "total"
 STATISTICS_FIELDS = ("insertions", "deletions", "substitutions", "correct")  # the kernel's order
@@ -531,7 +535,7 @@ class Evaluator:
     def __init__(self, table: AttributeTable, names: Sequence[str], inventory: Union[InventoryView, Sequence[str]],
                  languages: Sequence[str], split_complex: bool = False,
                  source_maps: Optional[Dict[str, Dict[str, str]]] = None, replacements: Optional[Dict[str, str]] = None,
-                 device=None, weighting: Optional["PropertyWeighting"] = None):
+                 device=None, weighting: Optional["PropertyWeighting"] = None, confusions: Union[bool, int] = False):
         self.device = _device(device)
         self.maps = EvaluationMaps(table, names, inventory, languages, split_complex, source_maps, replacements)
         self.weighting = weighting
@@ -548,6 +552,15 @@ class Evaluator:
         self._rows: Optional[Tuple[Tensor, Tensor]] = None
         self._costs: Optional[Tensor] = None
         self._operation_costs: Optional[Tensor] = None
+        # confusion tables: one accumulator for the uniform kernels' outputs, or one per part under a weighting (a key
+        # holds the output's index within its call)
+        self._confusions: Optional[List[Tuple[List[int], ConfusionCounts]]] = None
+        self._confusion_events: Optional[Tensor] = None
+        if confusions is not False:
+            capacity = 2 ** 20 if confusions is True else int(confusions)
+            parts = [list(range(len(self.names)))] if weighting is None else [index.tolist() for index, _, _, _ in self._parts]
+            self._confusions = [(outputs, ConfusionCounts(self.device, capacity, self.languages, [self.names[o] for o in outputs],
+                                                          [list(self.maps.spaces[o]) for o in outputs])) for outputs in parts]
 
     def _init_weighting(self, weighting: "PropertyWeighting") -> None:
         """Splits the outputs into the IPA ones, scored under ``weighting`` with one cost table per id space, and the
@@ -587,6 +600,13 @@ class Evaluator:
                 None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
                 self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual,
                 self._part_workspaces.get((p, False)), totals, weights)
+            if self._confusions is not None:
+                if p == 0:
+                    self._confusion_events = torch.empty(O, N, dtype=torch.int32, device=self.device)
+                self._confusion_events[index] = self._confusions[p][1].add_rows(
+                    tokens.index_select(0, index), counts.index_select(0, index),
+                    None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
+                    self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual, part_best, weights)
             statistics.index_copy_(0, index, part_statistics)
             best.index_copy_(0, index, part_best)
             costs.index_copy_(0, index, _unit_costs(part_statistics) if part_costs is None else part_costs)
@@ -617,6 +637,31 @@ class Evaluator:
 
     def reset(self) -> None:
         self.totals.zero_()
+        for _, counts in self._confusions or []:
+            counts.reset()
+
+    def confusion_events(self) -> Tensor:
+        """Of the last ``add`` with confusion tables: int32 [O, N], the number of events that each row's chosen candidate
+        contributed; -1 for a row without a chosen candidate and -2 for a flagged row, which add nothing.  A device tensor."""
+        if self._confusion_events is None:
+            raise ValueError("nothing added with confusion tables yet")
+        return self._confusion_events
+
+    def confusions(self) -> ConfusionTable:
+        """The confusion table of everything added since the last ``reset`` (``Evaluator(confusions=True)``): the events of
+        the candidates that the statistics chose, per language and output, ids in ``maps.spaces[o]``.  One host
+        synchronisation per accumulator; ``OverflowError`` if events were dropped (build the evaluator with a larger
+        ``confusions=capacity``)."""
+        if self._confusions is None:
+            raise ValueError("this evaluator keeps no confusion tables: build it with confusions=True")
+        columns: List[List[np.ndarray]] = [[] for _ in range(5)]
+        for outputs, counts in self._confusions:
+            part = counts.fetch()
+            for column, values in zip(columns, (part.group, np.asarray(outputs, dtype=np.int64)[part.output], part.expected,
+                                                part.actual, part.count)):
+                column.append(values)
+        return ConfusionTable(self.languages, self.names, [list(space) for space in self.maps.spaces],
+                              *(np.concatenate(column) for column in columns))
 
     def encode_labels(self, labels: Sequence[Sequence[str]], languages: Sequence[Union[str, int]]) -> "LabelBatch":
         """Encodes a batch's labels (per utterance its phoneme strings) and languages (codes of ``languages`` or their
@@ -678,6 +723,10 @@ class Evaluator:
             self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
             self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._workspace, self.totals)
         self._rows, self._costs = (statistics, best), None
+        if self._confusions is not None:  # the same stream, after the choice
+            self._confusion_events = self._confusions[0][1].add_rows(
+                tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets, self._label_maps,
+                self._hyp_maps, self.maps.H, labels.max_expected, max_actual, best)
 
     def operations(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
                    languages: Optional[Sequence[Union[str, int]]] = None) -> Tuple[Tensor, Tensor]:
@@ -858,6 +907,34 @@ def levensthein_operations_batch(expected: Sequence[Sequence[Hashable]], actual:
             for n in range(N)]
 
 
+def _pair_confusions(p: _Pairs, device: torch.device, weights: Optional[_Weights] = None, capacity: Optional[int] = None
+                     ) -> Tuple[ConfusionCounts, Tensor]:
+    """One confusion call over the pairs of ``p`` into a new table (by default large enough for every key the pairs can
+    give); returns the accumulator and ``row_events`` int32 [1, N]."""
+    N = p.tokens.shape[1]
+    if capacity is None:
+        keys = min((p.V + 1) ** 2, int(p.counts.sum()) + p.labels.numel())  # distinct pairs; events
+        capacity = 16
+        while capacity < 2 * keys:
+            capacity *= 2
+    counts = ConfusionCounts(device, capacity, [TOTAL], ["pairs"], [p.symbols])
+    row_events = counts.add_rows(p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
+                                 p.max_expected, p.T, None, weights)
+    return counts, row_events
+
+
+def levensthein_confusions_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                 device=None) -> ConfusionTable:
+    """The confusion table of the pairs (expected[i], actual[i]) under unit costs, on the device: one language (``"total"``)
+    and one output (``"pairs"``), which ``ConfusionTable``'s methods default to."""
+    if len(expected) != len(actual):
+        raise ValueError("expected and actual differ in length")
+    if len(expected) == 0:
+        return ConfusionTable([TOTAL], ["pairs"], [[]], [], [], [], [], [])
+    device = _device(device)
+    return _pair_confusions(_pairs(expected, actual, device), device)[0].fetch()
+
+
 def levensthein_operations(expected: Sequence[Hashable], actual: Sequence[Hashable], device=None
                            ) -> Tuple[List[Operation], float]:
     """Upstream's ``phonemes.levensthein_operations(string_a=expected, string_b=actual)`` on the device: the first best path's
@@ -993,6 +1070,15 @@ class PropertyWeighting:
         """Upstream's ``PropertyWeighting.levensthein_operations``: the first best path's operations (action, i, j) in order,
         and the fp32 cost."""
         return self.levensthein_operations_batch([expected], [actual], device)[0]
+
+    def levensthein_confusions_batch(self, expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
+                                     device=None) -> ConfusionTable:
+        """The confusion table of the pairs on this weighting's paths (see the module-level function): a pair of different
+        symbols with equal rows is a match of the path and an off-diagonal entry of the table."""
+        if len(expected) == 0 and len(actual) == 0:
+            return ConfusionTable([TOTAL], ["pairs"], [[]], [], [], [], [], [])
+        device, p, weights = self._prepare(expected, actual, device)
+        return _pair_confusions(p, device, weights)[0].fetch()
 
     def levensthein_matrix_batch(self, expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
                                  device=None) -> List[Tensor]:

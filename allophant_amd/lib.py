@@ -52,6 +52,9 @@ RESAMPLE_MAX_WINDOW = 16384  # AMX_RESAMPLE_MAX_WINDOW
 EDIT_EXPORTS = ["amx_edit_workspace", "amx_edit_statistics", "amx_edit_operations_workspace", "amx_edit_operations"]
 EDIT_WEIGHTED_EXPORTS = ["amx_edit_cost_table_bytes", "amx_edit_cost_table", "amx_edit_weighted_statistics",
                          "amx_edit_weighted_operations", "amx_edit_matrix"]
+EDIT_CONFUSION_EXPORTS = ["amx_edit_confusion_table_bytes", "amx_edit_confusions", "amx_edit_weighted_confusions",
+                          "amx_edit_confusion_merge"]  # (added to ABI 7, detected by name)
+EDIT_CONFUSION_GROUP_BITS, EDIT_CONFUSION_SYMBOL_BITS = 22, 21  # AMX_EDIT_CONFUSION_GROUP_BITS / _SYMBOL_BITS
 EDIT_MAX_LENGTH = 65535  # AMX_EDIT_MAX_LENGTH
 EDIT_MAX_SYMBOLS = 8192  # AMX_EDIT_MAX_SYMBOLS
 EDIT_MAX_FEATURES = 255  # AMX_EDIT_MAX_FEATURES
@@ -200,6 +203,17 @@ def load() -> C.CDLL:
         lib.amx_edit_weighted_operations.restype = i32
         lib.amx_edit_matrix.argtypes = [i32, vp, vp, vp, vp, i64, i64, i64, f32, f32, vp, i64, vp, C.c_size_t, vp, vp, vp]
         lib.amx_edit_matrix.restype = i32
+    if hasattr(lib, "amx_edit_confusions"):  # (added to ABI 7 by name: absent from older builds)
+        head = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64, i64, vp, C.c_size_t]
+        tail = [vp, vp, i64, vp, vp, vp]  # best, table, capacity, row_events, counters, stream
+        lib.amx_edit_confusion_table_bytes.argtypes = [i64, C.POINTER(C.c_size_t)]
+        lib.amx_edit_confusion_table_bytes.restype = i32
+        lib.amx_edit_confusions.argtypes = head + tail
+        lib.amx_edit_confusions.restype = i32
+        lib.amx_edit_weighted_confusions.argtypes = head + [C.c_float, C.c_float, vp, vp] + tail
+        lib.amx_edit_weighted_confusions.restype = i32
+        lib.amx_edit_confusion_merge.argtypes = [i32, vp, i64, vp, i64, vp, vp]
+        lib.amx_edit_confusion_merge.restype = i32
     if hasattr(lib, "amx_ctc_align"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_ctc_align_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
         lib.amx_ctc_align_workspace.restype = i32

@@ -173,6 +173,76 @@ int amx_edit_matrix(int device, const int32_t* expected_offsets, const int32_t* 
                     float deletion_cost, const uint8_t* cost_table, int64_t V, void* workspace, size_t workspace_bytes,
                     float* matrix, int32_t* status, void* stream);
 
+/* Confusion tables: which symbol is taken for which, what is deleted and inserted, and how often each symbol is right, per
+ * (group, output), accumulated on the device over any number of calls.  Added to ABI 7 without a struct change (detect the
+ * symbols with dlsym).  The contract is restated in DESIGN 9 and, as Python, in tests/confusion_util.py.
+ *
+ * A scored row, with expanded expected A[0, m) and actual B[0, n), contributes the EVENTS of upstream's back-trace from (m, n)
+ * (the path of amx_edit_statistics and amx_edit_operations, same tie-breaking), continued to the origin where upstream's walk
+ * stops at cost 0 (below such a cell every move is diagonal and i == j): a diagonal move is the event (A[i-1], B[j-1]), match
+ * and substitution alike; a deletion (A[i-1], eps); an insertion (eps, B[j-1]).  That is m + n - #diagonal events.  Summed over
+ * a row, events with eps on neither side and expected != actual are its S, (e, eps) its D, (eps, a) its I and (e, e) its C
+ * (weighted costs: pairs of table cost 0 are C, pairs of cost > 0 are S).
+ *
+ * TABLE: `capacity` slots of 16 bytes in device memory, a slot a uint64 key followed by a uint64 count.  Key 0 is an empty
+ * slot: the caller zeroes a new table.  An occupied slot's key packs
+ *     (g * O + o + 1) << 42 | (expected id + 1) << 21 | (actual id + 1)          eps: id -1, i.e. the field 0
+ * (AMX_EDIT_CONFUSION_GROUP_BITS / _SYMBOL_BITS: 22 / 21 / 21 bits; ids are those of the output's id space, what the maps
+ * expand to).  A row whose symbol ids exceed 2^21 - 2, or any row when G * O exceeds 2^22 - 1, is flagged -2 rather than
+ * truncated.  A key lives in the first free slot of the linear probe sequence that starts at hash(key) & (capacity - 1); an
+ * empty slot is claimed with a 64-bit compare-and-swap and counts grow by 64-bit integer atomic adds only, so every count is
+ * the same whatever the order of arrival and a table is bitwise reproducible once its occupied slots are sorted by key.  SLOT
+ * POSITIONS ARE NOT reproducible: they depend on which key arrives first.  A probe sequence ends after `capacity` slots; an
+ * event that finds none is added to counters[1] and otherwise lost (a full table cannot spin).
+ *
+ *   counters  uint64 [2]: [0] events added to the table (the sum of its counts), [1] events dropped.  Accumulated, never
+ *             cleared: the caller zeroes them with the table. */
+#define AMX_EDIT_CONFUSION_GROUP_BITS 22
+#define AMX_EDIT_CONFUSION_SYMBOL_BITS 21
+#define AMX_EDIT_CONFUSION_MIN_CAPACITY 16
+#define AMX_EDIT_CONFUSION_MAX_CAPACITY (1 << 28)
+
+/* Pure host function (no device, no HIP call): bytes of a table of `capacity` slots (16 * capacity).  `capacity` must be a
+ * power of two, AMX_EDIT_CONFUSION_MIN_CAPACITY <= capacity <= AMX_EDIT_CONFUSION_MAX_CAPACITY (AMX_EINVAL otherwise). */
+int amx_edit_confusion_table_bytes(int64_t capacity, size_t* bytes);
+
+/* Adds the events of one candidate of every (output, utterance) row to `table`.  Arguments up to workspace_bytes as
+ * amx_edit_statistics (tokens [O, N, K, T], counts [O, N, K], the same limits), except that the workspace is that of
+ * amx_edit_operations_workspace(O * N, max_expected, max_actual).  All pointers are DEVICE pointers:
+ *   best        int32 [O, N] as amx_edit_statistics wrote it, or NULL.  Row (o, n) walks candidate best[o, n]; best == -1 gives
+ *               row_events -1 and best == -2 (or a best at or past the candidates present) row_events -2, and such a row adds
+ *               nothing.  NULL: candidate 0, and a row whose hyp_counts is 0 (or less) has no candidate
+ *   table, capacity   as above
+ * and writes
+ *   row_events  int32 [O, N]: the number of events of the row (added or dropped); -1 for a row with no candidate; -2 for a row
+ *               flagged as amx_edit_operations flags it, or whose ids do not fit a key: nothing out of range is read and
+ *               nothing of the row is added
+ *   counters    as above
+ * One launch, stream-ordered on `stream`: no allocation and no host synchronisation (the call can be captured in a graph). */
+int amx_edit_confusions(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O, int N,
+                        int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets,
+                        const int32_t* label_ids, const int32_t* groups, int G, const int32_t* map_offsets,
+                        const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
+                        int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes, const int32_t* best,
+                        void* table, int64_t capacity, int32_t* row_events, uint64_t* counters, void* stream);
+
+/* amx_edit_confusions on the path of the weighted costs: cost arguments, their limits and the extra flag (a symbol outside its
+ * output's cost table: -2) as amx_edit_weighted_operations; `best` as amx_edit_weighted_statistics wrote it.  One launch. */
+int amx_edit_weighted_confusions(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O,
+                                 int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
+                                 const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
+                                 const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
+                                 const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual, void* workspace,
+                                 size_t workspace_bytes, float insertion_cost, float deletion_cost, const int64_t* cost_tables,
+                                 const uint8_t* cost_table_data, const int32_t* best, void* table, int64_t capacity,
+                                 int32_t* row_events, uint64_t* counters, void* stream);
+
+/* Adds every occupied slot of `src` (key, count) into `dst`: growing a table (into a zeroed larger one) or combining two.  The
+ * tables must not overlap.  counters[0] grows by the events that found a slot in `dst`, counters[1] by those that did not (a
+ * `dst` that is too small).  One launch over the slots of `src`, stream-ordered on `stream`. */
+int amx_edit_confusion_merge(int device, const void* src, int64_t src_capacity, void* dst, int64_t dst_capacity,
+                             uint64_t* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
