@@ -10,7 +10,7 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "BeamDecoded", "feature_decoders", "EditStatistics", "EvaluationResults", "MultilingualEvaluationResults", "Evaluator",
            "levensthein_statistics", "levensthein_statistics_batch", "Action", "UtteranceEdits", "levensthein_operations",
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
-           "levensthein_matrix", "levensthein_confusions_batch", "ConfusionCounts", "ConfusionTable", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "Score", "Scored",
+           "levensthein_matrix", "levensthein_confusions_batch", "ConfusionCounts", "ConfusionTable", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "segments", "Score", "Scored",
            "Rescored", "ctc_score", "Found", "Hit", "ctc_search", "pick_hits", "query_targets", "LongPlan", "plan_windows",
            "gather_windows", "stitch_windows"]
 __version__ = "0.1.0"
@@ -30,7 +30,7 @@ def __getattr__(name):
         from . import evaluation
 
         return getattr(evaluation, name)
-    if name in ("Alignment", "Aligned", "ctc_forced_align", "label_targets"):
+    if name in ("Alignment", "Aligned", "ctc_forced_align", "label_targets", "segments"):
         from . import alignment
 
         return getattr(alignment, name)

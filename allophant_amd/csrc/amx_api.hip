@@ -2410,10 +2410,10 @@ extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_
 // CTC forced alignment
 // =================================================================================================================
 namespace {
-int align_check(amx_handle h, int64_t rows, int64_t T, int64_t max_target) {
+int align_check(amx_handle h, int64_t rows, int64_t T, int64_t max_target, int64_t limit = AMX_ALIGN_MAX_TARGET) {
     if (rows < 0 || T < 0) return fail(h, AMX_EINVAL, "negative alignment geometry");
-    if (max_target < 0 || max_target > AMX_ALIGN_MAX_TARGET)
-        return fail(h, AMX_EINVAL, "max_target must be 0 to " + std::to_string(AMX_ALIGN_MAX_TARGET) + ", got " + std::to_string(max_target));
+    if (max_target < 0 || max_target > limit)
+        return fail(h, AMX_EINVAL, "max_target must be 0 to " + std::to_string(limit) + ", got " + std::to_string(max_target));
     int64_t cells = 0;
     if (__builtin_mul_overflow(rows, T, &cells) || cells > INT32_MAX) return fail(h, AMX_EINVAL, "rows * T must be below 2^31");
     return AMX_OK;
@@ -2423,21 +2423,68 @@ int align_check_classes(amx_handle h, int C, int blank) {
     if (blank < 0 || blank >= C) return fail(h, AMX_EINVAL, "blank_index out of range");
     return AMX_OK;
 }
-// amx_ctc_align / amx_ctc_align_emissions from the workspace check on: `c` holds the emission source and the row count
+// false when the size is not representable in size_t
+bool align_workspace_bytes(bool long_form, int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
+    if (!long_form) return ctc_align_workspace_bytes(rows, T, max_target, bytes);
+    AlignLongLayout at;
+    if (!ctc_align_long_layout(rows, T, max_target, &at)) return false;
+    *bytes = at.bytes;
+    return true;
+}
+// amx_ctc_align / amx_ctc_align_emissions and their long forms from the workspace check on: `c` holds the emission source and
+// the row count
 int align_rows(amx_handle h, int device, CtcRows c, const int64_t* host_lengths, const int32_t* target_offsets,
                const int32_t* target_ids, int64_t max_target, void* workspace, size_t workspace_bytes, int32_t* paths,
-               float* frame_scores, int32_t* spans, float* span_scores, float* totals, int32_t* status, hipStream_t s) {
+               float* frame_scores, int32_t* spans, float* span_scores, float* totals, int32_t* status, hipStream_t s,
+               bool long_form = false) {
     size_t need = 0;
-    if (!ctc_align_workspace_bytes(c.rows, c.T, max_target, &need)) return fail(h, AMX_EINVAL, "alignment workspace size not representable");
+    if (!align_workspace_bytes(long_form, c.rows, c.T, max_target, &need))
+        return fail(h, AMX_EINVAL, "alignment workspace size not representable");
     if (int rc = check_workspace(h, "alignment", need, workspace, workspace_bytes)) return rc;
     if (int rc = ctc_rows_begin(h, device, host_lengths, &c, s)) return rc;
     c.target_offsets = target_offsets, c.target_ids = target_ids, c.max_target = (int)max_target;
-    AlignArgs a{};
+    AlignLongArgs a{};
     static_cast<CtcRows&>(a) = c;
     a.workspace = (uint4*)workspace;
     a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
-    launch_ctc_align(a, s);
+    if (long_form)
+        launch_ctc_align_long(a, s);
+    else
+        launch_ctc_align(a, s);
     return ctc_launched(h, "alignment");
+}
+// the two forms of amx_ctc_align_emissions and of amx_ctc_align
+int align_emissions(bool long_form, int device, const float* emissions, int64_t stride_n, int64_t stride_t, const int32_t* frame_lengths,
+                    int N, int64_t T, int C, int blank_index, const int32_t* target_offsets, const int32_t* target_ids,
+                    int64_t max_target, void* workspace, size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans,
+                    float* span_scores, float* totals, int32_t* status, void* stream) {
+    if (int rc = align_check(nullptr, N, T, max_target, long_form ? AMX_ALIGN_LONG_MAX_TARGET : AMX_ALIGN_MAX_TARGET)) return rc;
+    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
+    if (N == 0) return AMX_OK;
+    if (!frame_lengths || !target_offsets || !totals || !status || (T && (!emissions || !paths || !frame_scores)) ||
+        (max_target && (!target_ids || !spans || !span_scores)))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    const CtcRows c = rows_of_tensor(emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    return align_rows(nullptr, device, c, nullptr, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths,
+                      frame_scores, spans, span_scores, totals, status, (hipStream_t)stream, long_form);
+}
+int align_handle(bool long_form, amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
+                 const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace, size_t workspace_bytes,
+                 int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores, float* totals, int32_t* status, void* stream) {
+    if (!h) return AMX_EINVAL;
+    if (!out || !frame_lengths || !target_offsets || !paths || !frame_scores || !totals || !status ||
+        (max_target > 0 && (!target_ids || !spans || !span_scores)))
+        return fail(h, AMX_EINVAL, "null buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    CtcRows c;
+    int rc = rows_of_handle(h, out, N, L, &c);
+    if (rc) return rc;
+    if ((rc = align_check(h, c.rows, c.T, max_target, long_form ? AMX_ALIGN_LONG_MAX_TARGET : AMX_ALIGN_MAX_TARGET))) return rc;
+    if (c.rows == 0) return AMX_OK;
+    for (const OutDesc& d : h->out_all)
+        if ((rc = align_check_classes(h, d.C, 0))) return rc;
+    return align_rows(h, 0, c, frame_lengths, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths, frame_scores,
+                      spans, span_scores, totals, status, (hipStream_t)stream, long_form);
 }
 }  // namespace
 
@@ -2453,35 +2500,40 @@ extern "C" int amx_ctc_align_emissions(int device, const float* emissions, int64
                                        const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
                                        size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores,
                                        float* totals, int32_t* status, void* stream) {
-    if (int rc = align_check(nullptr, N, T, max_target)) return rc;
-    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
-    if (N == 0) return AMX_OK;
-    if (!frame_lengths || !target_offsets || !totals || !status || (T && (!emissions || !paths || !frame_scores)) ||
-        (max_target && (!target_ids || !spans || !span_scores)))
-        return fail(nullptr, AMX_EINVAL, "null buffer");
-    const CtcRows c = rows_of_tensor(emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
-    return align_rows(nullptr, device, c, nullptr, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths,
-                      frame_scores, spans, span_scores, totals, status, (hipStream_t)stream);
+    return align_emissions(false, device, emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index, target_offsets, target_ids,
+                           max_target, workspace, workspace_bytes, paths, frame_scores, spans, span_scores, totals, status, stream);
 }
 
 extern "C" int amx_ctc_align(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
                              const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
                              size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores,
                              float* totals, int32_t* status, void* stream) {
-    if (!h) return AMX_EINVAL;
-    if (!out || !frame_lengths || !target_offsets || !paths || !frame_scores || !totals || !status ||
-        (max_target > 0 && (!target_ids || !spans || !span_scores)))
-        return fail(h, AMX_EINVAL, "null buffer");
-    HIPCHK(h, hipSetDevice(h->device));
-    CtcRows c;
-    int rc = rows_of_handle(h, out, N, L, &c);
-    if (rc) return rc;
-    if ((rc = align_check(h, c.rows, c.T, max_target))) return rc;
-    if (c.rows == 0) return AMX_OK;
-    for (const OutDesc& d : h->out_all)
-        if ((rc = align_check_classes(h, d.C, 0))) return rc;
-    return align_rows(h, 0, c, frame_lengths, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths, frame_scores,
-                      spans, span_scores, totals, status, (hipStream_t)stream);
+    return align_handle(false, h, out, frame_lengths, N, L, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths,
+                        frame_scores, spans, span_scores, totals, status, stream);
+}
+
+extern "C" int amx_ctc_align_long_workspace(int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = align_check(nullptr, rows, T, max_target, AMX_ALIGN_LONG_MAX_TARGET)) return rc;
+    if (!align_workspace_bytes(true, rows, T, max_target, bytes)) return fail(nullptr, AMX_EINVAL, "alignment workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_align_long_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                            const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index,
+                                            const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target,
+                                            void* workspace, size_t workspace_bytes, int32_t* paths, float* frame_scores,
+                                            int32_t* spans, float* span_scores, float* totals, int32_t* status, void* stream) {
+    return align_emissions(true, device, emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index, target_offsets, target_ids,
+                           max_target, workspace, workspace_bytes, paths, frame_scores, spans, span_scores, totals, status, stream);
+}
+
+extern "C" int amx_ctc_align_long(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
+                                  const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
+                                  size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores,
+                                  float* totals, int32_t* status, void* stream) {
+    return align_handle(true, h, out, frame_lengths, N, L, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths,
+                        frame_scores, spans, span_scores, totals, status, stream);
 }
 
 // =================================================================================================================

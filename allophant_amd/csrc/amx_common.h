@@ -542,7 +542,7 @@ void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t
 // emissions lie and which target rows are run over them.  With `descs` the emissions are every output block of the output
 // buffer (blank 0), else the N utterances of one [N, T, C] tensor read with element strides (stride_n, stride_t, 1).  Row r
 // has the targets target_ids[target_offsets[r] .. target_offsets[r + 1]); its S = 2 * targets + 1 states are cut into strips
-// of one wave.  Limits (checked by the callers): 2 <= C, 0 <= max_target <= 4095, rows * T < 2^31.
+// of one wave.  Limits (checked by the callers): 2 <= C, 0 <= max_target <= 4095 (the long alignment: 262143), rows * T < 2^31.
 constexpr int CTC_WAVE = 64;  // wave size, states per strip
 constexpr int ALIGN_MAX_WAVES = 16;
 constexpr int64_t ctc_strips(int64_t max_target) { return (2 * max_target + 1 + CTC_WAVE - 1) / CTC_WAVE; }
@@ -571,6 +571,26 @@ struct AlignArgs : CtcRows {
 // false when the size is not representable in size_t
 bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
 void launch_ctc_align(AlignArgs a, hipStream_t s);
+
+// The same contract for rows of up to AMX_ALIGN_LONG_MAX_TARGET targets (amx_ctc_align_long.hip): one launch per block of
+// ALIGN_LONG_FRAMES frames over a grid of (state tiles, rows); a tile owns ALIGN_LONG_OWNED states and recomputes a left halo
+// of ALIGN_LONG_HALO.  Besides the moves the workspace holds two state rows per row (strips * 64 floats each, ping-ponged by
+// block parity), the span bounds [rows, max_target, 2] and a live flag per row; the launcher places them (AlignLongLayout).
+constexpr int ALIGN_LONG_FRAMES = 64;
+constexpr int ALIGN_LONG_OWNED = 832;  // 13 strips: not a multiple of the 128 states that the steepest path crosses per frame block
+constexpr int ALIGN_LONG_HALO = 2 * ALIGN_LONG_FRAMES;
+struct AlignLongArgs : AlignArgs {
+    float* states;
+    int32_t* bounds;
+    int32_t* live;
+    int64_t row_base;  // the first row of this launch (the rows are launched in chunks that fit a grid)
+};
+struct AlignLongLayout {
+    size_t states, bounds, live, bytes;  // byte offsets of the sections after the moves (at 0), and the total
+};
+// false when the size is not representable in size_t
+bool ctc_align_long_layout(int64_t rows, int64_t T, int64_t max_target, AlignLongLayout* out);
+void launch_ctc_align_long(AlignLongArgs a, hipStream_t s);
 
 // CTC forward-backward scoring (amx_ctc_score.hip), one workgroup per row (o * N + n) * G + g (with `descs`) or n * G + g,
 // G = candidates: contract in include/allophant_amx_score.h.  The workspace holds per row and frame strips * 64 forward

@@ -60,17 +60,18 @@ def frame(log_emissions: Tensor, lengths: Optional[Tensor]) -> Frame:
                  torch.cuda.current_stream(device).cuda_stream)
 
 
-def pack_targets(rows: Sequence[Sequence[int]], utterances: Optional[int] = None, candidates: int = 1
-                 ) -> Tuple[Tensor, Tensor, List[int]]:
+def pack_targets(rows: Sequence[Sequence[int]], utterances: Optional[int] = None, candidates: int = 1,
+                 limit: int = MAX_TARGET) -> Tuple[Tensor, Tensor, List[int]]:
     """Target rows as the C ABI takes them: int32 offsets ``[R + 1]``, int32 ids, and the rows' lengths (host tensors).  With
-    ``utterances`` the row count must be ``utterances * candidates`` (row ``n * candidates + g``)."""
+    ``utterances`` the row count must be ``utterances * candidates`` (row ``n * candidates + g``).  ``limit`` is the most
+    targets a row may have (``lib.ALIGN_LONG_MAX_TARGET`` for the long form of the alignment)."""
     if candidates < 1:
         raise ValueError("candidates must be at least 1")
     if utterances is not None and len(rows) != utterances * candidates:
         raise ValueError(f"{len(rows)} target rows for {utterances} emission rows x {candidates} candidates")
     counts = [len(row) for row in rows]
-    if counts and max(counts) > MAX_TARGET:
-        raise ValueError(f"at most {MAX_TARGET} targets per row on the device, got {max(counts)}")
+    if counts and max(counts) > limit:
+        raise ValueError(f"at most {limit} targets per row on the device, got {max(counts)}")
     offsets = torch.zeros(len(rows) + 1, dtype=torch.int32)
     if rows:
         offsets[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0).to(torch.int32)

@@ -32,7 +32,7 @@ from . import lib as _lib
 from . import scoring as _scoring
 from . import search as _search
 from . import spec as _spec
-from .alignment import Aligned, Alignment, ctc_forced_align, label_targets  # noqa: F401  (the façade's alignment names)
+from .alignment import Aligned, Alignment, ctc_forced_align, label_targets, segments  # noqa: F401  (the façade's names)
 from .scoring import Rescored, Score, Scored, ctc_score  # noqa: F401  (the façade's scoring names)
 from .search import Found, Hit, ctc_search, pick_hits, query_targets  # noqa: F401  (the façade's search names)
 
@@ -601,7 +601,8 @@ class Estimator:
         The result is an ordinary ``Predictions`` of the whole batch (layout of ``amx_output_layout(R, Lmax)``, ``lengths`` the
         recordings' frames, zeros beyond them; a recording below the receptive field has length 0): ``greedy_decode``,
         ``beam_decode``, ``align``, ``score``, ``search`` and ``Evaluator`` take it unchanged (``search`` keeps its
-        ``N * Q * T < 2^31`` limit).  Recordings that each fit one window, at most ``batch_windows`` of them, give the bits of
+        ``N * Q * T < 2^31`` limit; ``align`` takes up to 262 143 targets per row, a whole transcript, and ``score`` keeps its
+        4095).  Recordings that each fit one window, at most ``batch_windows`` of them, give the bits of
         ``predict(batch)``.
 
         What a window cannot see: ``do_normalize`` normalises each window on its own samples, as it does each utterance the
@@ -825,17 +826,24 @@ class Estimator:
         """``beam_decode_device`` fetched to the host: per output and utterance up to ``n_best`` hypotheses, best first."""
         return self.beam_decode_device(predictions, beam_width, n_best, exp_emissions).hypotheses()
 
-    def align_device(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]]) -> "_alignment.Aligned":
+    def align_device(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]],
+                     long: Optional[bool] = None) -> "_alignment.Aligned":
         """On-device CTC forced alignment (``amx_ctc_align``) of every output of ``predictions`` against ``targets``: output
         name -> one class-index sequence per utterance (``alignment.label_targets`` builds them from labels).  An output
-        without an entry is aligned against nothing and left out of ``Aligned.present``.  The result stays in HBM."""
+        without an entry is aligned against nothing and left out of ``Aligned.present``.  The result stays in HBM.  ``long``
+        as in ``alignment.ctc_forced_align``: a call whose largest row has more than ``ALIGN_MAX_TARGET`` targets (a whole
+        transcript on a ``predict_long`` result, up to ``ALIGN_LONG_MAX_TARGET``) runs ``amx_ctc_align_long``."""
         names, N, L, T, O, frame_lengths, lengths_pointer, stream = self._predictions_call(predictions)
-        offsets, ids, counts = _alignment.pack_targets(self._target_rows(predictions, targets, names, N, "align"))
+        rows = self._target_rows(predictions, targets, names, N, "align")
+        limit = _alignment.ALIGN_MAX_TARGET if long is False else _alignment.ALIGN_LONG_MAX_TARGET
+        offsets, ids, counts = _alignment.pack_targets(rows, limit=limit)
         max_target = max(counts)
+        long = _alignment.use_long(max_target, long)
+        entry = self._lib.amx_ctc_align_long if long else self._lib.amx_ctc_align
         with torch.cuda.device(self._device):
             meta = torch.cat([offsets, ids, torch.zeros(1, dtype=torch.int32)]).to(self._device)
-            b = _alignment.allocate(self._lib, O * N, T, max_target, self._device)
-            code = self._lib.amx_ctc_align(
+            b = _alignment.allocate(self._lib, O * N, T, max_target, self._device, long)
+            code = entry(
                 self._handle, C.c_void_p(predictions._flat.data_ptr()), lengths_pointer, N, L, C.c_void_p(meta.data_ptr()),
                 C.c_void_p(meta.data_ptr() + 4 * (O * N + 1)), max_target, *b.pointers(), C.c_void_p(stream))
             _lib.check(self._lib, self._handle, code)
@@ -844,11 +852,11 @@ class Estimator:
                                   b.span_scores.view(O, N, max_target), b.totals.view(O, N), b.status.view(O, N),
                                   frame_lengths.tolist(), [counts[o * N:(o + 1) * N] for o in range(O)])
 
-    def align(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]]
+    def align(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]], long: Optional[bool] = None
               ) -> Dict[str, List[Optional["_alignment.Alignment"]]]:
         """``align_device`` fetched to the host: per output with targets and utterance an ``Alignment`` (``None`` where no
         alignment exists)."""
-        return self.align_device(predictions, targets).alignments()
+        return self.align_device(predictions, targets, long).alignments()
 
     def _score_call(self, call, predictions: Predictions, candidates: int, meta: Tensor, max_target: int, posteriors: bool):
         """``amx_ctc_score`` over every output of ``predictions`` (``call`` is their ``_predictions_call``): ``meta`` holds the

@@ -62,6 +62,11 @@ EDIT_MAX_CANDIDATES = 64  # AMX_EDIT_MAX_CANDIDATES
 # the CTC forced-alignment entry points (include/allophant_amx_align.h; added to ABI 6, detected by name)
 ALIGN_EXPORTS = ["amx_ctc_align_workspace", "amx_ctc_align_emissions", "amx_ctc_align"]
 ALIGN_MAX_TARGET = 4095  # AMX_ALIGN_MAX_TARGET
+# the same contract for whole transcripts (the same header; added to ABI 6, detected by name)
+ALIGN_LONG_EXPORTS = ["amx_ctc_align_long_workspace", "amx_ctc_align_long_emissions", "amx_ctc_align_long"]
+ALIGN_LONG_MAX_TARGET = 262143  # AMX_ALIGN_LONG_MAX_TARGET
+ALIGN_LONG_FRAME_BLOCK = 64  # AMX_ALIGN_LONG_FRAME_BLOCK
+ALIGN_LONG_TILE_STATES = 832  # AMX_ALIGN_LONG_TILE_STATES
 # the CTC forward-backward scoring entry points (include/allophant_amx_score.h; added to ABI 6, detected by name)
 SCORE_EXPORTS = ["amx_ctc_score_workspace", "amx_ctc_score_emissions", "amx_ctc_score"]
 SCORE_MAX_TARGET = 4095  # AMX_SCORE_MAX_TARGET
@@ -222,6 +227,13 @@ def load() -> C.CDLL:
         lib.amx_ctc_align_emissions.restype = i32
         lib.amx_ctc_align.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
         lib.amx_ctc_align.restype = i32
+    if hasattr(lib, "amx_ctc_align_long"):  # (absent from older builds under AMX_ABI_OVERRIDE)
+        lib.amx_ctc_align_long_workspace.argtypes = lib.amx_ctc_align_workspace.argtypes
+        lib.amx_ctc_align_long_workspace.restype = i32
+        lib.amx_ctc_align_long_emissions.argtypes = lib.amx_ctc_align_emissions.argtypes
+        lib.amx_ctc_align_long_emissions.restype = i32
+        lib.amx_ctc_align_long.argtypes = lib.amx_ctc_align.argtypes
+        lib.amx_ctc_align_long.restype = i32
     if hasattr(lib, "amx_ctc_score"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_ctc_score_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
         lib.amx_ctc_score_workspace.restype = i32

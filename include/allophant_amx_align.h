@@ -63,6 +63,42 @@ int amx_ctc_align(amx_handle h, const float* out, const int64_t* frame_lengths, 
                   const int32_t* target_ids, int64_t max_target, void* workspace, size_t workspace_bytes, int32_t* paths,
                   float* frame_scores, int32_t* spans, float* span_scores, float* totals, int32_t* status, void* stream);
 
+/* The same contract for whole transcripts: rows of up to AMX_ALIGN_LONG_MAX_TARGET targets (symbols added to ABI 6; detect
+ * them with dlsym).  Recurrence, tie rule, end-state rule, walk, outputs and status codes are those above, and every output
+ * is bit for bit what the entry points above give on a row both accept: a cell's value depends only on the cells of its
+ * dependency cone, however the trellis is cut.  The states of a row are spread over the device: after one launch that
+ * validates the rows, one launch per block of AMX_ALIGN_LONG_FRAME_BLOCK frames runs a grid of (state tiles, rows), where a
+ * tile owns AMX_ALIGN_LONG_TILE_STATES states and recomputes a left halo of twice the frame block; one launch walks back and
+ * writes the outputs.  No workgroup waits for another: the only ordering between frame blocks is the stream's.
+ *
+ * Limits: those above with 0 <= max_target <= AMX_ALIGN_LONG_MAX_TARGET (any max_target from 0 up is accepted, so the small
+ * rows of the entry points above run here too).  Stream-ordered on `stream`: no allocation, no host synchronisation beyond
+ * what the forms above do, and a number of launches that depends on the geometry alone (2 + ceil(T / 64) per 65535 rows).
+ *
+ * The workspace, with strips = ceil((2 max_target + 1) / 64) and Tp = T padded to a multiple of 64, holds in this order
+ *   moves        rows * strips * Tp * 16 bytes   (as above)
+ *   state rows   rows * 2 * strips * 64 * 4      (the state row between launches, ping-ponged by the frame block's parity)
+ *   span bounds  rows * max_target * 2 * 4, rounded up to a multiple of 16
+ *   live flags   rows * 4, rounded up to a multiple of 16
+ * and amx_ctc_align_long_workspace returns the sum.  Its contents need not be initialised. */
+#define AMX_ALIGN_LONG_MAX_TARGET 262143 /* 524 287 states */
+#define AMX_ALIGN_LONG_FRAME_BLOCK 64    /* frames per launch */
+#define AMX_ALIGN_LONG_TILE_STATES 832   /* states a workgroup owns; it computes 128 more, its left halo */
+
+/* Pure host function; AMX_EINVAL when a limit is broken or the size is not representable in size_t. */
+int amx_ctc_align_long_workspace(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
+
+/* amx_ctc_align_emissions for rows of up to AMX_ALIGN_LONG_MAX_TARGET targets: the same arguments. */
+int amx_ctc_align_long_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t, const int32_t* frame_lengths,
+                                 int N, int64_t T, int C, int blank_index, const int32_t* target_offsets, const int32_t* target_ids,
+                                 int64_t max_target, void* workspace, size_t workspace_bytes, int32_t* paths, float* frame_scores,
+                                 int32_t* spans, float* span_scores, float* totals, int32_t* status, void* stream);
+
+/* amx_ctc_align for rows of up to AMX_ALIGN_LONG_MAX_TARGET targets: the same arguments. */
+int amx_ctc_align_long(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L, const int32_t* target_offsets,
+                       const int32_t* target_ids, int64_t max_target, void* workspace, size_t workspace_bytes, int32_t* paths,
+                       float* frame_scores, int32_t* spans, float* span_scores, float* totals, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
