@@ -215,6 +215,9 @@ struct amx_handle_s {
     int last_attention = -1;              // ... with this form of the attention kernels (AttnForm; -1: an encoder without layers)
     int64_t last_rows = 0;
     bool qkv_dirty = false;
+    // columns [dh, dhp) of the Q / K / V rows (head dimensions other than 64 and 128) may hold something else than zeros, anywhere in
+    // the allocations: only amx_debug_scribble makes it so -- no pass writes them -- and the next pass zeroes the buffers whole
+    bool qkv_pad_dirty = false;
     int64_t last_L = 0, last_T = 0;
     bool last_keep = false;
     // the last forward pass ran its heads on the packed rows of a ragged batch (packed_early): hidden states kept for
@@ -1320,7 +1323,7 @@ struct PassPlan {
     int64_t Ts[AMX_MAX_CONV + 1] = {};
     int T = 0, Tp = 0, TpTot = 0, Tpad = 0;
     int64_t M = 0, Mp = 0, Mrows = 0, Mh = 0, rows1 = 0, rows2 = 0, xp_plane = 0, qk_plane = 0;
-    size_t qkv_bytes = 0;
+    size_t qkv_bytes = 0, qkv_zero_bytes = 0;  // (of each of Q / K / V: what the pass uses, what it zeroes first when needs_qkv_zero)
     // the forms the pass takes
     bool keep = false, masked = true, stable = true, blanks = true;
     bool packed = false, packed_early = false, ragged = false, window_ok = false, needs_qkv_zero = false;
@@ -1704,6 +1707,13 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     P.blanks = c.dependency_blanks != 0;
     if ((rc = plan_concat(h, P, s))) return rc;
     P.needs_qkv_zero = !P.packed && (h->last_N != N || h->last_T != P.T || h->qkv_dirty);
+    P.qkv_zero_bytes = P.qkv_bytes;
+    if (h->qkv_pad_dirty && P.dh != P.dhp) {
+        // the pad columns of a row are never written, in either row layout, and packed rows of a later, larger batch lie anywhere
+        // in the allocation: all of it (the three buffers are asked for together, so they are of one size)
+        P.needs_qkv_zero = true;
+        P.qkv_zero_bytes = std::min({h->ws["q"].bytes, h->ws["k"].bytes, h->ws["vt"].bytes}) / 4 * 4;
+    }
     P.Mrows = P.packed ? P.Mp : P.M;  // rows the layers work on
     P.xp_plane = pln(h, P.Mrows * D);
     P.qk_plane = P.packed ? (int64_t)H * P.TpTot * P.dhp : (int64_t)N * H * P.Tp * P.dhp;
@@ -1756,9 +1766,9 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
     // K/V/Q padding rows [T, Tp) must stay finite: re-zero when the geometry changes
     // (zero fills inside a pass are kernels, never memsets: amx_rowops.hip, launch_zero)
     if (P.needs_qkv_zero) {
-        launch_zero(P.qb, P.qkv_bytes, s);
-        launch_zero(P.kb, P.qkv_bytes, s);
-        launch_zero(P.vtb, P.qkv_bytes, s);
+        launch_zero(P.qb, P.qkv_zero_bytes, s);
+        launch_zero(P.kb, P.qkv_zero_bytes, s);
+        launch_zero(P.vtb, P.qkv_zero_bytes, s);
     }
     if (P.packed) {
         // rows [Mp, TpTot) of every head are read (never used) by the last key tile and query block: keep them finite
@@ -2090,7 +2100,7 @@ static std::vector<int64_t> graph_key(amx_handle h, const PassPlan& P, const int
     std::vector<int64_t> key;
     key.reserve(10 + (size_t)P.N);
     key.insert(key.end(), {(int64_t)(intptr_t)P.d_audio, (int64_t)(intptr_t)P.d_out, (int64_t)P.N, P.L, (int64_t)P.flags,
-                           (int64_t)P.needs_qkv_zero, (int64_t)h->inv, (int64_t)cur_inv(h).generation, (int64_t)h->ws_gen});
+                           P.needs_qkv_zero ? (int64_t)P.qkv_zero_bytes : 0, (int64_t)h->inv, (int64_t)cur_inv(h).generation, (int64_t)h->ws_gen});
     // (the stream is part of the key: an executable graph is launched on one stream at a time -- a handle is meant for one
     // stream, include/allophant_amx.h, but a caller that moves to another one gets a recording of its own, not a shared one)
     key.push_back((int64_t)(intptr_t)s);
@@ -2208,6 +2218,7 @@ extern "C" int amx_forward(amx_handle h, const float* audio, const int64_t* leng
         h->last_frames = P.frames_host;
     }
     h->qkv_dirty = P.packed;  // a packed call leaves other rows in the Q / K / V planes: the next padded call re-zeroes them
+    if (P.dh != P.dhp) h->qkv_pad_dirty = false;  // (if it was set, this pass zeroed the allocations whole: plan_pass)
     // a host-I/O call has synchronised and handed the outputs over already: its own range report does not wait for the next call
     if ((flags & AMX_FLAG_HOST_IO) && !(flags & AMX_FLAG_NO_RANGE_CHECK) && (rc = range_poll(h, true))) return rc;
     return AMX_OK;
@@ -3296,5 +3307,37 @@ extern "C" int amx_debug_fetch(amx_handle h, int what, int index, float* host_ou
         return AMX_OK;
     }
     HIPCHK(h, hipMemcpy(host_out, src, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return AMX_OK;
+}
+
+// Test hook: every DATA workspace of the handle (ws_get), over its whole allocation -- the geometric slack included -- filled with
+// `word16` repeated, by kernels on `stream`.  A pass whose outputs change under it has read something it did not write (DESIGN.md,
+// "History independence").  Skipped are the workspaces from which a kernel forms an address, a loop bound or a grid; the plan (or
+// the decode call) uploads each of them whole in front of every use, so garbage in them could change nothing but, through a bug
+// of the hook's caller, an address:
+//   len         int64 sample counts: the loop bounds of the audio statistics and of conv layer 0
+//   frames      int32 frame counts: row masks, the key loops of the attention, the walk of the log-softmax
+//   rowoff      int32 packed-row offsets, the dispatch order and the encoder's frame counts: row addresses of every packed kernel
+//   conv_tiles  int32 tile indices of the conv layers of a ragged batch: the row a workgroup starts at
+//   ctc_frames  int32 frame counts of a decode / align / score call: the loop bounds of those kernels
+// Everything else in h->ws holds floating-point data (fp16 / bf16 planes, fp32 rows, the fp64 partials of the audio statistics and
+// of the GroupNorm) or, audio_host_io / out_host_io, staged samples and outputs.  Not touched: weights, inventories, the
+// concatenation recipes (plan_concat's parts_dev: pointers) and the non-finite counter -- all of them dev_alloc, none in h->ws.
+// The Q / K / V planes lose their "still zero" premise, so the handle is told: qkv_dirty for the padding rows, qkv_pad_dirty for
+// the columns [dh, dhp), which no pass writes (plan_pass).  Recordings stay: no pointer moves, and what a pass zeroes first is
+// part of the graph key.
+extern "C" int amx_debug_scribble(amx_handle h, uint32_t word16, void* stream) {
+    if (!h) return AMX_EINVAL;
+    if (word16 > 0xffffu) return fail(h, AMX_EINVAL, "the scribble pattern is one 16-bit word");
+    HIPCHK(h, hipSetDevice(h->device));
+    static const char* const skipped[] = {"len", "frames", "rowoff", "conv_tiles", "ctc_frames"};
+    for (auto& kv : h->ws) {
+        if (!kv.second.p || !kv.second.bytes) continue;
+        bool skip = false;
+        for (const char* name : skipped) skip |= kv.first == name;
+        if (!skip) launch_fill16(kv.second.p, kv.second.bytes, word16, (hipStream_t)stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->qkv_dirty = h->qkv_pad_dirty = true;
     return AMX_OK;
 }

@@ -769,5 +769,7 @@ void launch_scale_copy(const float* src, float* dst, int64_t n, float scale, hip
 void launch_zero(void* p, size_t bytes, hipStream_t s);
 void launch_zero_2d(void* base, size_t pitch, size_t width_bytes, size_t rows, hipStream_t s);
 void launch_copy(void* dst, const void* src, size_t bytes, hipStream_t s);
+// the 16-bit word `word16` repeated over `bytes` bytes (amx_debug_scribble; p 4-byte aligned, an odd last byte takes the word's low byte)
+void launch_fill16(void* p, size_t bytes, uint32_t word16, hipStream_t s);
 
 }  // namespace amx

@@ -1804,6 +1804,16 @@ __global__ __launch_bounds__(256) void zero_fill_2d_kernel(unsigned char* __rest
     uint32_t* row = (uint32_t*)(base + (size_t)blockIdx.y * pitch);
     for (size_t w = (size_t)blockIdx.x * 256 + threadIdx.x; w < width_words; w += (size_t)gridDim.x * 256) row[w] = 0;
 }
+// (amx_debug_scribble) `pattern` over `words` 32-bit words, then the `tail` < 4 bytes behind them from its low bytes
+__global__ __launch_bounds__(256) void fill_words_kernel(uint32_t* __restrict__ p, size_t words, uint32_t pattern, int tail) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool aligned = ((uintptr_t)p & 15) == 0;
+    const size_t quads = aligned ? words / 4 : 0;
+    for (size_t q = i; q < quads; q += stride) ((uint4*)p)[q] = make_uint4(pattern, pattern, pattern, pattern);
+    for (size_t w = quads * 4 + i; w < words; w += stride) p[w] = pattern;
+    if (i < (size_t)tail) ((unsigned char*)(p + words))[i] = (unsigned char)(pattern >> (8 * i));
+}
 }  // namespace
 
 void launch_zero(void* p, size_t bytes, hipStream_t s) {
@@ -1829,6 +1839,15 @@ void launch_zero_2d(void* base, size_t pitch, size_t width_bytes, size_t rows, h
     size_t bx = (words + 255) / 256;
     if (bx > 64) bx = 64;
     hipLaunchKernelGGL(zero_fill_2d_kernel, dim3((unsigned)bx, (unsigned)rows), dim3(256), 0, s, (unsigned char*)base, pitch, words);
+}
+
+void launch_fill16(void* p, size_t bytes, uint32_t word16, hipStream_t s) {
+    if (bytes == 0) return;
+    const size_t words = bytes / 4;
+    size_t blocks = (words / 4 + 255) / 256 + 1;
+    if (blocks > 4096) blocks = 4096;
+    const uint32_t pattern = (word16 & 0xffffu) | (word16 << 16);
+    hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (uint32_t*)p, words, pattern, (int)(bytes - words * 4));
 }
 
 void launch_scale_copy(const float* src, float* dst, int64_t n, float scale, hipStream_t s) {

@@ -957,6 +957,15 @@ class Estimator:
             return buf[: n_t[0] * n_t[1] * ld.value].view(n_t[0] * n_t[1], ld.value)
         return buf
 
+    def _debug_scribble(self, word16: int) -> None:
+        """Test hook (``amx_debug_scribble``): fills every data workspace of the handle, over its whole allocation, with the
+        16-bit word ``word16`` repeated, in stream order.  The next ``predict`` must give the bits it gives on a fresh handle."""
+        if not hasattr(self._lib, "amx_debug_scribble"):
+            raise RuntimeError("this build of liballophant_amx has no amx_debug_scribble")
+        stream = torch.cuda.current_stream(self._device).cuda_stream
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib, self._handle, self._lib.amx_debug_scribble(self._handle, int(word16), C.c_void_p(stream)))
+
     def _last_geometry(self) -> Tuple[int, int]:
         if not hasattr(self, "_geom"):
             raise RuntimeError("no forward pass yet")

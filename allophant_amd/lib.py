@@ -36,7 +36,7 @@ EXPORTS = [
     "amx_create", "amx_destroy", "amx_last_error", "amx_set_inventory", "amx_output_layout", "amx_forward",
     "amx_synchronize", "amx_greedy_ctc", "amx_debug_fetch", "amx_device_bytes", "amx_timing_fetch",
     "amx_max_utterances", "amx_greedy_ctc_emissions", "amx_check_finite", "amx_gather_outputs", "amx_dist_last_error",
-    "amx_graph_info", "amx_pass_info",
+    "amx_graph_info", "amx_pass_info", "amx_debug_scribble",
 ]
 # the allophone-layer entry points (include/allophant_amx_allophones.h; added to ABI 6, detected by name)
 ALLOPHONE_EXPORTS = ["amx_set_allophones", "amx_map_allophones"]
@@ -164,6 +164,9 @@ def load() -> C.CDLL:
     if hasattr(lib, "amx_pass_info") or AMX_ABI_VERSION >= 6:  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_pass_info.argtypes = [vp, C.POINTER(C.c_int32), i32]
         lib.amx_pass_info.restype = i32
+    if hasattr(lib, "amx_debug_scribble"):  # (added to ABI 7 by name: absent from older builds)
+        lib.amx_debug_scribble.argtypes = [vp, C.c_uint32, vp]
+        lib.amx_debug_scribble.restype = i32
     if hasattr(lib, "amx_map_allophones"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_set_allophones.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
         lib.amx_set_allophones.restype = i32

@@ -261,6 +261,14 @@ int amx_greedy_ctc_emissions(int device, const float* emissions, int64_t stride_
  *   what = 2: raw logits buffer [N*T, ld] (index ignored); returns ld through *ld_out */
 int amx_debug_fetch(amx_handle h, int what, int index, float* host_out, int64_t capacity, int64_t* ld_out);
 
+/* Test hook (added to ABI 7, detected by name): fills every data workspace of the handle, over its whole allocation, with the 16-bit
+ * word `word16` repeated (kernels on `stream`), so that a test can show that the outputs of a forward pass do not depend on what
+ * the handle's earlier calls left behind.  The small integer workspaces from which kernels form addresses, loop bounds and grids
+ * (lengths, frame counts, row offsets, tile lists: uploaded whole in front of every use) are left alone, as are weights and
+ * inventories.  Pick a word that is finite in every type a workspace holds (fp16, bf16, fp32 and fp64 when repeated: 0x0000,
+ * 0x7BFF, 0x3C66); recordings of earlier passes stay valid. */
+int amx_debug_scribble(amx_handle h, uint32_t word16, void* stream);
+
 /* Measurement hook: sums the HIP-event durations (ms) and launch counts per kernel class (AMX_KC_*) of every
  * amx_forward issued with AMX_FLAG_TIMING since the previous fetch; synchronises the stream. */
 int amx_timing_fetch(amx_handle h, float* ms, int32_t* launches, int n_classes);
