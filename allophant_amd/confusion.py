@@ -261,14 +261,14 @@ class ConfusionCounts:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def add_rows(self, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int, G: int, maps: Tensor,
-                 n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int, max_actual: int,
-                 best: Optional[Tensor] = None, weights=None) -> Tensor:
-        """One ``amx_edit_confusions`` call (with ``weights``: ``amx_edit_weighted_confusions``): ``tokens`` int64
-        [O, N, K, T], ``counts`` int32 [O, N, K], ``best`` int32 [O, N] or None; the other arguments as
-        ``evaluation._run``.  Returns ``row_events`` int32 [O, N].  Stream-ordered: nothing waits for the device."""
+    def add_rows(self, rows, best: Optional[Tensor] = None, weights=None) -> Tensor:
+        """One ``amx_edit_confusions`` call (with ``weights``: ``amx_edit_weighted_confusions``) over ``rows``, the
+        ``evaluation._EditRows`` that the statistics were computed on, for the candidates ``best`` int32 [O, N] (None:
+        candidate 0).  Returns ``row_events`` int32 [O, N].  Stream-ordered: nothing waits for the device."""
         handle = _library()
-        O, N_, K, T = tokens.shape
+        rows = rows.unit_stride()
+        O, N, _, _ = rows.tokens.shape
+        G = rows.G
         if self.names is not None and len(self.names) != O:
             raise ValueError(f"{O} outputs for a table over {len(self.names)}")
         if self.languages is not None and len(self.languages) != G:
@@ -276,20 +276,9 @@ class ConfusionCounts:
         if self._shape not in (None, (G, O)):
             raise ValueError(f"{G} groups x {O} outputs added to a table over {self._shape}")
         self._shape = (G, O)
-        size = C.c_size_t()
-        _lib.check(handle, None, handle.amx_edit_operations_workspace(O * N_, max_expected, max_actual, C.byref(size)))
-        if self._workspace is None or self._workspace.numel() < size.value:
-            self._workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=self.device)
-        row_events = torch.empty(O, N_, dtype=torch.int32, device=self.device)
-        if tokens.stride(3) != 1:
-            tokens = tokens.contiguous()
-
-        def at(t: Tensor, offset: int):
-            return C.c_void_p(t.data_ptr() + offset * t.element_size())
-
-        head = (self.device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), tokens.stride(2), O, N_, K, T, _ptr(counts),
-                _ptr(hyp_counts), at(labels, 0), at(labels, 2 * N + 1), at(labels, N + 1), G, at(maps, 0), at(maps, n_offsets),
-                _ptr(label_maps), _ptr(hyp_maps), H, max_expected, max_actual, _ptr(self._workspace), self._workspace.numel())
+        self._workspace = rows.workspace(True, self._workspace)
+        row_events = torch.empty(O, N, dtype=torch.int32, device=self.device)
+        head = rows.head(self._workspace)
         tail = (_ptr(best), _ptr(self.table), self.capacity, _ptr(row_events), _ptr(self.counters), self._stream())
         with torch.cuda.device(self.device):
             if weights is None:

@@ -2809,38 +2809,77 @@ extern "C" int amx_edit_workspace(int64_t rows, int64_t max_expected, int64_t ma
     return AMX_OK;
 }
 
+// ---- the call frame that the six row entries share ----
+// Their leading arguments after `device`, in the entry points' order; the operations calls have one candidate (stride_k 0, K 1).
+struct EditRows {
+    const int64_t* tokens;
+    int64_t stride_o, stride_n, stride_k;
+    int O, N, K;
+    int64_t T;
+    const int32_t *counts, *hyp_counts, *label_offsets, *label_ids, *groups;
+    int G;
+    const int32_t *map_offsets, *map_values, *label_maps, *hyp_maps;
+    int H;
+    int64_t max_expected, max_actual;
+    void* workspace;
+    size_t workspace_bytes;
+};
+
+// Checks them in one order and fills `a`.  `candidates`: K is an argument of the entry, checked and part of its row count.
+// `codes`: the workspace is amx_edit_operations_workspace's, one row per (output, utterance); otherwise amx_edit_workspace's,
+// one row per candidate.  `outputs`: the entry's own required pointers are all there.  Returns AMX_OK with *pairs == 0 when
+// there is nothing to launch.
+static int edit_frame(const EditRows& r, bool candidates, bool codes, bool outputs, amx::EditArgs& a, int64_t* pairs) {
+    *pairs = 0;
+    if (r.O < 0 || r.N < 0 || r.T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
+    if (r.K < 1 || r.K > AMX_EDIT_MAX_CANDIDATES)
+        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
+    const std::string err = edit_limits(r.max_expected, r.max_actual);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    if (r.G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
+    if (r.H != 1 && r.H != r.G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
+    const int64_t rows = (int64_t)r.O * r.N;
+    if (rows > INT32_MAX / r.K)
+        return fail(nullptr, AMX_EINVAL, candidates ? "O * N * K must stay below 2^31" : "O * N must stay below 2^31");
+    size_t needed = 0;
+    if (!codes) needed = edit_workspace_bytes(rows * r.K, r.max_expected, r.max_actual);
+    else if (!edit_operations_workspace_bytes(rows, r.max_expected, r.max_actual, &needed))
+        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
+    if (rows == 0) return AMX_OK;
+    if (!r.tokens || !r.counts || !r.label_offsets || !r.label_ids || !r.groups || !r.map_offsets || !r.map_values ||
+        !r.label_maps || !r.hyp_maps || !r.workspace || !outputs)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    if (r.workspace_bytes < needed)
+        return fail(nullptr, AMX_EINVAL, codes ? "workspace smaller than amx_edit_operations_workspace"
+                                               : "workspace smaller than amx_edit_workspace");
+    a.tokens = r.tokens, a.stride_o = r.stride_o, a.stride_n = r.stride_n, a.stride_k = r.stride_k, a.T = r.T;
+    a.O = r.O, a.N = r.N, a.K = r.K, a.G = r.G, a.H = r.H;
+    a.counts = r.counts, a.hyp_counts = r.hyp_counts, a.label_offsets = r.label_offsets, a.label_ids = r.label_ids;
+    a.groups = r.groups, a.map_offsets = r.map_offsets, a.map_values = r.map_values, a.label_maps = r.label_maps;
+    a.hyp_maps = r.hyp_maps, a.cap_a = (int)r.max_expected, a.cap_b = (int)r.max_actual, a.workspace = (int32_t*)r.workspace;
+    *pairs = rows;
+    return AMX_OK;
+}
+static int edit_launched(const char* what) {
+    return hipGetLastError() == hipSuccess ? AMX_OK : fail(nullptr, AMX_EHIP, std::string(what) + " launch failed");
+}
+
 extern "C" int amx_edit_statistics(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O,
                                    int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
                                    const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
                                    const int32_t* map_offsets, const int32_t* map_values, const int32_t* label_maps,
                                    const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual, void* workspace,
                                    size_t workspace_bytes, int32_t* statistics, int32_t* best, uint64_t* totals, void* stream) {
-    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
-    if (K < 1 || K > AMX_EDIT_MAX_CANDIDATES)
-        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
-    const std::string err = edit_limits(max_expected, max_actual);
-    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
-    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
-    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
-    const int64_t rows = (int64_t)O * N * K;
-    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N * K must stay below 2^31");
-    if (rows == 0) return AMX_OK;
-    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
-        !workspace || !statistics || !best || !totals)
-        return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (workspace_bytes < edit_workspace_bytes(rows, max_expected, max_actual))
-        return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_workspace");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    const EditRows r{tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids, groups, G,
+                     map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace, workspace_bytes};
     amx::EditArgs a{};
-    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = stride_k, a.T = T;
-    a.O = O, a.N = N, a.K = K, a.G = G, a.H = H;
-    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
-    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
-    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
-    a.workspace = (int32_t*)workspace, a.statistics = statistics, a.best = best, a.totals = totals;
+    int64_t pairs = 0;
+    const int code = edit_frame(r, true, false, statistics && best && totals, a, &pairs);
+    if (code != AMX_OK || pairs == 0) return code;
+    a.statistics = statistics, a.best = best, a.totals = totals;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_statistics(a, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit statistics launch failed");
-    return AMX_OK;
+    return edit_launched("edit statistics");
 }
 
 extern "C" int amx_edit_operations_workspace(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes) {
@@ -2859,36 +2898,19 @@ extern "C" int amx_edit_operations(int device, const int64_t* tokens, int64_t st
                                    const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
                                    int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes,
                                    int64_t max_ops, int32_t* operations, int32_t* operation_counts, void* stream) {
-    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
-    const std::string err = edit_limits(max_expected, max_actual);
-    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
-    if (max_ops < std::max(max_expected, max_actual) || max_ops > INT32_MAX)
+    // (lengths beyond the limits are the frame's to report: they give no bound for max_ops)
+    if (edit_limits(max_expected, max_actual).empty() && (max_ops < std::max(max_expected, max_actual) || max_ops > INT32_MAX))
         return fail(nullptr, AMX_EINVAL, "max_ops must be max(max_expected, max_actual) to 2^31 - 1");
-    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
-    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
-    const int64_t rows = (int64_t)O * N;
-    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N must stay below 2^31");
-    size_t needed = 0;
-    if (!edit_operations_workspace_bytes(rows, max_expected, max_actual, &needed))
-        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
-    if (rows == 0) return AMX_OK;
-    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
-        !workspace || !operations || !operation_counts)
-        return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (workspace_bytes < needed) return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_operations_workspace");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    const EditRows r{tokens, stride_o, stride_n, 0, O, N, 1, T, counts, hyp_counts, label_offsets, label_ids, groups, G,
+                     map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace, workspace_bytes};
     amx::EditOpsArgs x{};
-    amx::EditArgs& a = x.e;
-    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = 0, a.T = T;
-    a.O = O, a.N = N, a.K = 1, a.G = G, a.H = H;
-    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
-    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
-    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
-    a.workspace = (int32_t*)workspace;
+    int64_t pairs = 0;
+    const int code = edit_frame(r, false, true, operations && operation_counts, x.e, &pairs);
+    if (code != AMX_OK || pairs == 0) return code;
     x.max_ops = max_ops, x.operations = operations, x.operation_counts = operation_counts;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_operations(x, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit operations launch failed");
-    return AMX_OK;
+    return edit_launched("edit operations");
 }
 
 // feature-weighted edit distance
@@ -2914,8 +2936,7 @@ extern "C" int amx_edit_cost_table(int device, const uint8_t* codes, int64_t V, 
     if (!table || (F > 0 && !codes)) return fail(nullptr, AMX_EINVAL, "null buffer");
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_cost_table(codes, (int)V, (int)F, table, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "cost table launch failed");
-    return AMX_OK;
+    return edit_launched("cost table");
 }
 
 extern "C" int amx_edit_weighted_statistics(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k,
@@ -2926,36 +2947,21 @@ extern "C" int amx_edit_weighted_statistics(int device, const int64_t* tokens, i
                                             void* workspace, size_t workspace_bytes, float insertion_cost, float deletion_cost,
                                             const int64_t* cost_tables, const uint8_t* cost_table_data, int32_t* statistics,
                                             int32_t* best, uint64_t* totals, float* costs, void* stream) {
-    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
-    if (K < 1 || K > AMX_EDIT_MAX_CANDIDATES)
-        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
-    std::string err = edit_limits(max_expected, max_actual);
-    if (err.empty()) err = edit_cost_limits(insertion_cost, deletion_cost);
+    const std::string err = edit_cost_limits(insertion_cost, deletion_cost);
     if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
-    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
-    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
-    const int64_t rows = (int64_t)O * N * K;
-    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N * K must stay below 2^31");
-    if (rows == 0) return AMX_OK;
-    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
-        !workspace || !statistics || !best || !totals || !cost_tables || !costs)
-        return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (workspace_bytes < edit_workspace_bytes(rows, max_expected, max_actual))
-        return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_workspace");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    const EditRows r{tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids, groups, G,
+                     map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace, workspace_bytes};
     amx::EditWeightedArgs w{};
     amx::EditArgs& a = w.x.e;
-    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = stride_k, a.T = T;
-    a.O = O, a.N = N, a.K = K, a.G = G, a.H = H;
-    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
-    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
-    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
-    a.workspace = (int32_t*)workspace, a.statistics = statistics, a.best = best, a.totals = totals;
+    int64_t pairs = 0;
+    const int code = edit_frame(r, true, false, statistics && best && totals && cost_tables && costs, a, &pairs);
+    if (code != AMX_OK || pairs == 0) return code;
+    a.statistics = statistics, a.best = best, a.totals = totals;
     w.insertion_cost = insertion_cost, w.deletion_cost = deletion_cost;
     w.tables = cost_tables, w.table_data = cost_table_data, w.costs = costs;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_weighted_statistics(w, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "weighted edit statistics launch failed");
-    return AMX_OK;
+    return edit_launched("weighted edit statistics");
 }
 
 extern "C" int amx_edit_weighted_operations(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int O, int N,
@@ -2966,39 +2972,23 @@ extern "C" int amx_edit_weighted_operations(int device, const int64_t* tokens, i
                                             void* workspace, size_t workspace_bytes, float insertion_cost, float deletion_cost,
                                             const int64_t* cost_tables, const uint8_t* cost_table_data, int64_t max_ops,
                                             int32_t* operations, int32_t* operation_counts, float* costs, void* stream) {
-    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
-    std::string err = edit_limits(max_expected, max_actual);
-    if (err.empty()) err = edit_cost_limits(insertion_cost, deletion_cost);
+    const std::string err = edit_cost_limits(insertion_cost, deletion_cost);
     if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
-    if (max_ops < max_expected + max_actual || max_ops > INT32_MAX)
+    // (lengths beyond the limits are the frame's to report: they give no bound for max_ops)
+    if (edit_limits(max_expected, max_actual).empty() && (max_ops < max_expected + max_actual || max_ops > INT32_MAX))
         return fail(nullptr, AMX_EINVAL, "max_ops must be max_expected + max_actual to 2^31 - 1");
-    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
-    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
-    const int64_t rows = (int64_t)O * N;
-    if (rows > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N must stay below 2^31");
-    size_t needed = 0;
-    if (!edit_operations_workspace_bytes(rows, max_expected, max_actual, &needed))
-        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
-    if (rows == 0) return AMX_OK;
-    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
-        !workspace || !operations || !operation_counts || !cost_tables || !costs)
-        return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (workspace_bytes < needed) return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_operations_workspace");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    const EditRows r{tokens, stride_o, stride_n, 0, O, N, 1, T, counts, hyp_counts, label_offsets, label_ids, groups, G,
+                     map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace, workspace_bytes};
     amx::EditWeightedArgs w{};
-    amx::EditArgs& a = w.x.e;
-    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = 0, a.T = T;
-    a.O = O, a.N = N, a.K = 1, a.G = G, a.H = H;
-    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
-    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
-    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
-    a.workspace = (int32_t*)workspace;
+    int64_t pairs = 0;
+    const int code = edit_frame(r, false, true, operations && operation_counts && cost_tables && costs, w.x.e, &pairs);
+    if (code != AMX_OK || pairs == 0) return code;
     w.x.max_ops = max_ops, w.x.operations = operations, w.x.operation_counts = operation_counts;
     w.insertion_cost = insertion_cost, w.deletion_cost = deletion_cost;
     w.tables = cost_tables, w.table_data = cost_table_data, w.costs = costs;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_weighted_operations(w, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "weighted edit operations launch failed");
-    return AMX_OK;
+    return edit_launched("weighted edit operations");
 }
 
 extern "C" int amx_edit_matrix(int device, const int32_t* expected_offsets, const int32_t* expected_ids,
@@ -3025,8 +3015,7 @@ extern "C" int amx_edit_matrix(int device, const int32_t* expected_offsets, cons
     a.insertion_cost = insertion_cost, a.deletion_cost = deletion_cost;
     a.workspace = (int2*)workspace, a.matrix = matrix, a.status = status;
     launch_edit_matrix(a, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit matrix launch failed");
-    return AMX_OK;
+    return edit_launched("edit matrix");
 }
 
 // confusion tables
@@ -3045,46 +3034,6 @@ extern "C" int amx_edit_confusion_table_bytes(int64_t capacity, size_t* bytes) {
     return AMX_OK;
 }
 
-// The checks and the row arguments that the two confusion entries share.  Returns AMX_OK with *rows == 0 when there is
-// nothing to launch.
-static int confusion_frame(const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O, int N, int K,
-                           int64_t T, const int32_t* counts, const int32_t* hyp_counts, const int32_t* label_offsets,
-                           const int32_t* label_ids, const int32_t* groups, int G, const int32_t* map_offsets,
-                           const int32_t* map_values, const int32_t* label_maps, const int32_t* hyp_maps, int H,
-                           int64_t max_expected, int64_t max_actual, void* workspace, size_t workspace_bytes, const int32_t* best,
-                           void* table, int64_t capacity, int32_t* row_events, uint64_t* counters, amx::EditOpsArgs& x,
-                           amx::EditConfusionOut& c, int64_t* rows) {
-    *rows = 0;
-    if (O < 0 || N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative edit geometry");
-    if (K < 1 || K > AMX_EDIT_MAX_CANDIDATES)
-        return fail(nullptr, AMX_EINVAL, "K must be 1 to " + std::to_string(AMX_EDIT_MAX_CANDIDATES) + " candidates");
-    std::string err = edit_limits(max_expected, max_actual);
-    if (err.empty()) err = confusion_capacity_limits(capacity);
-    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
-    if (G < 1) return fail(nullptr, AMX_EINVAL, "at least one group");
-    if (H != 1 && H != G) return fail(nullptr, AMX_EINVAL, "H must be 1 or G hypothesis-map sets");
-    if ((int64_t)O * N * K > INT32_MAX) return fail(nullptr, AMX_EINVAL, "O * N * K must stay below 2^31");
-    size_t needed = 0;
-    if (!edit_operations_workspace_bytes((int64_t)O * N, max_expected, max_actual, &needed))
-        return fail(nullptr, AMX_EINVAL, "workspace size not representable");
-    if ((int64_t)O * N == 0) return AMX_OK;
-    if (!tokens || !counts || !label_offsets || !label_ids || !groups || !map_offsets || !map_values || !label_maps || !hyp_maps ||
-        !workspace || !table || !row_events || !counters)
-        return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (workspace_bytes < needed) return fail(nullptr, AMX_EINVAL, "workspace smaller than amx_edit_operations_workspace");
-    amx::EditArgs& a = x.e;
-    a.tokens = tokens, a.stride_o = stride_o, a.stride_n = stride_n, a.stride_k = stride_k, a.T = T;
-    a.O = O, a.N = N, a.K = K, a.G = G, a.H = H;
-    a.counts = counts, a.hyp_counts = hyp_counts, a.label_offsets = label_offsets, a.label_ids = label_ids, a.groups = groups;
-    a.map_offsets = map_offsets, a.map_values = map_values, a.label_maps = label_maps, a.hyp_maps = hyp_maps;
-    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
-    a.workspace = (int32_t*)workspace;
-    c.best = best, c.table = (unsigned long long*)table, c.capacity = capacity, c.row_events = row_events;
-    c.counters = (unsigned long long*)counters;
-    *rows = (int64_t)O * N;
-    return AMX_OK;
-}
-
 extern "C" int amx_edit_confusions(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k, int O,
                                    int N, int K, int64_t T, const int32_t* counts, const int32_t* hyp_counts,
                                    const int32_t* label_offsets, const int32_t* label_ids, const int32_t* groups, int G,
@@ -3092,16 +3041,18 @@ extern "C" int amx_edit_confusions(int device, const int64_t* tokens, int64_t st
                                    const int32_t* hyp_maps, int H, int64_t max_expected, int64_t max_actual, void* workspace,
                                    size_t workspace_bytes, const int32_t* best, void* table, int64_t capacity, int32_t* row_events,
                                    uint64_t* counters, void* stream) {
+    const std::string err = confusion_capacity_limits(capacity);
+    if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    const EditRows r{tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids, groups, G,
+                     map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace, workspace_bytes};
     amx::EditConfusionArgs p{};
-    int64_t rows = 0;
-    const int code = confusion_frame(tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids,
-                                     groups, G, map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace,
-                                     workspace_bytes, best, table, capacity, row_events, counters, p.x, p.c, &rows);
-    if (code != AMX_OK || rows == 0) return code;
+    int64_t pairs = 0;
+    const int code = edit_frame(r, true, true, table && row_events && counters, p.x.e, &pairs);
+    if (code != AMX_OK || pairs == 0) return code;
+    p.c = {best, (unsigned long long*)table, capacity, row_events, (unsigned long long*)counters};
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_confusions(p, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "edit confusions launch failed");
-    return AMX_OK;
+    return edit_launched("edit confusions");
 }
 
 extern "C" int amx_edit_weighted_confusions(int device, const int64_t* tokens, int64_t stride_o, int64_t stride_n, int64_t stride_k,
@@ -3112,21 +3063,21 @@ extern "C" int amx_edit_weighted_confusions(int device, const int64_t* tokens, i
                                             void* workspace, size_t workspace_bytes, float insertion_cost, float deletion_cost,
                                             const int64_t* cost_tables, const uint8_t* cost_table_data, const int32_t* best,
                                             void* table, int64_t capacity, int32_t* row_events, uint64_t* counters, void* stream) {
-    const std::string err = edit_cost_limits(insertion_cost, deletion_cost);
+    std::string err = edit_cost_limits(insertion_cost, deletion_cost);
+    if (err.empty()) err = confusion_capacity_limits(capacity);
     if (!err.empty()) return fail(nullptr, AMX_EINVAL, err);
+    const EditRows r{tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids, groups, G,
+                     map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace, workspace_bytes};
     amx::EditWeightedConfusionArgs p{};
-    int64_t rows = 0;
-    const int code = confusion_frame(tokens, stride_o, stride_n, stride_k, O, N, K, T, counts, hyp_counts, label_offsets, label_ids,
-                                     groups, G, map_offsets, map_values, label_maps, hyp_maps, H, max_expected, max_actual, workspace,
-                                     workspace_bytes, best, table, capacity, row_events, counters, p.w.x, p.c, &rows);
-    if (code != AMX_OK || rows == 0) return code;
-    if (!cost_tables) return fail(nullptr, AMX_EINVAL, "null buffer");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    int64_t pairs = 0;
+    const int code = edit_frame(r, true, true, table && row_events && counters && cost_tables, p.w.x.e, &pairs);
+    if (code != AMX_OK || pairs == 0) return code;
+    p.c = {best, (unsigned long long*)table, capacity, row_events, (unsigned long long*)counters};
     p.w.insertion_cost = insertion_cost, p.w.deletion_cost = deletion_cost;
     p.w.tables = cost_tables, p.w.table_data = cost_table_data, p.w.costs = nullptr;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_weighted_confusions(p, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "weighted edit confusions launch failed");
-    return AMX_OK;
+    return edit_launched("weighted edit confusions");
 }
 
 extern "C" int amx_edit_confusion_merge(int device, const void* src, int64_t src_capacity, void* dst, int64_t dst_capacity,
@@ -3140,8 +3091,7 @@ extern "C" int amx_edit_confusion_merge(int device, const void* src, int64_t src
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
     launch_edit_confusion_merge((const unsigned long long*)src, src_capacity, (unsigned long long*)dst, dst_capacity,
                                 (unsigned long long*)counters, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, AMX_EHIP, "confusion merge launch failed");
-    return AMX_OK;
+    return edit_launched("confusion merge");
 }
 
 // =================================================================================================================

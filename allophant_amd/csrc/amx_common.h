@@ -670,8 +670,9 @@ void launch_resample(const float* x, int64_t stride, int64_t L_in, const int64_t
                      const float* bank, const int32_t* phases, int window, int N, int64_t L_out, float* y, hipStream_t s);
 
 // edit statistics (amx_edit.hip): contract in include/allophant_amx_edit.h.  One wave per scored (output, utterance,
-// candidate) row, then one thread per (output, utterance) for the candidate choice and the totals.  The launcher fills the
-// workspace layout (per row, in int32: expected, actual, two boundary rows of int2 cells, each padded to 16).
+// candidate) row, then one thread per (output, utterance) for the candidate choice and the totals.  edit_layout fills the
+// workspace layout (per row, in int32: expected, actual, two boundary rows of int2 cells, each padded to 16), for the
+// launchers and for the sizes that the callers are told.
 struct EditArgs {
     const int64_t* tokens;
     int64_t stride_o, stride_n, stride_k, T;
@@ -687,6 +688,7 @@ struct EditArgs {
 size_t edit_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual);
 void launch_edit_statistics(EditArgs a, hipStream_t s);
 int64_t edit_pad(int64_t v);  // rounded up to a multiple of 16
+void edit_layout(EditArgs& a);  // fills cap_a_pad, cap_b_pad, bnd_pad and span from cap_a and cap_b
 
 // edit operations (amx_edit_ops.hip): one wave per (output, utterance) row, candidate 0 (e.K == 1; the statistics outputs
 // unused).  A row's workspace is the statistics row's, then the path codes: per strip of 64 expected symbols, code_stride
@@ -698,6 +700,7 @@ struct EditOpsArgs {
 };
 // false when the size is not representable in size_t
 bool edit_operations_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes);
+void edit_layout(EditOpsArgs& x);  // the statistics row's layout, then codes_at, code_stride and the longer span
 void launch_edit_operations(EditOpsArgs x, hipStream_t s);
 
 // feature-weighted edit distance (amx_edit_weighted.hip): upstream's PropertyWeighting, contract in

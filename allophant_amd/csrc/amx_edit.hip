@@ -65,16 +65,34 @@ __global__ __launch_bounds__(SELECT_THREADS) void edit_select_kernel(EditArgs a)
 
 int64_t edit_pad(int64_t v) { return (v + 15) / 16 * 16; }
 
-size_t edit_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual) {
-    const int64_t span = edit_pad(max_expected) + edit_pad(max_actual) + 4 * edit_pad(max_actual + 1);
-    return (size_t)rows * (size_t)span * sizeof(int32_t);
-}
-
-void launch_edit_statistics(EditArgs a, hipStream_t s) {
+// The layout of a row's workspace, in int32: expected, actual, two boundary rows of int2 cells, each padded to 16.  Every
+// size that a caller is told and every offset that a kernel indexes with comes from here.
+void edit_layout(EditArgs& a) {
     a.cap_a_pad = edit_pad(a.cap_a);
     a.cap_b_pad = edit_pad(a.cap_b);
     a.bnd_pad = edit_pad(a.cap_b + 1);  // int2 cells per boundary row
-    a.span = a.cap_a_pad + a.cap_b_pad + 4 * edit_pad(a.cap_b + 1);
+    a.span = a.cap_a_pad + a.cap_b_pad + 4 * a.bnd_pad;
+}
+
+// The operations' and confusions' row: the same, then the path codes, per strip of 64 expected symbols code_stride words of
+// 16 bytes.
+void edit_layout(EditOpsArgs& x) {
+    EditArgs& a = x.e;
+    edit_layout(a);
+    x.codes_at = a.span;
+    x.code_stride = edit_pad(a.cap_b + WAVE);  // steps t <= n + 63 of a strip
+    a.span = x.codes_at + (a.cap_a + WAVE - 1) / WAVE * x.code_stride * 4;
+}
+
+size_t edit_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual) {
+    EditArgs a{};
+    a.cap_a = (int)max_expected, a.cap_b = (int)max_actual;
+    edit_layout(a);
+    return (size_t)rows * (size_t)a.span * sizeof(int32_t);
+}
+
+void launch_edit_statistics(EditArgs a, hipStream_t s) {
+    edit_layout(a);
     const int64_t rows = (int64_t)a.O * a.N * a.K;
     hipLaunchKernelGGL(edit_rows_kernel, dim3((unsigned)rows), dim3(WAVE), 0, s, a);
     const int64_t pairs = (int64_t)a.O * a.N;

@@ -91,15 +91,8 @@ __global__ __launch_bounds__(MERGE_THREADS) void edit_confusion_merge_kernel(con
 }  // namespace
 
 void launch_edit_confusions(EditConfusionArgs p, hipStream_t s) {
-    EditOpsArgs& x = p.x;
-    EditArgs& a = x.e;
-    a.cap_a_pad = edit_pad(a.cap_a);
-    a.cap_b_pad = edit_pad(a.cap_b);
-    a.bnd_pad = edit_pad(a.cap_b + 1);  // int2 cells per boundary row
-    x.codes_at = a.cap_a_pad + a.cap_b_pad + 4 * a.bnd_pad;
-    x.code_stride = edit_pad(a.cap_b + WAVE);  // steps t <= n + 63 of a strip
-    a.span = x.codes_at + (a.cap_a + WAVE - 1) / WAVE * x.code_stride * 4;
-    const int64_t rows = (int64_t)a.O * a.N;
+    edit_layout(p.x);
+    const int64_t rows = (int64_t)p.x.e.O * p.x.e.N;
     hipLaunchKernelGGL(edit_confusion_kernel, dim3((unsigned)rows), dim3(WAVE), 0, s, p);
 }
 

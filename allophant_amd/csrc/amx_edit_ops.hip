@@ -61,23 +61,19 @@ __global__ __launch_bounds__(WAVE) void edit_ops_kernel(EditOpsArgs x) {
 
 // Per row: the statistics row's layout for one candidate, then ceil(max_expected / 64) strips of code words.
 bool edit_operations_workspace_bytes(int64_t rows, int64_t max_expected, int64_t max_actual, size_t* bytes) {
-    const int64_t codes = (max_expected + WAVE - 1) / WAVE * edit_pad(max_actual + WAVE) * 4;  // int32 per row
-    const int64_t span = edit_pad(max_expected) + edit_pad(max_actual) + 4 * edit_pad(max_actual + 1) + codes;
+    EditOpsArgs x{};
+    x.e.cap_a = (int)max_expected, x.e.cap_b = (int)max_actual;
+    edit_layout(x);
     size_t total = 0;
-    if (__builtin_mul_overflow((size_t)rows, (size_t)span, &total) || __builtin_mul_overflow(total, sizeof(int32_t), &total))
+    if (__builtin_mul_overflow((size_t)rows, (size_t)x.e.span, &total) || __builtin_mul_overflow(total, sizeof(int32_t), &total))
         return false;
     *bytes = total;
     return true;
 }
 
 void launch_edit_operations(EditOpsArgs x, hipStream_t s) {
-    EditArgs& a = x.e;
-    a.cap_a_pad = edit_pad(a.cap_a);
-    a.cap_b_pad = edit_pad(a.cap_b);
-    a.bnd_pad = edit_pad(a.cap_b + 1);  // int2 cells per boundary row
-    x.codes_at = a.cap_a_pad + a.cap_b_pad + 4 * a.bnd_pad;
-    x.code_stride = edit_pad(a.cap_b + WAVE);  // steps t <= n + 63 of a strip
-    a.span = x.codes_at + (a.cap_a + WAVE - 1) / WAVE * x.code_stride * 4;
+    edit_layout(x);
+    const EditArgs& a = x.e;
     const int64_t rows = (int64_t)a.O * a.N;
     hipLaunchKernelGGL(edit_ops_kernel, dim3((unsigned)rows), dim3(WAVE), 0, s, x);
 }

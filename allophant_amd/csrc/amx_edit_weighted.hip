@@ -181,10 +181,7 @@ void launch_edit_cost_table(const uint8_t* codes, int V, int F, uint8_t* table, 
 
 void launch_edit_weighted_statistics(EditWeightedArgs w, hipStream_t s) {
     EditArgs& a = w.x.e;
-    a.cap_a_pad = edit_pad(a.cap_a);
-    a.cap_b_pad = edit_pad(a.cap_b);
-    a.bnd_pad = edit_pad(a.cap_b + 1);  // int2 cells per boundary row
-    a.span = a.cap_a_pad + a.cap_b_pad + 4 * a.bnd_pad;
+    edit_layout(a);
     const int64_t rows = (int64_t)a.O * a.N * a.K;
     hipLaunchKernelGGL(edit_weighted_rows_kernel, dim3((unsigned)rows), dim3(WAVE), 0, s, w);
     const int64_t pairs = (int64_t)a.O * a.N;
@@ -193,14 +190,8 @@ void launch_edit_weighted_statistics(EditWeightedArgs w, hipStream_t s) {
 }
 
 void launch_edit_weighted_operations(EditWeightedArgs w, hipStream_t s) {
-    EditOpsArgs& x = w.x;
-    EditArgs& a = x.e;
-    a.cap_a_pad = edit_pad(a.cap_a);
-    a.cap_b_pad = edit_pad(a.cap_b);
-    a.bnd_pad = edit_pad(a.cap_b + 1);
-    x.codes_at = a.cap_a_pad + a.cap_b_pad + 4 * a.bnd_pad;
-    x.code_stride = edit_pad(a.cap_b + WAVE);  // steps t <= n + 63 of a strip
-    a.span = x.codes_at + (a.cap_a + WAVE - 1) / WAVE * x.code_stride * 4;
+    edit_layout(w.x);
+    const EditArgs& a = w.x.e;
     hipLaunchKernelGGL(edit_weighted_ops_kernel, dim3((unsigned)((int64_t)a.O * a.N)), dim3(WAVE), 0, s, w);
 }
 

@@ -72,14 +72,8 @@ __global__ __launch_bounds__(WAVE) void edit_weighted_confusion_kernel(EditWeigh
 }  // namespace
 
 void launch_edit_weighted_confusions(EditWeightedConfusionArgs p, hipStream_t s) {
-    EditOpsArgs& x = p.w.x;
-    EditArgs& a = x.e;
-    a.cap_a_pad = edit_pad(a.cap_a);
-    a.cap_b_pad = edit_pad(a.cap_b);
-    a.bnd_pad = edit_pad(a.cap_b + 1);
-    x.codes_at = a.cap_a_pad + a.cap_b_pad + 4 * a.bnd_pad;
-    x.code_stride = edit_pad(a.cap_b + WAVE);  // steps t <= n + 63 of a strip
-    a.span = x.codes_at + (a.cap_a + WAVE - 1) / WAVE * x.code_stride * 4;
+    edit_layout(p.w.x);
+    const EditArgs& a = p.w.x.e;
     hipLaunchKernelGGL(edit_weighted_confusion_kernel, dim3((unsigned)((int64_t)a.O * a.N)), dim3(WAVE), 0, s, p);
 }
 

@@ -332,34 +332,82 @@ def _ptr(t: Optional[Tensor], offset: int = 0):
     return C.c_void_p(t.data_ptr() + offset * t.element_size()) if t is not None else None
 
 
-def _run(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int, G: int,
-         maps: Tensor, n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int, max_actual: int,
-         workspace: Optional[Tensor], totals: Tensor, weights: Optional["_Weights"] = None
+class _EditRows(NamedTuple):
+    """What every row call of the edit family scores: the candidates, the labels and the maps between them."""
+    tokens: Tensor  # int64 [O, N, K, T]
+    counts: Tensor  # int32 [O, N, K], contiguous
+    hyp_counts: Optional[Tensor]  # int32 [O, N], or None: all K candidates
+    labels: Tensor  # the uploaded int32 block [offsets N + 1 | groups N | label ids]
+    N: int
+    G: int
+    maps: Tensor  # the uploaded int32 block [map offsets | map values]
+    n_offsets: int
+    label_maps: Tensor  # int32 [O, 2]
+    hyp_maps: Tensor  # int32 [H, O, 2]
+    H: int
+    max_expected: int
+    max_actual: int
+
+    def head(self, workspace: Tensor, candidates: bool = True) -> tuple:
+        """The leading ctypes arguments of a row call on ``workspace``, the same for the six entries but for
+        ``candidates=False``: an operations call has neither ``stride_k`` nor ``K``.  ``tokens`` have stride 1 along T
+        (``unit_stride``)."""
+        t, N = self.tokens, self.N
+        O, N_, K, T = t.shape
+        shape = (t.stride(0), t.stride(1), t.stride(2), O, N_, K, T) if candidates else (t.stride(0), t.stride(1), O, N_, T)
+        return (t.device.index, _ptr(t), *shape, _ptr(self.counts), _ptr(self.hyp_counts), _ptr(self.labels),
+                _ptr(self.labels, 2 * N + 1), _ptr(self.labels, N + 1), self.G, _ptr(self.maps), _ptr(self.maps, self.n_offsets),
+                _ptr(self.label_maps), _ptr(self.hyp_maps), self.H, self.max_expected, self.max_actual, _ptr(workspace),
+                workspace.numel())
+
+    def unit_stride(self) -> "_EditRows":
+        return self if self.tokens.stride(3) == 1 else self._replace(tokens=self.tokens.contiguous())
+
+    def select(self, index: Tensor, label_maps: Tensor, hyp_maps: Tensor) -> "_EditRows":
+        """The rows of the outputs ``index``, under those outputs' map descriptors."""
+        return self._replace(tokens=self.tokens.index_select(0, index), counts=self.counts.index_select(0, index),
+                             hyp_counts=None if self.hyp_counts is None else self.hyp_counts.index_select(0, index),
+                             label_maps=label_maps, hyp_maps=hyp_maps)
+
+    def first(self) -> "_EditRows":
+        """Candidate 0 of every row: what the operations calls take."""
+        return self._replace(tokens=self.tokens[:, :, :1], counts=self.counts[:, :, :1].contiguous())
+
+    def workspace(self, codes: bool, workspace: Optional[Tensor] = None) -> Tensor:
+        """``workspace`` if it holds what ``amx_edit_operations_workspace`` (``codes``) or ``amx_edit_workspace`` asks for
+        these rows, a new one otherwise."""
+        handle = _library()
+        O, N_, K, _ = self.tokens.shape
+        size = C.c_size_t()
+        if codes:
+            code = handle.amx_edit_operations_workspace(O * N_, self.max_expected, self.max_actual, C.byref(size))
+        else:
+            code = handle.amx_edit_workspace(O * N_ * K, self.max_expected, self.max_actual, C.byref(size))
+        _lib.check(handle, None, code)
+        if workspace is None or workspace.numel() < size.value:
+            workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=self.tokens.device)
+        return workspace
+
+
+def _run(rows: _EditRows, workspace: Optional[Tensor], totals: Tensor, weights: Optional["_Weights"] = None
          ) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
-    """One ``amx_edit_statistics`` call, or with ``weights`` one ``amx_edit_weighted_statistics`` call.  ``labels`` is the
-    uploaded int32 block [offsets N + 1 | groups N | label ids], ``maps`` the uploaded int32 block [map offsets | map values];
-    returns (statistics, best, workspace, costs float32 [O, N, K] or None; NaN where nothing was scored)."""
+    """One ``amx_edit_statistics`` call, or with ``weights`` one ``amx_edit_weighted_statistics`` call.  Returns (statistics,
+    best, workspace, costs float32 [O, N, K] or None; NaN where nothing was scored)."""
     handle = _library() if weights is None else _weighted_library()
-    O, N_, K, T = tokens.shape
-    rows = O * N_ * K
-    size = C.c_size_t()
-    _lib.check(handle, None, handle.amx_edit_workspace(rows, max_expected, max_actual, C.byref(size)))
-    if workspace is None or workspace.numel() < size.value:
-        workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=device)
-    statistics = torch.empty(O, N_, K, 4, dtype=torch.int32, device=device)
-    best = torch.empty(O, N_, dtype=torch.int32, device=device)
-    if tokens.stride(3) != 1:
-        tokens = tokens.contiguous()
+    rows = rows.unit_stride()
+    device = rows.tokens.device
+    O, N, K, _ = rows.tokens.shape
+    workspace = rows.workspace(False, workspace)
+    statistics = torch.empty(O, N, K, 4, dtype=torch.int32, device=device)
+    best = torch.empty(O, N, dtype=torch.int32, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
-    head = (device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), tokens.stride(2), O, N_, K, T, _ptr(counts),
-            _ptr(hyp_counts), _ptr(labels), _ptr(labels, 2 * N + 1), _ptr(labels, N + 1), G, _ptr(maps), _ptr(maps, n_offsets),
-            _ptr(label_maps), _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel())
+    head = rows.head(workspace)
     costs = None
     with torch.cuda.device(device):
         if weights is None:
             code = handle.amx_edit_statistics(*head, _ptr(statistics), _ptr(best), _ptr(totals), C.c_void_p(stream))
         else:
-            costs = torch.full((O, N_, K), float("nan"), dtype=torch.float32, device=device)
+            costs = torch.full((O, N, K), float("nan"), dtype=torch.float32, device=device)
             code = handle.amx_edit_weighted_statistics(
                 *head, weights.insertion_cost, weights.deletion_cost, _ptr(weights.descriptors), _ptr(weights.data),
                 _ptr(statistics), _ptr(best), _ptr(totals), _ptr(costs), C.c_void_p(stream))
@@ -367,34 +415,30 @@ def _run(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optio
     return statistics, best, workspace, costs
 
 
-def _run_operations(device: torch.device, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: Tensor, N: int,
-                    G: int, maps: Tensor, n_offsets: int, label_maps: Tensor, hyp_maps: Tensor, H: int, max_expected: int,
-                    max_actual: int, workspace: Optional[Tensor], weights: Optional["_Weights"] = None
+def _run_operations(rows: _EditRows, workspace: Optional[Tensor], weights: Optional["_Weights"] = None
                     ) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
-    """One ``amx_edit_operations`` (with ``weights``: ``amx_edit_weighted_operations``) call on candidate 0: ``tokens``
-    [O, N, T], ``counts`` int32 [O, N]; arguments otherwise as ``_run``.  Returns (operations int32 [O, N, max_ops, 5],
-    operation counts int32 [O, N], workspace, costs float32 [O, N] or None; NaN where there is no path)."""
+    """One ``amx_edit_operations`` (with ``weights``: ``amx_edit_weighted_operations``) call on ``rows`` of one candidate
+    (``first()``).  Returns (operations int32 [O, N, max_ops, 5], operation counts int32 [O, N], workspace, costs float32
+    [O, N] or None; NaN where there is no path)."""
     handle = _library() if weights is None else _weighted_library()
-    O, N_, T = tokens.shape
-    size = C.c_size_t()
-    _lib.check(handle, None, handle.amx_edit_operations_workspace(O * N_, max_expected, max_actual, C.byref(size)))
-    if workspace is None or workspace.numel() < size.value:
-        workspace = torch.empty(max(16, size.value), dtype=torch.uint8, device=device)
+    rows = rows.unit_stride()
+    device = rows.tokens.device
+    O, N, K, _ = rows.tokens.shape
+    if K != 1:
+        raise ValueError(f"the operations calls take one candidate per row, not {K}")
+    workspace = rows.workspace(True, workspace)
+    max_expected, max_actual = rows.max_expected, rows.max_actual
     max_ops = max(1, max_expected, max_actual) if weights is None else max(1, max_expected + max_actual)
-    operations = torch.empty(O, N_, max_ops, 5, dtype=torch.int32, device=device)
-    operation_counts = torch.empty(O, N_, dtype=torch.int32, device=device)
-    if tokens.stride(2) != 1:
-        tokens = tokens.contiguous()
+    operations = torch.empty(O, N, max_ops, 5, dtype=torch.int32, device=device)
+    operation_counts = torch.empty(O, N, dtype=torch.int32, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
-    head = (device.index, _ptr(tokens), tokens.stride(0), tokens.stride(1), O, N_, T, _ptr(counts), _ptr(hyp_counts),
-            _ptr(labels), _ptr(labels, 2 * N + 1), _ptr(labels, N + 1), G, _ptr(maps), _ptr(maps, n_offsets), _ptr(label_maps),
-            _ptr(hyp_maps), H, max_expected, max_actual, _ptr(workspace), workspace.numel())
+    head = rows.head(workspace, candidates=False)
     costs = None
     with torch.cuda.device(device):
         if weights is None:
             code = handle.amx_edit_operations(*head, max_ops, _ptr(operations), _ptr(operation_counts), C.c_void_p(stream))
         else:
-            costs = torch.full((O, N_), float("nan"), dtype=torch.float32, device=device)
+            costs = torch.full((O, N), float("nan"), dtype=torch.float32, device=device)
             code = handle.amx_edit_weighted_operations(
                 *head, weights.insertion_cost, weights.deletion_cost, _ptr(weights.descriptors), _ptr(weights.data), max_ops,
                 _ptr(operations), _ptr(operation_counts), _ptr(costs), C.c_void_p(stream))
@@ -586,47 +630,35 @@ class Evaluator:
                 self._parts.append((index, label_maps, hyp_maps, weights))
         self._part_workspaces: Dict[Tuple[int, bool], Optional[Tensor]] = {}
 
-    def _add_weighted(self, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: "LabelBatch",
-                      max_actual: int) -> Tuple[Tuple[Tensor, Tensor], Tensor]:
-        O, N, K, _ = tokens.shape
-        G = len(self.languages)
+    def _add_weighted(self, rows: _EditRows) -> Tuple[Tuple[Tensor, Tensor], Tensor]:
+        O, N, K, _ = rows.tokens.shape
         statistics = torch.empty(O, N, K, 4, dtype=torch.int32, device=self.device)
         best = torch.empty(O, N, dtype=torch.int32, device=self.device)
         costs = torch.empty(O, N, K, dtype=torch.float32, device=self.device)
         for p, (index, label_maps, hyp_maps, weights) in enumerate(self._parts):
-            totals = torch.zeros(G, len(index), 4, dtype=torch.int64, device=self.device)
+            totals = torch.zeros(rows.G, len(index), 4, dtype=torch.int64, device=self.device)
+            part = rows.select(index, label_maps, hyp_maps)
             part_statistics, part_best, self._part_workspaces[p, False], part_costs = _run(
-                self.device, tokens.index_select(0, index), counts.index_select(0, index),
-                None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
-                self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual,
-                self._part_workspaces.get((p, False)), totals, weights)
+                part, self._part_workspaces.get((p, False)), totals, weights)
             if self._confusions is not None:
                 if p == 0:
                     self._confusion_events = torch.empty(O, N, dtype=torch.int32, device=self.device)
-                self._confusion_events[index] = self._confusions[p][1].add_rows(
-                    tokens.index_select(0, index), counts.index_select(0, index),
-                    None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
-                    self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual, part_best, weights)
+                self._confusion_events[index] = self._confusions[p][1].add_rows(part, part_best, weights)
             statistics.index_copy_(0, index, part_statistics)
             best.index_copy_(0, index, part_best)
             costs.index_copy_(0, index, _unit_costs(part_statistics) if part_costs is None else part_costs)
             self.totals.index_add_(1, index, totals)
         return (statistics, best), costs
 
-    def _operations_weighted(self, tokens: Tensor, counts: Tensor, hyp_counts: Optional[Tensor], labels: "LabelBatch",
-                             max_actual: int) -> Tuple[Tensor, Tensor]:
-        O, N, _ = tokens.shape
-        G = len(self.languages)
-        max_ops = max(1, labels.max_expected + max_actual)
+    def _operations_weighted(self, rows: _EditRows) -> Tuple[Tensor, Tensor]:
+        O, N, _, _ = rows.tokens.shape
+        max_ops = max(1, rows.max_expected + rows.max_actual)
         operations = torch.empty(O, N, max_ops, 5, dtype=torch.int32, device=self.device)
         operation_counts = torch.empty(O, N, dtype=torch.int32, device=self.device)
         costs = torch.empty(O, N, dtype=torch.float32, device=self.device)
         for p, (index, label_maps, hyp_maps, weights) in enumerate(self._parts):
             part_operations, part_counts, self._part_workspaces[p, True], part_costs = _run_operations(
-                self.device, tokens.index_select(0, index), counts.index_select(0, index),
-                None if hyp_counts is None else hyp_counts.index_select(0, index), labels.data, N, G, self._maps,
-                self._n_offsets, label_maps, hyp_maps, self.maps.H, labels.max_expected, max_actual,
-                self._part_workspaces.get((p, True)), weights)
+                rows.select(index, label_maps, hyp_maps), self._part_workspaces.get((p, True)), weights)
             operations[:, :, :part_operations.shape[2]].index_copy_(0, index, part_operations)
             operation_counts.index_copy_(0, index, part_counts)
             if part_costs is None:  # unit costs: one per record
@@ -690,20 +722,16 @@ class Evaluator:
         data, _ = _upload([offsets, groups, ids_np], self.device)
         return LabelBatch(data, N, max_expected)
 
-    def add(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
-            languages: Optional[Sequence[Union[str, int]]] = None) -> None:
-        """Scores ``decoded`` (``Decoded`` or ``BeamDecoded``, device-resident) against ``labels`` (per utterance its phoneme
-        strings, with ``languages``; or a ``LabelBatch`` from ``encode_labels``) and adds each (output, utterance)'s best
-        candidate to the totals of its language.  Stream-ordered: nothing waits for the device."""
-        rows = [decoded.names.index(name) for name in self.names]
-        tokens, counts = decoded.tokens, decoded.counts
+    def _edit_rows(self, decoded, tokens: Tensor, counts: Tensor, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
+                   languages: Optional[Sequence[Union[str, int]]]) -> _EditRows:
+        """The rows of ``add`` and ``operations``: ``tokens`` [outputs of ``decoded``, N, K, T] and ``counts`` narrowed to
+        the outputs of ``names``, with the encoded labels and this evaluator's maps."""
+        outputs = [decoded.names.index(name) for name in self.names]
         hyp_counts = getattr(decoded, "hyp_counts", None)
         if tokens.device != self.device:
             raise ValueError(f"decoded results live on {tokens.device}, the evaluator on {self.device}")
-        if tokens.dim() == 3:  # greedy: one candidate
-            tokens, counts = tokens.unsqueeze(2), counts.unsqueeze(2)
-        if rows != list(range(len(decoded.names))):
-            index = torch.tensor(rows, dtype=torch.long, device=self.device)
+        if outputs != list(range(len(decoded.names))):
+            index = torch.tensor(outputs, dtype=torch.long, device=self.device)
             tokens, counts = tokens.index_select(0, index), counts.index_select(0, index)
             hyp_counts = None if hyp_counts is None else hyp_counts.index_select(0, index)
         counts = counts.to(torch.int32).contiguous()
@@ -716,17 +744,25 @@ class Evaluator:
         if N != labels.N:
             raise ValueError(f"{N} decoded utterances for {labels.N} labels")
         max_actual = min(T * self.maps.hyp_fanout, _lib.EDIT_MAX_LENGTH)
+        return _EditRows(tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
+                         self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual)
+
+    def add(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
+            languages: Optional[Sequence[Union[str, int]]] = None) -> None:
+        """Scores ``decoded`` (``Decoded`` or ``BeamDecoded``, device-resident) against ``labels`` (per utterance its phoneme
+        strings, with ``languages``; or a ``LabelBatch`` from ``encode_labels``) and adds each (output, utterance)'s best
+        candidate to the totals of its language.  Stream-ordered: nothing waits for the device."""
+        tokens, counts = decoded.tokens, decoded.counts
+        if tokens.dim() == 3:  # greedy: one candidate
+            tokens, counts = tokens.unsqueeze(2), counts.unsqueeze(2)
+        rows = self._edit_rows(decoded, tokens, counts, labels, languages)
         if self.weighting is not None:
-            self._rows, self._costs = self._add_weighted(tokens, counts, hyp_counts, labels, max_actual)
+            self._rows, self._costs = self._add_weighted(rows)
             return
-        statistics, best, self._workspace, _ = _run(
-            self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
-            self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._workspace, self.totals)
+        statistics, best, self._workspace, _ = _run(rows, self._workspace, self.totals)
         self._rows, self._costs = (statistics, best), None
         if self._confusions is not None:  # the same stream, after the choice
-            self._confusion_events = self._confusions[0][1].add_rows(
-                tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets, self._label_maps,
-                self._hyp_maps, self.maps.H, labels.max_expected, max_actual, best)
+            self._confusion_events = self._confusions[0][1].add_rows(rows, best)
 
     def operations(self, decoded, labels: Union[Sequence[Sequence[str]], "LabelBatch"],
                    languages: Optional[Sequence[Union[str, int]]] = None) -> Tuple[Tensor, Tensor]:
@@ -736,32 +772,13 @@ class Evaluator:
         (action, i, j, expected id or -1, actual id or -1) in upstream's order, ids in ``maps.spaces[o]``; ``counts`` is -1
         for a row with no candidate and -2 for a row with an out-of-range token.  Stream-ordered: nothing waits for the
         device (capturable in a graph with a ``LabelBatch`` after one call outside the capture has sized the workspace)."""
-        rows = [decoded.names.index(name) for name in self.names]
         tokens, counts = decoded.tokens, decoded.counts
-        hyp_counts = getattr(decoded, "hyp_counts", None)
-        if tokens.device != self.device:
-            raise ValueError(f"decoded results live on {tokens.device}, the evaluator on {self.device}")
         if tokens.dim() == 4:  # beam: candidate 0, the highest-scoring hypothesis
             tokens, counts = tokens[:, :, 0], counts[:, :, 0]
-        if rows != list(range(len(decoded.names))):
-            index = torch.tensor(rows, dtype=torch.long, device=self.device)
-            tokens, counts = tokens.index_select(0, index), counts.index_select(0, index)
-            hyp_counts = None if hyp_counts is None else hyp_counts.index_select(0, index)
-        counts = counts.to(torch.int32).contiguous()
-        hyp_counts = None if hyp_counts is None else hyp_counts.to(torch.int32).contiguous()
-        O, N, T = tokens.shape
-        if not isinstance(labels, LabelBatch):
-            if languages is None:
-                raise ValueError("labels given as strings need their languages")
-            labels = self.encode_labels(labels, languages)
-        if N != labels.N:
-            raise ValueError(f"{N} decoded utterances for {labels.N} labels")
-        max_actual = min(T * self.maps.hyp_fanout, _lib.EDIT_MAX_LENGTH)
+        rows = self._edit_rows(decoded, tokens.unsqueeze(2), counts.unsqueeze(2), labels, languages)
         if self.weighting is not None:
-            return self._operations_weighted(tokens, counts, hyp_counts, labels, max_actual)
-        operations, operation_counts, self._ops_workspace, _ = _run_operations(
-            self.device, tokens, counts, hyp_counts, labels.data, N, len(self.languages), self._maps, self._n_offsets,
-            self._label_maps, self._hyp_maps, self.maps.H, labels.max_expected, max_actual, self._ops_workspace)
+            return self._operations_weighted(rows)
+        operations, operation_counts, self._ops_workspace, _ = _run_operations(rows, self._ops_workspace)
         return operations, operation_counts
 
     def edits(self, decoded, labels: Sequence[Sequence[str]], languages: Sequence[Union[str, int]],
@@ -844,6 +861,11 @@ class _Pairs(NamedTuple):
     T: int
     symbols: List[Hashable]  # the id space: symbol of id v
 
+    def rows(self) -> _EditRows:
+        """One output, one group, the identity as both maps."""
+        return _EditRows(self.tokens, self.counts, None, self.labels, self.tokens.shape[1], 1, self.maps, self.V + 1,
+                         self.descriptor, self.descriptor, 1, self.max_expected, self.T)
+
 
 def _pairs(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]], device: torch.device) -> _Pairs:
     N = len(expected)
@@ -869,20 +891,40 @@ def _pairs(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Has
                   torch.from_numpy(identity).to(device), descriptor, V, max(map(len, label_ids)), T, list(space))
 
 
+def _pair_statistics(p: _Pairs, weights: Optional[_Weights] = None) -> List[EditStatistics]:
+    totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=p.tokens.device)
+    statistics = _run(p.rows(), None, totals, weights)[0]
+    return [EditStatistics(*row) for row in statistics.reshape(-1, 4).cpu().tolist()]
+
+
+def _pair_operations(p: _Pairs, weights: Optional[_Weights] = None) -> List[Tuple[List[Operation], float]]:
+    operations, counts, _, costs = _run_operations(p.rows(), None, weights)
+    records, lengths = operations[0].cpu().numpy(), counts[0].cpu().tolist()
+    costs = [float(length) for length in lengths] if costs is None else costs[0].cpu().tolist()  # unit costs: one per record
+    return [([(Action(action), i, j) for action, i, j in records[n, :length, :3].tolist()], costs[n])
+            for n, length in enumerate(lengths)]
+
+
+def _pair_confusions(p: _Pairs, device: torch.device, weights: Optional[_Weights] = None, capacity: Optional[int] = None
+                     ) -> Tuple[ConfusionCounts, Tensor]:
+    """One confusion call over the pairs of ``p`` into a new table (by default large enough for every key the pairs can
+    give); returns the accumulator and ``row_events`` int32 [1, N]."""
+    if capacity is None:
+        keys = min((p.V + 1) ** 2, int(p.counts.sum()) + p.labels.numel())  # distinct pairs; events
+        capacity = 16
+        while capacity < 2 * keys:
+            capacity *= 2
+    counts = ConfusionCounts(device, capacity, [TOTAL], ["pairs"], [p.symbols])
+    return counts, counts.add_rows(p.rows(), None, weights)
+
+
 def levensthein_statistics_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
                                  device=None) -> List[EditStatistics]:
     """``levensthein_statistics(expected[i], actual[i])`` for every pair, on the device (symbols compare by equality)."""
     if len(expected) != len(actual):
         raise ValueError("expected and actual differ in length")
     device = _device(device)
-    N = len(expected)
-    if N == 0:
-        return []
-    p = _pairs(expected, actual, device)
-    totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=device)
-    statistics, _, _, _ = _run(device, p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
-                               p.max_expected, p.T, None, totals)
-    return [EditStatistics(*row) for row in statistics.reshape(N, 4).cpu().tolist()]
+    return _pair_statistics(_pairs(expected, actual, device)) if len(expected) else []
 
 
 def levensthein_statistics(expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> EditStatistics:
@@ -896,31 +938,7 @@ def levensthein_operations_batch(expected: Sequence[Sequence[Hashable]], actual:
     if len(expected) != len(actual):
         raise ValueError("expected and actual differ in length")
     device = _device(device)
-    N = len(expected)
-    if N == 0:
-        return []
-    p = _pairs(expected, actual, device)
-    operations, counts, _, _ = _run_operations(device, p.tokens[:, :, 0], p.counts[:, :, 0], None, p.labels, N, 1, p.maps,
-                                               p.V + 1, p.descriptor, p.descriptor, 1, p.max_expected, p.T, None)
-    records, lengths = operations[0].cpu().numpy(), counts[0].cpu().tolist()
-    return [([(Action(action), i, j) for action, i, j in records[n, :lengths[n], :3].tolist()], float(lengths[n]))
-            for n in range(N)]
-
-
-def _pair_confusions(p: _Pairs, device: torch.device, weights: Optional[_Weights] = None, capacity: Optional[int] = None
-                     ) -> Tuple[ConfusionCounts, Tensor]:
-    """One confusion call over the pairs of ``p`` into a new table (by default large enough for every key the pairs can
-    give); returns the accumulator and ``row_events`` int32 [1, N]."""
-    N = p.tokens.shape[1]
-    if capacity is None:
-        keys = min((p.V + 1) ** 2, int(p.counts.sum()) + p.labels.numel())  # distinct pairs; events
-        capacity = 16
-        while capacity < 2 * keys:
-            capacity *= 2
-    counts = ConfusionCounts(device, capacity, [TOTAL], ["pairs"], [p.symbols])
-    row_events = counts.add_rows(p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
-                                 p.max_expected, p.T, None, weights)
-    return counts, row_events
+    return _pair_operations(_pairs(expected, actual, device)) if len(expected) else []
 
 
 def levensthein_confusions_batch(expected: Sequence[Sequence[Hashable]], actual: Sequence[Sequence[Hashable]],
@@ -1043,12 +1061,8 @@ class PropertyWeighting:
                                      device=None) -> List[EditStatistics]:
         if len(expected) == 0 and len(actual) == 0:
             return []
-        device, p, weights = self._prepare(expected, actual, device)
-        N = len(expected)
-        totals = torch.zeros(1, 1, 4, dtype=torch.int64, device=device)
-        statistics, _, _, _ = _run(device, p.tokens, p.counts, None, p.labels, N, 1, p.maps, p.V + 1, p.descriptor, p.descriptor,
-                                   1, p.max_expected, p.T, None, totals, weights)
-        return [EditStatistics(*row) for row in statistics.reshape(N, 4).cpu().tolist()]
+        _, p, weights = self._prepare(expected, actual, device)
+        return _pair_statistics(p, weights)
 
     def levensthein_statistics(self, expected: Sequence[Hashable], actual: Sequence[Hashable], device=None) -> EditStatistics:
         """Upstream's ``PropertyWeighting.levensthein_statistics(string_a=expected, string_b=actual)``."""
@@ -1058,12 +1072,8 @@ class PropertyWeighting:
                                      device=None) -> List[Tuple[List[Operation], float]]:
         if len(expected) == 0 and len(actual) == 0:
             return []
-        device, p, weights = self._prepare(expected, actual, device)
-        N = len(expected)
-        operations, counts, _, costs = _run_operations(device, p.tokens[:, :, 0], p.counts[:, :, 0], None, p.labels, N, 1, p.maps,
-                                                       p.V + 1, p.descriptor, p.descriptor, 1, p.max_expected, p.T, None, weights)
-        records, lengths, costs = operations[0].cpu().numpy(), counts[0].cpu().tolist(), costs[0].cpu().tolist()
-        return [([(Action(action), i, j) for action, i, j in records[n, :lengths[n], :3].tolist()], costs[n]) for n in range(N)]
+        _, p, weights = self._prepare(expected, actual, device)
+        return _pair_operations(p, weights)
 
     def levensthein_operations(self, expected: Sequence[Hashable], actual: Sequence[Hashable], device=None
                                ) -> Tuple[List[Operation], float]:

@@ -185,11 +185,12 @@ def load() -> C.CDLL:
         lib.amx_resample_bank.restype = i32
         lib.amx_resample.argtypes = [i32, vp, i64, i64, vp, vp, vp, vp, i64, i32, i64, vp, vp]
         lib.amx_resample.restype = i32
+    # device to workspace_bytes: what the statistics and confusion entries begin with, uniform and weighted
+    edit_head = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64, i64, vp, C.c_size_t]
     if hasattr(lib, "amx_edit_statistics"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_edit_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
         lib.amx_edit_workspace.restype = i32
-        lib.amx_edit_statistics.argtypes = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
-                                            i32, i64, i64, vp, C.c_size_t, vp, vp, vp, vp]
+        lib.amx_edit_statistics.argtypes = edit_head + [vp, vp, vp, vp]
         lib.amx_edit_statistics.restype = i32
     if hasattr(lib, "amx_edit_operations"):
         lib.amx_edit_operations_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
@@ -203,8 +204,7 @@ def load() -> C.CDLL:
         lib.amx_edit_cost_table_bytes.restype = i32
         lib.amx_edit_cost_table.argtypes = [i32, vp, i64, i64, vp, vp]
         lib.amx_edit_cost_table.restype = i32
-        lib.amx_edit_weighted_statistics.argtypes = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp,
-                                                     vp, vp, i32, i64, i64, vp, C.c_size_t, f32, f32, vp, vp, vp, vp, vp, vp, vp]
+        lib.amx_edit_weighted_statistics.argtypes = edit_head + [f32, f32, vp, vp, vp, vp, vp, vp, vp]
         lib.amx_edit_weighted_statistics.restype = i32
         lib.amx_edit_weighted_operations.argtypes = [i32, vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
                                                      i32, i64, i64, vp, C.c_size_t, f32, f32, vp, vp, i64, vp, vp, vp, vp]
@@ -212,13 +212,12 @@ def load() -> C.CDLL:
         lib.amx_edit_matrix.argtypes = [i32, vp, vp, vp, vp, i64, i64, i64, f32, f32, vp, i64, vp, C.c_size_t, vp, vp, vp]
         lib.amx_edit_matrix.restype = i32
     if hasattr(lib, "amx_edit_confusions"):  # (added to ABI 7 by name: absent from older builds)
-        head = [i32, vp, i64, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64, i64, vp, C.c_size_t]
         tail = [vp, vp, i64, vp, vp, vp]  # best, table, capacity, row_events, counters, stream
         lib.amx_edit_confusion_table_bytes.argtypes = [i64, C.POINTER(C.c_size_t)]
         lib.amx_edit_confusion_table_bytes.restype = i32
-        lib.amx_edit_confusions.argtypes = head + tail
+        lib.amx_edit_confusions.argtypes = edit_head + tail
         lib.amx_edit_confusions.restype = i32
-        lib.amx_edit_weighted_confusions.argtypes = head + [C.c_float, C.c_float, vp, vp] + tail
+        lib.amx_edit_weighted_confusions.argtypes = edit_head + [C.c_float, C.c_float, vp, vp] + tail
         lib.amx_edit_weighted_confusions.restype = i32
         lib.amx_edit_confusion_merge.argtypes = [i32, vp, i64, vp, i64, vp, vp]
         lib.amx_edit_confusion_merge.restype = i32

@@ -46,8 +46,7 @@ def _per_row(ev, p, weights=None, capacity=2 ** 16):
     N = p.tokens.shape[1]
     p.labels[N + 1:2 * N + 1] = torch.arange(N, dtype=torch.int32, device=p.labels.device)
     counts = ConfusionCounts(p.tokens.device, capacity, [str(n) for n in range(N)], ["pairs"], [p.symbols])
-    row_events = counts.add_rows(p.tokens, p.counts, None, p.labels, N, N, p.maps, p.V + 1, p.descriptor, p.descriptor, 1,
-                                 p.max_expected, p.T, None, weights)
+    row_events = counts.add_rows(p.rows()._replace(G=N), None, weights)
     return counts, row_events.reshape(N).cpu().tolist()
 
 
@@ -267,8 +266,7 @@ def test_grow_and_merge(ev):
         counts = ConfusionCounts(device, 64, ["total"], ["pairs"], [both.symbols])
         present = torch.zeros(1, N, dtype=torch.int32, device=device)
         present[0, rows] = 1
-        row_events = counts.add_rows(both.tokens, both.counts, present, both.labels, N, 1, both.maps, both.V + 1, both.descriptor,
-                                     both.descriptor, 1, both.max_expected, both.T, None)
+        row_events = counts.add_rows(both.rows()._replace(hyp_counts=present))
         assert torch.equal(row_events[0] == -1, present[0] == 0)  # rows without a candidate
         return counts
 

@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from allophant_amd import lib, synthetic  # noqa: E402
+from allophant_amd import synthetic  # noqa: E402
 from allophant_amd.estimator import Batch, Estimator  # noqa: E402
 from allophant_amd.evaluation import Evaluator  # noqa: E402
 from allophant_amd.phonetic import IPA_LAYERS, AttributeTable  # noqa: E402
@@ -99,13 +99,9 @@ def main():
         tokens, token_counts = decoded.tokens, decoded.counts
         if tokens.dim() == 3:
             tokens, token_counts = tokens.unsqueeze(2), token_counts.unsqueeze(2)
-        token_counts = token_counts.to(torch.int32).contiguous()
-        hyp_counts = getattr(decoded, "hyp_counts", None)
-        hyp_counts = None if hyp_counts is None else hyp_counts.to(torch.int32).contiguous()
+        rows = ev._edit_rows(decoded, tokens, token_counts, static, None)
         best = ev.rows()[1]
-        max_actual = min(tokens.shape[-1] * ev.maps.hyp_fanout, lib.EDIT_MAX_LENGTH)
-        call = lambda: counts.add_rows(tokens, token_counts, hyp_counts, static.data, N, len(languages), ev._maps,  # noqa: E731
-                                       ev._n_offsets, ev._label_maps, ev._hyp_maps, ev.maps.H, static.max_expected, max_actual, best)
+        call = lambda: counts.add_rows(rows, best)  # noqa: E731
         confusions_ms = timed(call, args.iters)
         row_events = call().cpu().numpy()
         added, dropped = counts.events()

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from allophant_amd import evaluation, lib, synthetic  # noqa: E402
+from allophant_amd import evaluation, synthetic  # noqa: E402
 from allophant_amd.estimator import Batch, Estimator  # noqa: E402
 from allophant_amd.evaluation import Evaluator, PropertyWeighting  # noqa: E402
 from allophant_amd.phonetic import IPA_LAYERS, AttributeTable  # noqa: E402
@@ -94,30 +94,25 @@ def main():
     totals = torch.zeros(G, O, 4, dtype=torch.int64, device=device)
     for case, decoded in (("greedy", greedy), ("beam16_nbest4", beam)):
         tokens, counts = decoded.tokens, decoded.counts
-        hyp_counts = getattr(decoded, "hyp_counts", None)
         if tokens.dim() == 3:
             tokens, counts = tokens.unsqueeze(2), counts.unsqueeze(2)
-        counts = counts.to(torch.int32).contiguous()
-        hyp_counts = None if hyp_counts is None else hyp_counts.to(torch.int32).contiguous()
-        max_actual = min(tokens.shape[3] * ev.maps.hyp_fanout, lib.EDIT_MAX_LENGTH)
+        rows = ev._edit_rows(decoded, tokens, counts, static, None)
+        max_actual = rows.max_actual
         workspace = [None]
 
         def statistics(w):
-            out = evaluation._run(device, tokens, counts, hyp_counts, static.data, N, G, ev._maps, ev._n_offsets, ev._label_maps,
-                                  ev._hyp_maps, ev.maps.H, static.max_expected, max_actual, workspace[0], totals, w)
+            out = evaluation._run(rows, workspace[0], totals, w)
             workspace[0] = out[2]
             return out
 
         uniform_ms = timed(lambda: statistics(None), args.iters)
         weighted_ms = timed(lambda: statistics(weights), args.iters)
         same = torch.equal(statistics(None)[0], statistics(weights)[0])
-        first_tokens, first_counts = tokens[:, :, 0], counts[:, :, 0].contiguous()
+        candidate0 = rows.first()
         ops_workspace = [None]
 
         def operations(w):
-            out = evaluation._run_operations(device, first_tokens, first_counts, hyp_counts, static.data, N, G, ev._maps,
-                                             ev._n_offsets, ev._label_maps, ev._hyp_maps, ev.maps.H, static.max_expected,
-                                             max_actual, ops_workspace[0], w)
+            out = evaluation._run_operations(candidate0, ops_workspace[0], w)
             ops_workspace[0] = out[2]
             return out
 
