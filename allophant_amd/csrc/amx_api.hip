@@ -81,8 +81,9 @@ struct amx_handle_s {
 
     // weights
     float *c0_w = nullptr, *c0_b = nullptr;
-    double* c0_stats = nullptr;  // conv layer 0 on the matrix pipe: fp64 mean / covariance of the rows [w_c, b_c] (amx_common.h)
-    float c0_wscale = 1.f;       // power of two its fp16 weight planes are built under
+    Conv0Route c0{};             // the kernels of conv layer 0 (conv0_route, amx_common.h): fixed at amx_create
+    double* c0_stats = nullptr;  // its CONV0_STATS_TABLE: fp64 mean / covariance of the rows [w_c, b_c]
+    float c0_wscale = 1.f;       // matrix pipe: power of two its fp16 weight planes are built under
     // the variant of the wav2vec 2.0 encoder (amx_config ABI 4)
     bool gn = false;         // feat_extract_norm == "group": GroupNorm over time behind conv layer 0, no norm behind layers 1..
     bool stable = true;      // do_stable_layer_norm: pre-LN layers + final LayerNorm; false: post-LN layers
@@ -452,20 +453,22 @@ static void* alloc_planes(amx_handle h, int64_t elems_per_plane) {
 
 // ---- amx_create, section by section (each returns an AMX_* code with the message set; amx_create destroys the handle) ----
 
-static int check_config(const amx_config* cfg, int n_classes) {
+// (interleaved planes: see amx_handle_s::il)
+static bool planes_interleaved(const amx_config* cfg) {
+    return prec_planes(cfg->precision) > 1 && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
+}
+
+static int check_config(const amx_config* cfg, int n_classes, const Conv0Route& c0) {
     if (cfg->abi_version != AMX_ABI_VERSION) return fail(nullptr, AMX_EINVAL, "ABI version mismatch");
     if (cfg->n_conv < 2 || cfg->n_conv > AMX_MAX_CONV) return fail(nullptr, AMX_EINVAL, "n_conv out of range");
     if (cfg->heads < 1 || cfg->hidden % cfg->heads != 0 || (cfg->hidden / cfg->heads) % 8 || cfg->hidden / cfg->heads > 128)
         return fail(nullptr, AMX_EINVAL, "head_dim (hidden / heads) must be a multiple of 8 and at most 128");
-    if (cfg->hidden > 2048 || cfg->hidden % 8 || cfg->conv_dim > 1024 || cfg->conv_dim % 8)
-        return fail(nullptr, AMX_EINVAL, "hidden must be a multiple of 8 and <= 2048, conv_dim a multiple of 8 and <= 1024");
-    if (cfg->conv_dim >= 64 && cfg->conv_dim % 64) return fail(nullptr, AMX_EINVAL, "conv_dim must be < 64 or a multiple of 64");
+    if (cfg->hidden > 2048 || cfg->hidden % 8 || cfg->conv_dim % 8)
+        return fail(nullptr, AMX_EINVAL, "hidden must be a multiple of 8 and <= 2048, conv_dim a multiple of 8");
     if (cfg->conv_kernel[0] > 16) return fail(nullptr, AMX_EINVAL, "first conv kernel must be <= 16");
     for (int i = 0; i < cfg->n_conv; ++i)
         if (cfg->conv_kernel[i] < 1 || cfg->conv_stride[i] < 1) return fail(nullptr, AMX_EINVAL, "conv kernels and strides must be positive");
-    if (conv0_window_lds_bytes(cfg->conv_kernel[0], cfg->conv_stride[0], cfg->feat_extract_norm == AMX_NORM_GROUP) > 64 * 1024)
-        return fail(nullptr, AMX_EINVAL, "first conv stride too large for the LDS window of the conv-0 kernels (stride <= 16 with the "
-                                         "group-norm extractor, <= 127 otherwise)");
+    if (c0.refusal) return fail(nullptr, AMX_EINVAL, c0.refusal);  // a conv_dim or first stride no first-layer kernel serves
     if (cfg->hidden % cfg->pos_groups != 0 || (cfg->hidden / cfg->pos_groups) % 8 || cfg->hidden / cfg->pos_groups > 128)
         return fail(nullptr, AMX_EINVAL, "hidden / pos_groups must be a multiple of 8 and <= 128");
     if (cfg->ffn % 8) return fail(nullptr, AMX_EINVAL, "ffn must be a multiple of 8");
@@ -551,10 +554,9 @@ static int create_feature_extractor(amx_handle h, const TensorMap& tm, float* st
         }
         c_in = C;
     }
-    if (!conv0_mfma_eligible(C, cfg.conv_kernel[0], cfg.conv_stride[0])) return AMX_OK;
     const amx_tensor* wt = tm.get(p0 + "conv.weight");
-    h->c0_wscale = pack_scale({{wt, 1.f}});
-    if (h->gn) return AMX_OK;
+    if (h->c0.mfma) h->c0_wscale = pack_scale({{wt, 1.f}});
+    if (h->c0.stats != CONV0_STATS_TABLE) return AMX_OK;
     // conv layer 0 on the matrix pipe (LayerNorm variant, k = 10, C = 512): the LayerNorm statistics of a frame are a linear
     // and a quadratic form of its 10 samples -- mean_c(w_c . x + b_c) = m . [x; 1], var_c = [x; 1]^T G [x; 1] with m / G the mean
     // / covariance of the rows [w_c, b_c] over the channels -- tabulated here in fp64
@@ -871,7 +873,9 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
                           const amx_tensor* tensors, int n_tensors) {
     if (!out || !cfg || !classes || !tensors) return fail(nullptr, AMX_EINVAL, "null argument");
     *out = nullptr;
-    if (int rc = check_config(cfg, n_classes)) return rc;
+    const Conv0Route c0 = conv0_route(cfg->precision, planes_interleaved(cfg), cfg->conv_dim, cfg->conv_kernel[0], cfg->conv_stride[0],
+                                      cfg->feat_extract_norm == AMX_NORM_GROUP);
+    if (int rc = check_config(cfg, n_classes, c0)) return rc;
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -891,7 +895,8 @@ extern "C" int amx_create(amx_handle* out, int device, const amx_config* cfg, co
     h->adapter = h->stable ? cfg->adapter_attn_dim : 0;
     // (hidden too -- round 6: the residual-stream planes [M, hidden] are GEMM operands like the others; a hidden size off the
     // 32-element blocks -- 240 = 2 heads of 120 -- ran interleaved planes through kernels that assume block-aligned rows)
-    h->il = h->NT > 1 && cfg->conv_dim % 32 == 0 && cfg->ffn % 32 == 0 && cfg->hidden % 32 == 0;
+    h->il = planes_interleaved(cfg);
+    h->c0 = c0;
     h->classes.assign(classes, classes + n_classes);
     auto bail = [&](int code) {
         g_create_error = h->err;
@@ -1674,7 +1679,7 @@ static int plan_pass(amx_handle h, const float* audio, const int64_t* lengths, i
     // ---- the rest of the plan: every buffer and host-side table the pass needs exists before anything is enqueued, so that
     // enqueue_pass issues nothing but memsets, kernels and device copies (which is what a HIP graph may hold) ----
     if (h->gn) {
-        WS("gn_partial", conv0_groupnorm_partial_bytes(N, (int)P.Ts[1], C), P.gn_partial);
+        WS("gn_partial", h->c0.gn_partial_bytes(N, (int)P.Ts[1]), P.gn_partial);
         WS("gn_scale", (size_t)N * C * 4, P.gn_scale);
         WS("gn_shift", (size_t)N * C * 4, P.gn_shift);
     }
@@ -1780,19 +1785,19 @@ static int enqueue_pass(amx_handle h, const PassPlan& P, hipStream_t s) {
     if (!(P.flags & AMX_FLAG_CONTINUE)) launch_zero(h->nonfinite, 4, s);
     // ---- input normalisation statistics + conv layer 0 (fused norm + conv + LN + GELU) ----
     { Timed t_(h, AMX_KC_OTHER); launch_audio_stats(P.d_audio, (const int64_t*)P.d_len, N, P.L, (double*)P.d_partial, (float*)P.d_stats, c.do_normalize, s); }
-    if (h->gn) {
-        // group-norm variant: GroupNorm statistics over ALL frames of the padded length (upstream normalises the padded batch
-        // tensor), then conv + affine + GELU; frame blocks in an utterance's padding may still be skipped in the second pass
+    {
+        // (group-norm variant: GroupNorm statistics over ALL frames of the padded length -- upstream normalises the padded batch
+        // tensor --, then conv + affine + GELU; frame blocks in an utterance's padding may still be skipped in the second pass)
+        Conv0Args a{};
+        a.audio = P.d_audio; a.lengths = (const int64_t*)P.d_len; a.mean_rstd = (const float*)P.d_stats;
+        a.N = N; a.L = P.L; a.T1 = (int)P.Ts[1]; a.C = C; a.k = c.conv_kernel[0]; a.stride = c.conv_stride[0];
+        a.w = h->c0_w; a.b = h->conv_b[0]; a.gamma = h->conv_g[0]; a.beta = h->conv_be[0];
+        a.eps = 1e-5f; a.do_normalize = c.do_normalize;
+        a.table = h->c0_stats; a.w_scale = h->c0_wscale;
+        a.gn_partial = (double*)P.gn_partial; a.gn_scale = (float*)P.gn_scale; a.gn_shift = (float*)P.gn_shift;
+        a.out = P.actA; a.out_plane = pln(h, P.rows1 * C); a.skip_padding = P.ragged ? 1 : 0;
         Timed t_(h, AMX_KC_CONV0);
-        launch_conv0_groupnorm(prec, P.d_audio, (const int64_t*)P.d_len, (const float*)P.d_stats, N, P.L, (int)P.Ts[1], C, c.conv_kernel[0],
-                               c.conv_stride[0], h->c0_w, h->conv_b[0], h->conv_g[0], h->conv_be[0], 1e-5f, c.do_normalize,
-                               (double*)P.gn_partial, (float*)P.gn_scale, (float*)P.gn_shift, P.actA, pln(h, P.rows1 * C), P.ragged ? 1 : 0, s,
-                               conv0_mfma_eligible(C, c.conv_kernel[0], c.conv_stride[0]) ? h->c0_wscale : 0.f);
-    } else {
-        Timed t_(h, AMX_KC_CONV0);
-        launch_conv0(prec, P.d_audio, (const int64_t*)P.d_len, (const float*)P.d_stats, N, P.L, (int)P.Ts[1], C, c.conv_kernel[0],
-                     c.conv_stride[0], h->c0_w, h->conv_b[0], h->conv_g[0], h->conv_be[0], 1e-5f, c.do_normalize, P.actA,
-                     pln(h, P.rows1 * C), P.ragged ? 1 : 0, s, h->c0_stats, h->c0_wscale);
+        launch_conv0(h->c0, a, s);
     }
     // ---- conv layers 1..n-1: implicit GEMM over overlapping channels-last windows, then LN + GELU rows ----
     void* cur = P.actA;
@@ -2228,7 +2233,7 @@ extern "C" int amx_pass_info(amx_handle h, int32_t* info, int n) {
     if (!h || !info || n < 0) return AMX_EINVAL;
     const int32_t values[AMX_PASS_INFO_COUNT] = {h->last_fold ? 1 : 0, h->last_packed, h->last_graph,
                                                  (int32_t)std::min<int64_t>(h->last_rows, INT32_MAX), (int32_t)(h->pass_counter & 0x7fffffff),
-                                                 h->last_attention};
+                                                 h->last_attention, h->c0.code()};
     for (int i = 0; i < n && i < AMX_PASS_INFO_COUNT; ++i) info[i] = values[i];
     return AMX_OK;
 }

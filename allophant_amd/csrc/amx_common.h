@@ -414,35 +414,70 @@ int attention_form(const AttnParams& p);
 int launch_attention(int prec, const AttnParams& p, hipStream_t stream);  // returns the form it launched
 
 // ---------------------------------------------------------------------------------------------------------------
-// row-wise / elementwise kernels (amx_rowops.hip)
+// conv layer 0 (amx_conv0.hip)
 // ---------------------------------------------------------------------------------------------------------------
+// input normalisation statistics [N][mean, rstd]; applied on the fly by the first-layer kernels
 void launch_audio_stats(const float* audio, const int64_t* lengths, int N, int64_t L, double* partial, float* mean_rstd,
                         int do_normalize, hipStream_t s);
-// conv layer 0 (C_in = 1) + LayerNorm(C) + GELU, fused; writes planes [N*T1, C]
-void launch_conv0(int prec, const float* audio, const int64_t* lengths, const float* mean_rstd, int N, int64_t L, int T1,
-                  int C, int k, int stride, const float* w /*[C,k]*/, const float* b, const float* gamma,
-                  const float* beta, float eps, int do_normalize, void* out, int64_t out_plane, int skip_padding, hipStream_t s,
-                  const double* mfma_stats = nullptr, float w_scale = 1.f);
-// (skip_padding: frame blocks that start beyond an utterance's own frames are not computed -- ragged batches)
-// (mfma_stats: device table of CONV0_MFMA_STATS doubles for the matrix-pipe form of the kernel, conv0_mfma_eligible shapes:
-// the mean of the rows [w_c, b_c] over the channels (11) and their covariance (11 x 11, row-major), computed in fp64 at
-// amx_create; w_scale: the power of two the fp16 weight planes are built under.  Null: the VALU kernel.)
+
+// Where the normalisation statistics of the first layer come from.
+enum Conv0Stats {
+    CONV0_STATS_NONE = 0,        // LayerNorm, scalar apply: the kernel reduces over the channels of each frame itself
+    CONV0_STATS_TABLE = 1,       // LayerNorm, matrix-pipe apply: per frame from the fp64 table of amx_create (CONV0_MFMA_STATS)
+    CONV0_STATS_COVARIANCE = 2,  // GroupNorm from the utterance's 10 x 10 sample covariance: no second evaluation of the conv
+    CONV0_STATS_RECOMPUTE8 = 3,  // GroupNorm, conv recomputed with the register blocking of the scalar apply (C = 512, k = 10)
+    CONV0_STATS_RECOMPUTE = 4,   // GroupNorm, conv recomputed, any shape
+};
+// the table of CONV0_STATS_TABLE: the mean of the rows [w_c, b_c] over the channels (11 doubles) and their covariance (11 x 11,
+// row-major), computed in fp64 at amx_create
 constexpr int CONV0_MFMA_STATS = 11 + 121;
-bool conv0_mfma_eligible(int C, int k, int stride);
-// the group-norm feature extractor (feat_extract_norm = "group"): conv layer 0 + GroupNorm(C groups) over the T1 frames of the
-// padded length + GELU.  Two passes over the audio (the k-tap conv is recomputed, never stored): per-(utterance, channel)
-// fp64 statistics into `partial` (conv0_groupnorm_partial_bytes) -> scale / shift [N, C] -> the conv0 kernel with the affine
-// form y = conv * scale + shift.  gamma / beta: the GroupNorm affine parameters [C]
-size_t conv0_groupnorm_partial_bytes(int N, int T1, int C);
-// dynamic LDS the conv-0 kernels request for this first-layer geometry (must stay <= 64 KiB: checked by amx_create)
-size_t conv0_window_lds_bytes(int k, int stride, int group_norm);
-void launch_conv0_groupnorm(int prec, const float* audio, const int64_t* lengths, const float* mean_rstd, int N, int64_t L, int T1,
-                            int C, int k, int stride, const float* w, const float* b, const float* gamma, const float* beta,
-                            float eps, int do_normalize, double* partial, float* scale, float* shift, void* out, int64_t out_plane,
-                            int skip_padding, hipStream_t s, float mfma_w_scale = 0.f);
-// (mfma_w_scale > 0 and a conv0_mfma_eligible shape: GroupNorm statistics from the utterance's 10 x 10 sample covariance in fp64
-// -- no second evaluation of the convolution -- and the apply pass on the matrix pipe; the power of two is that of the fp16
-// weight planes)
+
+// The kernels that run the first layer of a model: decided once per handle by conv0_route, which holds every condition.
+// amx_create refuses from it, builds the table and weight scale it asks for, the plan sizes `gn_partial` from it, and
+// launch_conv0 launches what it names.
+struct Conv0Route {
+    const char* refusal;  // null: kernels exist for the shape; else amx_create's message
+    int prec;
+    bool group_norm;      // GroupNorm(C groups) over the T1 frames of the padded length instead of LayerNorm over the channels
+    bool mfma;            // apply pass: conv0_mfma_kernel (needs Conv0Args.w_scale); false: conv0_kernel<CPL, KW>
+    int kw, cpl;          //   (0 on the matrix pipe)
+    Conv0Stats stats;
+    size_t apply_lds, stats_lds;  // dynamic LDS of the apply launch and of the statistics launch (0: none), both <= 64 KiB
+    int stats_frames;             // frames per workgroup of the statistics launch ...
+    size_t stats_block_bytes;     // ... and the bytes of `gn_partial` each workgroup writes
+    size_t gn_partial_bytes(int N, int T1) const {
+        return stats_frames ? (size_t)N * ((T1 + stats_frames - 1) / stats_frames) * stats_block_bytes : 0;
+    }
+    // amx_pass_info, AMX_PASS_INFO_CONV0: 10000 * stats + 100 * kw + cpl
+    int code() const { return 10000 * (int)stats + 100 * kw + cpl; }
+};
+// pure host function; `il`: the handle's plane buffers are interleaved (PLANE_IL)
+Conv0Route conv0_route(int prec, bool il, int C, int k, int stride, bool group_norm);
+
+// conv layer 0 (C_in = 1) + LayerNorm(C) or GroupNorm(C groups, over time) + GELU, fused; writes planes [N * T1, C]
+struct Conv0Args {
+    const float* audio;      // [N, L]
+    const int64_t* lengths;  // [N]
+    const float* mean_rstd;  // [N][2], launch_audio_stats
+    int N;
+    int64_t L;
+    int T1, C, k, stride;
+    const float *w /*[C, k]*/, *b, *gamma, *beta;  // gamma / beta: the affine parameters [C] of the norm
+    float eps;
+    int do_normalize;
+    const double* table;  // CONV0_STATS_TABLE: device table of CONV0_MFMA_STATS doubles
+    float w_scale;        // matrix pipe: the power of two its fp16 weight planes are built under
+    double* gn_partial;   // group norm: fp64 block partials (Conv0Route::gn_partial_bytes) -> scale / shift [N, C], which the
+    float *gn_scale, *gn_shift;  // apply pass uses in the affine form y = conv * scale + shift
+    void* out;
+    int64_t out_plane;
+    int skip_padding;  // frame blocks that start beyond an utterance's own frames are not computed -- ragged batches
+};
+void launch_conv0(const Conv0Route& r, const Conv0Args& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------------------------
+// row-wise / elementwise kernels (amx_rowops.hip)
+// ---------------------------------------------------------------------------------------------------------------
 // rows of the padded [N, T, D] fp32 matrix <-> rows of the packed [sum(frame_len), D] matrix (utterance n at row_off[n]);
 // only rows t < frame_len[n] move
 void launch_pack_rows(const float* padded, float* packed, const int* row_off, const int* frame_len, int N, int T, int D, bool unpack,

@@ -993,13 +993,21 @@ class Estimator:
         products, ``packed`` 0 / 1 / 2 = padded rows / packed layers / packed from the feature projection on, ``graph`` 0 / 1 / 2
         = eager / recorded / replayed, ``rows`` = frames the encoder layers worked on, ``id`` = number of the pass, ``attention`` = the
         form of the attention kernels (0 / 1: 8- / 4-wave workgroups, 2: 4 waves with the key split, 3: the long-key kernel, 4 / 5:
-        a head dimension other than 64 on 64- / 128-wide rows)."""
+        a head dimension other than 64 on 64- / 128-wide rows), ``conv0`` = the kernels of conv layer 0 (see ``conv0_route``)."""
         if _lib.AMX_ABI_VERSION < 6:
             return {}
         n = len(_lib.PASS_INFO)
         info = (C.c_int32 * n)()
         _lib.check(self._lib, self._handle, self._lib.amx_pass_info(self._handle, info, n))
         return {k: int(info[i]) for i, k in enumerate(_lib.PASS_INFO)}
+
+    def conv0_route(self) -> Dict[str, Any]:
+        """The kernels conv layer 0 of this model runs in (``AMX_PASS_INFO_CONV0``; fixed when the estimator is built): ``apply``
+        ``"mfma"`` (matrix pipe) or ``"scalar"`` with the ``kw`` taps and ``cpl`` channels per lane the kernel is instantiated for,
+        and ``stats``, where the normalisation statistics come from (``lib.CONV0_STATS``)."""
+        code = self.pass_info()["conv0"]
+        kw, cpl = code // 100 % 100, code % 100
+        return {"apply": "scalar" if cpl else "mfma", "kw": kw, "cpl": cpl, "stats": _lib.CONV0_STATS[code // 10000]}
 
     def check_finite(self) -> None:
         """Range check of the last ``predict`` (``amx_check_finite``; no upstream counterpart -- the reference computes in

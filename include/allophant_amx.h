@@ -88,7 +88,7 @@ typedef struct amx_handle_s* amx_handle;
 typedef struct amx_config {
     int32_t abi_version;                 /* AMX_ABI_VERSION */
     int32_t n_conv;                      /* feature-extractor conv layers (7) */
-    int32_t conv_dim;                    /* 512 */
+    int32_t conv_dim;                    /* 512; a multiple of 8 below 64, or 64, 128, 256, 512 (AMX_EINVAL otherwise) */
     int32_t conv_kernel[AMX_MAX_CONV];   /* 10,3,3,3,3,2,2 */
     int32_t conv_stride[AMX_MAX_CONV];   /* 5,2,2,2,2,2,2 */
     int32_t hidden;                      /* 1024 (a multiple of 8, at most 2048: XLS-R 1B / 2B have 1280 / 1920; ABI 6) */
@@ -225,7 +225,13 @@ int amx_graph_info(amx_handle h, int64_t* captures, int64_t* replays);
                                      the key tiles split over two wave groups; 3: the long-key kernel (64 queries per wave); 4 / 5: a head
                                      dimension other than 64, on rows of 64 / 128 columns; -1: an encoder without layers.  Which one a
                                      batch takes depends on its geometry and on the device's CU count */
-#define AMX_PASS_INFO_COUNT 6
+#define AMX_PASS_INFO_CONV0 6     /* the kernels conv layer 0 runs in (appended like ATTENTION; fixed at amx_create, so valid before the
+                                     first pass): 10000 * statistics + 100 * KW + CPL.  KW / CPL: the taps and channels per lane the scalar
+                                     apply kernel is instantiated for, 0 / 0 when the apply pass runs on the matrix pipe.  statistics: 0 =
+                                     LayerNorm inside the scalar kernel; 1 = LayerNorm from the fp64 table (matrix pipe); 2 = GroupNorm from
+                                     the sample covariance (matrix pipe); 3 / 4 = GroupNorm with the convolution recomputed, register-
+                                     blocked / general (scalar apply) */
+#define AMX_PASS_INFO_COUNT 7
 int amx_pass_info(amx_handle h, int32_t* info, int n);
 
 /* Range check of the last amx_forward on `stream` (no upstream counterpart: the reference computes in fp32).  The 16-bit

@@ -1,4 +1,4 @@
-"""conv layer 0 on the matrix pipe (round 5: ``conv0_mfma_kernel``, csrc/amx_rowops.hip) against the CPU oracle.
+"""conv layer 0 on the matrix pipe (round 5: ``conv0_mfma_kernel``, csrc/amx_conv0.hip) against the CPU oracle.
 
 The kernel replaces the fp32 FMA taps and the two LayerNorm reductions of ``conv0_kernel`` by one split-precision MFMA per
 (16 channels x 16 frames) and by per-frame statistics taken from fp64 tables (mean and covariance of the conv rows over the
