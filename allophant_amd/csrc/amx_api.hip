@@ -6,6 +6,7 @@
 #include "../../include/allophant_amx_align.h"
 #include "../../include/allophant_amx_score.h"
 #include "../../include/allophant_amx_search.h"
+#include "../../include/allophant_amx_variants.h"
 #include "../../include/allophant_amx_restrict.h"
 #include "../../include/allophant_amx_long.h"
 #include "../../include/allophant_amx_resample.h"
@@ -2626,6 +2627,44 @@ extern "C" int amx_ctc_score(amx_handle h, const float* out, const int64_t* fram
         if ((rc = align_check_classes(h, d.C, 0))) return rc;
     return score_rows_run(h, 0, c, frame_lengths, candidates, target_offsets, target_ids, max_target, workspace, workspace_bytes,
                           log_likelihood, occupancy, position_sums, score_sums, posteriors, status, (hipStream_t)stream);
+}
+
+// =================================================================================================================
+// CTC scoring of every one-edit variant of a transcript (the alignment's geometry checks)
+// =================================================================================================================
+extern "C" int amx_ctc_variants_workspace(int64_t rows, int64_t T, int64_t max_target, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = align_check(nullptr, rows, T, max_target, AMX_VARIANTS_MAX_TARGET)) return rc;
+    if (!ctc_variants_workspace_bytes(rows, T, max_target, bytes))
+        return fail(nullptr, AMX_EINVAL, "variants workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_variants_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                          const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index,
+                                          const int32_t* target_offsets, const int32_t* target_ids, int64_t max_target, void* workspace,
+                                          size_t workspace_bytes, float* log_likelihood, float* substitutions, float* insertions,
+                                          int32_t* status, void* stream) {
+    if (int rc = align_check(nullptr, N, T, max_target, AMX_VARIANTS_MAX_TARGET)) return rc;
+    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
+    if (C > AMX_VARIANTS_MAX_CLASSES)
+        return fail(nullptr, AMX_EINVAL, "variants take at most " + std::to_string(AMX_VARIANTS_MAX_CLASSES) + " classes, got " + std::to_string(C));
+    if (N == 0) return AMX_OK;
+    if (!frame_lengths || !target_offsets || !log_likelihood || !insertions || !status || (T && !emissions) ||
+        (max_target && (!target_ids || !substitutions)))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    size_t need = 0;
+    if (!ctc_variants_workspace_bytes(N, T, max_target, &need)) return fail(nullptr, AMX_EINVAL, "variants workspace size not representable");
+    if (int rc = check_workspace(nullptr, "variants", need, workspace, workspace_bytes)) return rc;
+    CtcRows c = rows_of_tensor(emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    if (int rc = ctc_rows_begin(nullptr, device, nullptr, &c, (hipStream_t)stream)) return rc;
+    c.target_offsets = target_offsets, c.target_ids = target_ids, c.max_target = (int)max_target;
+    VariantsArgs a{};
+    static_cast<CtcRows&>(a) = c;
+    a.forward = (float*)workspace;
+    a.log_likelihood = log_likelihood, a.substitutions = substitutions, a.insertions = insertions, a.status = status;
+    launch_ctc_variants(a, (hipStream_t)stream);
+    return ctc_launched(nullptr, "variants");
 }
 
 // =================================================================================================================

@@ -640,6 +640,22 @@ struct ScoreArgs : CtcRows {
 bool ctc_score_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
 void launch_ctc_score(ScoreArgs a, hipStream_t s);
 
+// CTC scoring of every one-edit variant of a transcript (amx_ctc_variants.hip), rows n over one [N, T, C] tensor (no `descs`):
+// contract in include/allophant_amx_variants.h.  A lattice launch of one workgroup per row stores a[t][i] (`forward`) and
+// b[t][i] (`backward`, which the launcher places behind it), strips * 64 values per row and frame; a variants launch of one
+// wave per (row, slot, 64 classes) follows, VARIANTS_GRID_ROWS rows at a time from `row_base`.  The limits are the
+// alignment's, and C <= 65535.
+constexpr int VARIANTS_GRID_ROWS = 65535;
+struct VariantsArgs : CtcRows {
+    float *forward, *backward;
+    float *log_likelihood, *substitutions, *insertions;
+    int32_t* status;
+    int64_t row_base;
+};
+// false when the size is not representable in size_t
+bool ctc_variants_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
+void launch_ctc_variants(VariantsArgs a, hipStream_t s);
+
 // CTC search (amx_ctc_search.hip), one wave per (utterance, query) row n * Q + q over one [N, T, C] tensor read with element
 // strides (stride_n, stride_t, 1): contract in include/allophant_amx_search.h.  `frame_max` is the workspace, the per-frame
 // maxima [N, T] that a pre-pass writes.  Limits (checked by the caller): 2 <= C, 1 <= max_query <= 256, N * Q * T < 2^31.

@@ -32,9 +32,11 @@ from . import lib as _lib
 from . import scoring as _scoring
 from . import search as _search
 from . import spec as _spec
+from . import variants as _variants
 from .alignment import Aligned, Alignment, ctc_forced_align, label_targets, segments  # noqa: F401  (the façade's names)
 from .scoring import Rescored, Score, Scored, ctc_score  # noqa: F401  (the façade's scoring names)
 from .search import Found, Hit, ctc_search, pick_hits, query_targets  # noqa: F401  (the façade's search names)
+from .variants import Alternatives, Variants, ctc_variants  # noqa: F401  (the façade's variant names)
 
 
 @dataclass
@@ -933,6 +935,26 @@ class Estimator:
         """``search_device`` fetched to the host: per utterance and query the best ``Hit`` (``None`` where the query does not
         occur)."""
         return self.search_device(predictions, queries, output).best()
+
+    def variants_device(self, predictions: Predictions, targets, output: str) -> "_variants.Variants":
+        """On-device CTC scoring of every one-edit variant (``amx_ctc_variants_emissions``) of each utterance's transcript on
+        ``predictions.outputs[output]``: each symbol substituted by each class or deleted, and each class inserted into each
+        gap.  ``targets`` are as for ``score_device``, restricted to this output: its rows (class indices under the
+        predictions' own inventory, e.g. from ``label_targets``), or a dict that holds them under ``output``.  The output's
+        ``[T, N, C]`` tensor is read in place through its transposed view; the result stays in HBM."""
+        if output not in predictions.outputs:
+            raise ValueError(f"unknown output {output!r}, the predictions hold {list(predictions.outputs.keys())}")
+        if isinstance(targets, dict):
+            if list(targets) != [output]:
+                raise ValueError(f"variants take the targets of the one output {output!r}, got {list(targets)}")
+            targets = targets[output]
+        return _variants.ctc_variants(predictions.outputs[output].transpose(0, 1), predictions.lengths, targets, 0)
+
+    def variants(self, predictions: Predictions, targets, output: str, threshold: float = 0.0
+                 ) -> List[Optional[List["_variants.Finding"]]]:
+        """``variants_device`` fetched to the host: per utterance the single edits that beat the transcript by more than
+        ``threshold`` nats (``Variants.diagnose``), ``None`` for an utterance of no frames whose transcript is not empty."""
+        return self.variants_device(predictions, targets, output).diagnose(threshold)
 
     def debug_fetch(self, what: str, index: int = 0) -> Tensor:
         """Test hook: intermediates of the last ``predict(..., _keep_hidden=True)`` as CPU fp32 tensors.  Without the flag a pass

@@ -71,6 +71,10 @@ ALIGN_LONG_TILE_STATES = 832  # AMX_ALIGN_LONG_TILE_STATES
 # the CTC forward-backward scoring entry points (include/allophant_amx_score.h; added to ABI 6, detected by name)
 SCORE_EXPORTS = ["amx_ctc_score_workspace", "amx_ctc_score_emissions", "amx_ctc_score"]
 SCORE_MAX_TARGET = 4095  # AMX_SCORE_MAX_TARGET
+# the CTC one-edit-variant entry points (include/allophant_amx_variants.h; added to ABI 7, detected by name)
+VARIANTS_EXPORTS = ["amx_ctc_variants_workspace", "amx_ctc_variants_emissions"]
+VARIANTS_MAX_TARGET = 4095  # AMX_VARIANTS_MAX_TARGET
+VARIANTS_MAX_CLASSES = 65535  # AMX_VARIANTS_MAX_CLASSES
 # the CTC search entry points (include/allophant_amx_search.h; added to ABI 6, detected by name)
 SEARCH_EXPORTS = ["amx_ctc_search_workspace", "amx_ctc_search_emissions"]
 SEARCH_MAX_QUERY = 256  # AMX_SEARCH_MAX_QUERY
@@ -245,6 +249,12 @@ def load() -> C.CDLL:
         lib.amx_ctc_score_emissions.restype = i32
         lib.amx_ctc_score.argtypes = [vp, vp, C.POINTER(i64), i32, i64, i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
         lib.amx_ctc_score.restype = i32
+    if hasattr(lib, "amx_ctc_variants_emissions"):  # (added to ABI 7 by name: absent from older builds)
+        lib.amx_ctc_variants_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_ctc_variants_workspace.restype = i32
+        lib.amx_ctc_variants_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, vp, vp, i64, vp, C.c_size_t, vp, vp, vp,
+                                                   vp, vp]
+        lib.amx_ctc_variants_emissions.restype = i32
     if hasattr(lib, "amx_ctc_search_emissions"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_ctc_search_workspace.argtypes = [i64, i64, i64, i64, C.POINTER(C.c_size_t)]
         lib.amx_ctc_search_workspace.restype = i32
