@@ -12,7 +12,7 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
            "levensthein_matrix", "levensthein_confusions_batch", "ConfusionCounts", "ConfusionTable", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "segments", "Score", "Scored",
            "Rescored", "ctc_score", "Found", "Hit", "ctc_search", "pick_hits", "query_targets", "LongPlan", "plan_windows",
-           "gather_windows", "stitch_windows", "Variants", "Alternatives", "ctc_variants"]
+           "gather_windows", "stitch_windows", "Variants", "Alternatives", "ctc_variants", "PhonotacticLM"]
 __version__ = "0.1.0"
 
 
@@ -50,4 +50,8 @@ def __getattr__(name):
         from . import variants
 
         return getattr(variants, name)
+    if name == "PhonotacticLM":
+        from . import phonotactics
+
+        return phonotactics.PhonotacticLM
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

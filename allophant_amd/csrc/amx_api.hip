@@ -3,6 +3,7 @@
 #include "../../include/allophant_amx.h"
 #include "../../include/allophant_amx_allophones.h"
 #include "../../include/allophant_amx_beam.h"
+#include "../../include/allophant_amx_beam_lm.h"
 #include "../../include/allophant_amx_align.h"
 #include "../../include/allophant_amx_score.h"
 #include "../../include/allophant_amx_search.h"
@@ -2420,6 +2421,38 @@ extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_
     launch_beam_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, beam_width, n_best,
                               (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores,
                               hyp_counts, (hipStream_t)stream);
+    return ctc_launched(nullptr, "beam-search");
+}
+
+extern "C" int amx_beam_ctc_lm_workspace(int beam_width, int64_t rows, int64_t T, size_t* bytes) {
+    return amx_beam_ctc_workspace(beam_width, rows, T, bytes);
+}
+
+extern "C" int amx_beam_ctc_lm_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                         const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index, int beam_width,
+                                         int n_best, uint32_t flags, const float* lm, int n_lm, const int32_t* lm_index,
+                                         double lm_weight, double token_score, void* workspace, size_t workspace_bytes,
+                                         int64_t* tokens, int64_t* timesteps, int32_t* counts, double* scores, int32_t* hyp_counts,
+                                         void* stream) {
+    if (int rc = beam_check(nullptr, beam_width, n_best, flags)) return rc;
+    if (C < 2 || C > AMX_BEAM_LM_MAX_CLASSES)
+        return fail(nullptr, AMX_EINVAL, "beam search with a language model needs 2 to " + std::to_string(AMX_BEAM_LM_MAX_CLASSES) +
+                                             " classes, got " + std::to_string(C));
+    if (blank_index < 0 || blank_index >= C) return fail(nullptr, AMX_EINVAL, "blank_index out of range");
+    if (n_lm < 1) return fail(nullptr, AMX_EINVAL, "n_lm must be at least 1, got " + std::to_string(n_lm));
+    if (!std::isfinite(lm_weight) || !std::isfinite(token_score)) return fail(nullptr, AMX_EINVAL, "lm_weight and token_score must be finite");
+    if (N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative emission geometry");
+    if (T > INT32_MAX) return fail(nullptr, AMX_EINVAL, "too many frames");
+    if (N == 0) return AMX_OK;
+    if (!emissions || !frame_lengths || !lm || !lm_index || !tokens || !timesteps || !counts || !scores || !hyp_counts)
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    size_t need = 0;
+    amx_beam_ctc_workspace(beam_width, N, T, &need);
+    if (int rc = check_workspace(nullptr, "beam-search", need, workspace, workspace_bytes)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+    launch_beam_ctc_lm_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, beam_width, n_best,
+                                 (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, lm, n_lm, lm_index, lm_weight, token_score,
+                                 (uint32_t*)workspace, tokens, timesteps, counts, scores, hyp_counts, (hipStream_t)stream);
     return ctc_launched(nullptr, "beam-search");
 }
 

@@ -572,6 +572,13 @@ void launch_beam_ctc(const OutDesc* descs_dev, int n_out, const float* out, cons
 void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
                                int blank, int beam, int n_best, int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps,
                                int* counts, double* scores, int* hyp_counts, hipStream_t s);
+// The same search with shallow fusion of a bigram table (amx_ctc_beam_lm.hip): lm fp32 [n_lm, C + 1, C + 1], lm_index int32
+// [N] on the device (-1: the row runs without a table).  Limits as above, and C <= BEAM_LM_MAX_CLASSES.
+constexpr int BEAM_LM_MAX_CLASSES = 4095;
+void launch_beam_ctc_lm_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
+                                  int blank, int beam, int n_best, int exp_mode, const float* lm, int n_lm, const int* lm_index,
+                                  double lm_weight, double token_score, uint32_t* ws, int64_t* tokens, int64_t* timesteps, int* counts,
+                                  double* scores, int* hyp_counts, hipStream_t s);
 
 // The call frame that CTC forced alignment and forward-backward scoring share (device half in amx_ctc_row.inc): where the
 // emissions lie and which target rows are run over them.  With `descs` the emissions are every output block of the output

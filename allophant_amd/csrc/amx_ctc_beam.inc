@@ -1,0 +1,242 @@
+// What the two CTC beam-search kernels share (amx_ctc_beam.hip, the decoder without a language model, and
+// amx_ctc_beam_lm.hip, the one with a phonotactic bigram): prefix hashes, the order-preserving key images, the merge of a
+// group's members, the workgroup scan, the exact radix select with its compaction, and the end step's trace and collapse.
+// Included inside namespace amx { namespace { ... } } by each of them.  The templates take the including file's
+// shared-memory struct `Smem`, of which they use: int hist[256], int wtmp[BM_WAVES], uint64_t sel_prefix, sel_mask,
+// int sel_take, sel_done, int win[], int carry[2].
+
+constexpr int BM_THREADS = 256;
+constexpr int BM_WAVES = BM_THREADS / 64;
+constexpr double BM_THRESHOLD = 50.0;                   // torchaudio's beam_threshold default
+constexpr uint64_t BM_ROOT = 0x6a09e667f3bcc908ull;     // hash of the empty prefix
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint64_t extend_hash(uint64_t h, int n) { return splitmix64(h ^ ((uint64_t)(unsigned)n * 0xd6e8feb86659fd93ull)); }
+
+// order-preserving integer images (larger float -> larger key); candidate keys are kept >= 1 so that 0 means "none"
+__device__ __forceinline__ uint32_t key32(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint64_t key64(double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint64_t k = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+    return k ? k : 1;
+}
+__device__ __forceinline__ double unkey64(uint64_t k) {
+    const uint64_t sign = 0x8000000000000000ull;
+    return __longlong_as_double((long long)((k & sign) ? (k ^ sign) : ~k));
+}
+
+// the emission as flashlight adds it: the fp32 value, or (EXP) its fp32 exponential -- exp in fp64 rounded once to fp32, so
+// the value is the correctly rounded expf (up to a double-rounding tie)
+__device__ __forceinline__ double emission(float x, bool exp_mode) { return exp_mode ? (double)(float)exp((double)x) : (double)x; }
+
+// the members of one merge group (at most three): scores and state slots, in the order they were found
+struct Members {
+    double x0, x1, x2;
+    int s0, s1, s2, m;
+    __device__ __forceinline__ void push(double v, int slot) {
+        if (m == 0) { x0 = v; s0 = slot; }
+        else if (m == 1) { x1 = v; s1 = slot; }
+        else { x2 = v; s2 = slot; }
+        ++m;
+    }
+};
+
+__device__ __forceinline__ double logadd(double a, double c) {
+    const double hi = fmax(a, c), lo = fmin(a, c);
+    return hi + log1p(exp(lo - hi));
+}
+
+// log-add of the members folded in descending order; *best = the slot of the highest member (the first of equal ones)
+__device__ __forceinline__ double fold(Members g, int* best) {
+    double a = g.x0, b = g.x1, c = g.x2;
+    int sa = g.s0, sb = g.s1, sc = g.s2;
+    if (g.m > 1 && b > a) { double t = a; a = b; b = t; int u = sa; sa = sb; sb = u; }
+    if (g.m > 2) {
+        if (c > b) { double t = b; b = c; c = t; int u = sb; sb = sc; sc = u; }
+        if (b > a) { double t = a; a = b; b = t; int u = sa; sa = sb; sb = u; }
+    }
+    double acc = a;
+#pragma nounroll
+    for (int r = 1; r < g.m; ++r) acc = logadd(acc, r == 1 ? b : c);
+    *best = sa;
+    return acc;
+}
+
+// exclusive prefix sum over the workgroup in thread order
+__device__ __forceinline__ int block_scan(int v, int* wtmp, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wtmp[w] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < BM_WAVES; ++i) {
+        const int c = wtmp[i];
+        base += i < w ? c : 0;
+        tot += c;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + x - v;
+}
+
+// Radix select (8-bit digits from the top) of the `want` largest of n integer keys, want <= n.  Leaves in sm.sel_* the
+// boundary region: keys with (key & mask) > prefix are in, of those with (key & mask) == prefix the first `take` in index
+// order.  Expects sm.hist zero and leaves it zero.
+template <typename K, int BITS, typename KeyF, typename Smem>
+__device__ __forceinline__ void radix_select(int n, int want, KeyF key, Smem& sm) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        sm.sel_prefix = 0;
+        sm.sel_mask = 0;
+        sm.sel_take = want;
+        sm.sel_done = 0;
+    }
+    __syncthreads();
+    for (int shift = BITS - 8; shift >= 0; shift -= 8) {
+        const K prefix = (K)sm.sel_prefix, mask = (K)sm.sel_mask;
+        for (int i = tid; i < n; i += BM_THREADS) {
+            const K k = key(i);
+            if ((k & mask) == prefix) atomicAdd(&sm.hist[(int)(k >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (tid < 64) {
+            // lane l owns bins 255 - 4l .. 252 - 4l: an inclusive scan over lanes counts keys from the top
+            int c[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                c[j] = sm.hist[255 - 4 * tid - j];
+                sm.hist[255 - 4 * tid - j] = 0;
+            }
+            const int sum = c[0] + c[1] + c[2] + c[3];
+            int incl = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int y = __shfl_up(incl, o, 64);
+                if (tid >= o) incl += y;
+            }
+            const int take = sm.sel_take;
+            int cum = incl - sum;
+            if (cum < take && take <= incl) {
+                bool found = false;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!found && cum + c[j] >= take) {
+                        found = true;
+                        sm.sel_prefix |= (uint64_t)(255 - 4 * tid - j) << shift;
+                        sm.sel_mask |= (uint64_t)0xff << shift;
+                        sm.sel_take = take - cum;
+                        sm.sel_done = c[j] == take - cum;  // the region is taken whole: lower digits cannot change the set
+                    }
+                    if (!found) cum += c[j];
+                }
+            }
+        }
+        __syncthreads();
+        if (sm.sel_done) break;
+    }
+}
+
+// Emits the selected keys in index order: emit(position, index), positions < cap.  Each thread owns a contiguous range.
+template <typename K, typename KeyF, typename EmitF, typename Smem>
+__device__ __forceinline__ void compact(int n, int cap, KeyF key, EmitF emit, Smem& sm) {
+    const K prefix = (K)sm.sel_prefix, mask = (K)sm.sel_mask;
+    const int take = sm.sel_take;
+    const int per = (n + BM_THREADS - 1) / BM_THREADS;
+    const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
+    int gt = 0, eq = 0;
+    for (int i = lo; i < hi; ++i) {
+        const K k = key(i) & mask;
+        gt += k > prefix;
+        eq += k == prefix;
+    }
+    int total;
+    const int ex = block_scan((gt << 16) | eq, sm.wtmp, &total);
+    int gb = ex >> 16, eb = ex & 0xffff;
+    for (int i = lo; i < hi; ++i) {
+        const K k = key(i) & mask;
+        int pos = -1;
+        if (k > prefix) {
+            pos = gb + min(eb, take);
+            ++gb;
+        } else if (k == prefix) {
+            if (eb < take) pos = gb + eb;
+            ++eb;
+        }
+        if (pos >= 0 && pos < cap) emit(pos, i);
+    }
+}
+
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// The end step's last part, for the nh ranked hypotheses whose final slots are in sm.win: traces the backpointers
+// (parent slot << 16 | frame token per (frame, slot)) back into timesteps[r, t], then collapses them in place into tokens
+// and 1-based timesteps.
+template <typename Smem>
+__device__ __forceinline__ void trace_and_collapse(int nh, int len, int T, int beam, int blank, const uint32_t* __restrict__ bp,
+                                                   int64_t* __restrict__ tokens, int64_t* __restrict__ timesteps,
+                                                   int* __restrict__ counts, Smem& sm) {
+    const int tid = threadIdx.x;
+    // trace back: the frame tokens of hypothesis r go to timesteps[r, t] first
+    if (tid < nh) {
+        int slot = sm.win[tid];
+        int64_t* raw = timesteps + (int64_t)tid * T;
+        for (int t = len - 1; t >= 0; --t) {
+            const uint32_t v = bp[(int64_t)t * beam + slot];
+            raw[t] = (int64_t)(v & 0xffffu);
+            slot = (int)(v >> 16);
+        }
+    }
+    __syncthreads();
+    // collapse in place, 4 frames per thread per chunk: non-blank tokens that differ from the previous frame's token
+    constexpr int IT = 4, CH = BM_THREADS * IT;
+    for (int r = 0; r < nh; ++r) {
+        int64_t* tok = tokens + (int64_t)r * T;
+        int64_t* ts = timesteps + (int64_t)r * T;
+        int pos_base = 0;
+        for (int c0 = 0, ci = 0; c0 < len; c0 += CH, ++ci) {
+            const int t0 = c0 + tid * IT;
+            int v[IT], prev;
+            prev = tid == 0 ? (c0 == 0 ? blank : sm.carry[(ci - 1) & 1]) : (t0 - 1 < len ? (int)ts[t0 - 1] : blank);
+#pragma unroll
+            for (int j = 0; j < IT; ++j) v[j] = t0 + j < len ? (int)ts[t0 + j] : blank;
+            if (tid == BM_THREADS - 1 && t0 + IT <= len) sm.carry[ci & 1] = v[IT - 1];  // the next chunk's first `prev`
+            int cnt = 0;
+            bool emit[IT];
+#pragma unroll
+            for (int j = 0; j < IT; ++j) {
+                emit[j] = t0 + j < len && v[j] != blank && v[j] != (j ? v[j - 1] : prev);
+                cnt += emit[j];
+            }
+            int total;
+            int pos = pos_base + block_scan(cnt, sm.wtmp, &total);
+#pragma unroll
+            for (int j = 0; j < IT; ++j)
+                if (emit[j]) {
+                    tok[pos] = v[j];
+                    ts[pos] = t0 + j + 1;
+                    ++pos;
+                }
+            pos_base += total;
+        }
+        if (tid == 0) counts[r] = pos_base;
+        __syncthreads();
+    }
+}

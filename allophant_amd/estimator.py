@@ -29,6 +29,7 @@ from torch import Tensor
 from . import alignment as _alignment
 from . import ctc as _ctc
 from . import lib as _lib
+from . import phonotactics as _phonotactics
 from . import scoring as _scoring
 from . import search as _search
 from . import spec as _spec
@@ -36,6 +37,7 @@ from . import variants as _variants
 from .alignment import Aligned, Alignment, ctc_forced_align, label_targets, segments  # noqa: F401  (the façade's names)
 from .scoring import Rescored, Score, Scored, ctc_score  # noqa: F401  (the façade's scoring names)
 from .search import Found, Hit, ctc_search, pick_hits, query_targets  # noqa: F401  (the façade's search names)
+from .phonotactics import PhonotacticLM  # noqa: F401  (the façade's language-model name)
 from .variants import Alternatives, Variants, ctc_variants  # noqa: F401  (the façade's variant names)
 
 
@@ -769,12 +771,25 @@ class Estimator:
         return self.greedy_decode_device(predictions).hypotheses()
 
     def beam_decode_device(self, predictions: Predictions, beam_width: int, n_best: int = 1,
-                           exp_emissions: bool = True) -> "BeamDecoded":
+                           exp_emissions: bool = True, *, lm=None, lm_weight: float = 1.0, token_score: float = 0.0,
+                           lm_ids=None) -> "BeamDecoded":
         """On-device ``BeamCTCDecoder`` (reference predictions.py:210-235) over every output of ``predictions``, as the
         reference's decode loop applies it per classifier (run.py:767-785).  ``exp_emissions`` (default, like upstream's
-        ``log_emissions.exp()``) adds probabilities; False adds the log-probabilities as given.  The result stays in HBM."""
+        ``log_emissions.exp()``) adds probabilities; False adds the log-probabilities as given.  The result stays in HBM.
+
+        ``lm`` (a ``PhonotacticLM``, or a sequence of them with one ``lm_ids`` index per utterance, -1 for none) fuses a
+        phonotactic bigram into the search of the phoneme / phone outputs whose class count is the model's
+        (``amx_beam_ctc_lm_emissions``: every new token adds ``lm_weight * lm[previous, token] + token_score``, the end
+        ``lm_weight * lm[last, end]``); their rows replace those of the plain decode, every other output is unchanged.  For
+        ``predict_languages`` predictions ``lm`` speaks union classes and each language's rows run under
+        ``lm.restrict(columns)``.  Fusion is meant for ``exp_emissions=False``: with upstream's sums of probabilities a
+        log-probability term is on another scale."""
         names, N, L, T, O, _, lengths_pointer, stream = self._predictions_call(predictions)
         _check_beam(beam_width, n_best)
+        fusion = None
+        if lm is not None:
+            _phonotactics.check_scalars(lm_weight, token_score)
+            fusion = (*_phonotactics.lm_call(lm, lm_ids, N), float(lm_weight), float(token_score))
         with torch.cuda.device(self._device):
             size = C.c_size_t()
             _lib.check(self._lib, None, self._lib.amx_beam_ctc_workspace(beam_width, O * N, T, C.byref(size)))
@@ -792,18 +807,53 @@ class Estimator:
             _lib.check(self._lib, self._handle, code)
         decoded = BeamDecoded(names, tokens, timesteps, counts, scores, hyp_counts)
         if predictions._languages is not None:
-            decoded = self._beam_decode_languages(predictions, decoded, beam_width, n_best, exp_emissions)
+            decoded = self._beam_decode_languages(predictions, decoded, beam_width, n_best, exp_emissions, fusion)
+        elif fusion is not None:
+            decoded = self._beam_decode_fused(predictions, decoded, beam_width, n_best, exp_emissions, fusion)
+        return decoded
+
+    @staticmethod
+    def _fused_outputs(predictions: Predictions, names: List[str], classes: int) -> List[int]:
+        """The outputs a language model of ``classes`` classes is fused into: phoneme / phone blocks of that class count."""
+        found = [o for o, name in enumerate(names)
+                 if name in (_spec.PHONEME, _spec.PHONE) and predictions.outputs[name].shape[2] == classes]
+        if not found:
+            raise ValueError(f"no phoneme or phone output has the language model's {classes} classes")
+        return found
+
+    def _beam_decode_fused(self, predictions: Predictions, decoded: "BeamDecoded", beam_width: int, n_best: int,
+                           exp_emissions: bool, fusion) -> "BeamDecoded":
+        """The rest of ``beam_decode_device`` under a language model: the phoneme / phone rows decoded again through
+        ``amx_beam_ctc_lm_emissions``, which reads the output's block in place through its strides."""
+        lms, lm_ids, lm_weight, token_score = fusion
+        if any(m.blank != 0 for m in lms):
+            raise ValueError("the outputs' blank is class 0: the language model's must be too")
+        with torch.cuda.device(self._device):
+            stack = _phonotactics.PhonotacticLM.stack(lms).to(self._device)
+            for o in self._fused_outputs(predictions, decoded.names, lms[0].classes):
+                block = predictions.outputs[decoded.names[o]]  # [T, N, C]
+                rows = _beam_ctc_rows(block.transpose(0, 1), predictions.lengths, beam_width, n_best, 0, exp_emissions,
+                                      (stack, lm_ids, lm_weight, token_score))
+                for whole, piece in zip(decoded[1:], rows):
+                    whole[o] = piece
         return decoded
 
     def _beam_decode_languages(self, predictions: Predictions, decoded: "BeamDecoded", beam_width: int, n_best: int,
-                               exp_emissions: bool) -> "BeamDecoded":
+                               exp_emissions: bool, fusion=None) -> "BeamDecoded":
         """The rest of ``beam_decode_device`` for ``predict_languages`` predictions.  Upstream hands the decoder probabilities as
         scores, so a class of probability 0 is still a candidate, while upstream's per-language decoder does not have the
         class at all: the composed outputs are decoded again per language, over the language's utterances and its own columns
         of the restricted block (the emissions path), the tokens mapped back to union ids, and the rows of ``decoded``
-        replaced."""
+        replaced.  With ``fusion`` (language models over the union classes) each language's rows run under the models
+        restricted to its columns."""
         ids, inventories = predictions._languages
         ids_host = ids.cpu().tolist()
+        fused = None
+        if fusion is not None:
+            lms, lm_ids, lm_weight, token_score = fusion
+            if any(m.blank != 0 for m in lms):
+                raise ValueError("the outputs' blank is class 0: the language model's must be too")
+            fused = self._fused_outputs(predictions, decoded.names, lms[0].classes)
         with torch.cuda.device(self._device):
             lengths = predictions.lengths.to(self._device)
             for o, name in enumerate(decoded.names):
@@ -814,19 +864,25 @@ class Estimator:
                     columns = inventories.columns(language).to(self._device)
                     if columns.numel() < 2:
                         raise ValueError(f"beam search needs a phoneme in the inventory of {inventories.languages[language]!r}")
-                    own = torch.tensor([n for n, l in enumerate(ids_host) if l == language], dtype=torch.int64, device=self._device)
+                    rows_of = [n for n, l in enumerate(ids_host) if l == language]
+                    own = torch.tensor(rows_of, dtype=torch.int64, device=self._device)
                     compact = block.index_select(1, own).index_select(2, columns).transpose(0, 1).contiguous()
-                    tokens, *rest = _beam_ctc_rows(compact, lengths[own], beam_width, n_best, 0, exp_emissions)
+                    table = None
+                    if fused is not None and o in fused:
+                        stack = _phonotactics.PhonotacticLM.stack([m.restrict(columns) for m in lms]).to(self._device)
+                        table = (stack, lm_ids[rows_of], lm_weight, token_score)
+                    tokens, *rest = _beam_ctc_rows(compact, lengths[own], beam_width, n_best, 0, exp_emissions, table)
                     # per-language ids -> union ids (the entries past `counts` are not tokens: clamped into the table)
                     decoded.tokens[o, own] = columns[tokens.clamp_(0, columns.numel() - 1)]
                     for whole, piece in zip(decoded[2:], rest):
                         whole[o, own] = piece
         return decoded
 
-    def beam_decode(self, predictions: Predictions, beam_width: int, n_best: int = 1,
-                    exp_emissions: bool = True) -> Dict[str, List[List[CTCHypothesis]]]:
+    def beam_decode(self, predictions: Predictions, beam_width: int, n_best: int = 1, exp_emissions: bool = True, *, lm=None,
+                    lm_weight: float = 1.0, token_score: float = 0.0, lm_ids=None) -> Dict[str, List[List[CTCHypothesis]]]:
         """``beam_decode_device`` fetched to the host: per output and utterance up to ``n_best`` hypotheses, best first."""
-        return self.beam_decode_device(predictions, beam_width, n_best, exp_emissions).hypotheses()
+        return self.beam_decode_device(predictions, beam_width, n_best, exp_emissions, lm=lm, lm_weight=lm_weight,
+                                       token_score=token_score, lm_ids=lm_ids).hypotheses()
 
     def align_device(self, predictions: Predictions, targets: Dict[str, Sequence[Sequence[int]]],
                      long: Optional[bool] = None) -> "_alignment.Aligned":
@@ -1136,9 +1192,13 @@ class BeamCTCDecoder:
     Upstream this is torchaudio's flashlight ``ctc_decoder`` (lexicon-free, no LM, blank = silence, log_add) called on
     ``log_emissions.exp()``; here ``amx_beam_ctc_emissions`` reads the fp32 ``[N, T, C]`` tensor in place (any strides with a
     unit class stride) and exponentiates each value as it is read.  Returns, per utterance, up to ``n_best``
-    ``CTCHypothesis(tokens, [], score, timesteps)``, best first.  There is no CPU path."""
+    ``CTCHypothesis(tokens, [], score, timesteps)``, best first.  There is no CPU path.
 
-    def __init__(self, tokens: List[str], beam_width: int, n_best: int = 1, blank_index: int = 0) -> None:
+    ``lm`` (keyword-only, a ``PhonotacticLM`` over the decoder's tokens) fuses a phonotactic bigram into the search, see
+    ``beam_ctc_decode``; upstream's decoder has no such argument."""
+
+    def __init__(self, tokens: List[str], beam_width: int, n_best: int = 1, blank_index: int = 0, *, lm=None,
+                 lm_weight: float = 1.0, token_score: float = 0.0) -> None:
         _check_beam(beam_width, n_best)
         self._tokens = list(tokens)
         if not 0 <= blank_index < len(self._tokens):
@@ -1146,35 +1206,61 @@ class BeamCTCDecoder:
         self._beam_width = int(beam_width)
         self._n_best = int(n_best)
         self._blank_index = int(blank_index)
+        if lm is not None:
+            _phonotactics.check_scalars(lm_weight, token_score)
+            if not isinstance(lm, PhonotacticLM) or lm.classes != len(self._tokens) or lm.blank != self._blank_index:
+                raise ValueError(f"lm must be a PhonotacticLM over the decoder's {len(self._tokens)} tokens and its blank")
+        self._lm, self._lm_weight, self._token_score = lm, float(lm_weight), float(token_score)
 
     def __call__(self, log_emissions: Tensor, lengths: Optional[Tensor] = None) -> List[List[CTCHypothesis]]:
         if log_emissions.dim() == 3 and log_emissions.shape[2] != len(self._tokens):
             raise ValueError(f"emissions have {log_emissions.shape[2]} classes, the decoder {len(self._tokens)} tokens")
-        return beam_ctc_decode(log_emissions, lengths, self._beam_width, self._n_best, self._blank_index)
+        return beam_ctc_decode(log_emissions, lengths, self._beam_width, self._n_best, self._blank_index, lm=self._lm,
+                               lm_weight=self._lm_weight, token_score=self._token_score)
 
 
 def beam_ctc_decode(log_emissions: Tensor, lengths: Optional[Tensor], beam_width: int, n_best: int = 1, blank_index: int = 0,
-                    exp_emissions: bool = True) -> List[List[CTCHypothesis]]:
+                    exp_emissions: bool = True, *, lm=None, lm_weight: float = 1.0, token_score: float = 0.0,
+                    lm_ids=None) -> List[List[CTCHypothesis]]:
     """``BeamCTCDecoder.__call__`` (reference predictions.py:231-233) through ``amx_beam_ctc_emissions``; ``exp_emissions``
-    False adds the values as given instead of their exponentials."""
+    False adds the values as given instead of their exponentials.
+
+    With ``lm`` (a ``PhonotacticLM`` over the emissions' classes, or a sequence of them with one ``lm_ids`` index per
+    utterance, -1 for none) the search runs through ``amx_beam_ctc_lm_emissions``: a new token ``n`` after the prefix ``P``
+    adds ``lm_weight * lm[last(P), n] + token_score``, the end ``lm_weight * lm[last(P), end]``, and the scores are the
+    fused totals.  Meant for ``exp_emissions=False``."""
     log_emissions, N, _, Cn = _ctc.emissions(log_emissions, "decodes")
     _check_beam(beam_width, n_best)
+    fusion = None
+    if lm is not None:
+        _phonotactics.check_scalars(lm_weight, token_score)
+        lms, ids = _phonotactics.lm_call(lm, lm_ids, N)
+        if any(m.classes != Cn or m.blank != blank_index for m in lms):
+            raise ValueError(f"the language model must have the emissions' {Cn} classes and blank {blank_index}")
+        if Cn > _lib.BEAM_LM_MAX_CLASSES:
+            raise ValueError(f"beam search with a language model takes at most {_lib.BEAM_LM_MAX_CLASSES} classes")
     _lib.load()
     _ctc.check_classes(Cn, blank_index)
     if N == 0:
         return []
-    return _beam_hypotheses(*_beam_ctc_rows(log_emissions, lengths, beam_width, n_best, blank_index, exp_emissions))
+    if lm is not None:
+        fusion = (PhonotacticLM.stack(lms).to(log_emissions.device), ids, float(lm_weight), float(token_score))
+    return _beam_hypotheses(*_beam_ctc_rows(log_emissions, lengths, beam_width, n_best, blank_index, exp_emissions, fusion))
 
 
 def _beam_ctc_rows(log_emissions: Tensor, lengths: Optional[Tensor], beam_width: int, n_best: int, blank_index: int,
-                   exp_emissions: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+                   exp_emissions: bool, fusion=None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """``amx_beam_ctc_emissions`` over ``[N, T, C]`` emissions, ``N >= 1``: the device tensors ``tokens`` / ``timesteps``
-    ``[N, n_best, T]``, ``counts`` / ``scores`` ``[N, n_best]`` and ``hyp_counts`` ``[N]``."""
+    ``[N, n_best, T]``, ``counts`` / ``scores`` ``[N, n_best]`` and ``hyp_counts`` ``[N]``.  With ``fusion`` (the device stack
+    ``[n_lm, C + 1, C + 1]``, the int32 host ``lm_ids`` ``[N]``, ``lm_weight``, ``token_score``) through
+    ``amx_beam_ctc_lm_emissions``."""
     log_emissions, N, T, Cn = _ctc.emissions(log_emissions, "decodes")
     _check_beam(beam_width, n_best)
     lib = _lib.load()
     device = log_emissions.device
     _ctc.check_classes(Cn, blank_index)
+    if fusion is not None and not hasattr(lib, "amx_beam_ctc_lm_emissions"):
+        raise RuntimeError(f"{_lib.LIB_PATH} predates beam search with a language model (amx_beam_ctc_lm_emissions): rebuild it")
     with torch.cuda.device(device):
         frame_lengths, index, stream = _ctc.frame(log_emissions, lengths)
         size = C.c_size_t()
@@ -1185,12 +1271,23 @@ def _beam_ctc_rows(log_emissions: Tensor, lengths: Optional[Tensor], beam_width:
         counts = torch.empty(N, n_best, dtype=torch.int32, device=device)
         scores = torch.empty(N, n_best, dtype=torch.float64, device=device)
         hyp_counts = torch.empty(N, dtype=torch.int32, device=device)
-        code = lib.amx_beam_ctc_emissions(
-            index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
-            C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, beam_width, n_best,
-            _lib.BEAM_EXP_EMISSIONS if exp_emissions else 0, C.c_void_p(workspace.data_ptr()), size.value,
-            C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()), C.c_void_p(counts.data_ptr()),
-            C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
+        head = (index, C.c_void_p(log_emissions.data_ptr()), log_emissions.stride(0), log_emissions.stride(1),
+                C.c_void_p(frame_lengths.data_ptr()), N, T, Cn, blank_index, beam_width, n_best,
+                _lib.BEAM_EXP_EMISSIONS if exp_emissions else 0)
+        tail = (C.c_void_p(workspace.data_ptr()), size.value, C.c_void_p(tokens.data_ptr()), C.c_void_p(timesteps.data_ptr()),
+                C.c_void_p(counts.data_ptr()), C.c_void_p(scores.data_ptr()), C.c_void_p(hyp_counts.data_ptr()), C.c_void_p(stream))
+        if fusion is None:
+            code = lib.amx_beam_ctc_emissions(*head, *tail)
+        else:
+            stack, lm_ids, lm_weight, token_score = fusion
+            if stack.dim() != 3 or tuple(stack.shape[1:]) != (Cn + 1, Cn + 1) or stack.dtype != torch.float32:
+                raise ValueError(f"the language-model stack must be fp32 [n_lm, {Cn + 1}, {Cn + 1}]")
+            stack = stack.to(device).contiguous()
+            ids = lm_ids.to(device=device, dtype=torch.int32).contiguous()
+            code = lib.amx_beam_ctc_lm_emissions(*head, C.c_void_p(stack.data_ptr()), stack.shape[0], C.c_void_p(ids.data_ptr()),
+                                                 lm_weight, token_score, *tail)
+            current = torch.cuda.current_stream(device)
+            stack.record_stream(current), ids.record_stream(current)
         _lib.check(lib, None, code)
         return tokens, timesteps, counts, scores, hyp_counts
 

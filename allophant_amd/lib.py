@@ -45,6 +45,9 @@ ALLOPHONE_EXPORTS = ["amx_set_allophones", "amx_map_allophones"]
 BEAM_EXPORTS = ["amx_beam_ctc_workspace", "amx_beam_ctc", "amx_beam_ctc_emissions"]
 BEAM_EXP_EMISSIONS = 1  # AMX_BEAM_EXP_EMISSIONS
 BEAM_MAX_WIDTH = 64
+# the same search with a phonotactic language model (include/allophant_amx_beam_lm.h; added to ABI 7, detected by name)
+BEAM_LM_EXPORTS = ["amx_beam_ctc_lm_workspace", "amx_beam_ctc_lm_emissions"]
+BEAM_LM_MAX_CLASSES = 4095  # AMX_BEAM_LM_MAX_CLASSES
 # the sinc-resampling entry points (include/allophant_amx_resample.h; added to ABI 6, detected by name)
 RESAMPLE_EXPORTS = ["amx_resample_bank", "amx_resample"]
 RESAMPLE_MAX_PHASES = 4096  # AMX_RESAMPLE_MAX_PHASES
@@ -185,6 +188,12 @@ def load() -> C.CDLL:
         lib.amx_beam_ctc_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, i32, i32, C.c_uint32, vp, C.c_size_t,
                                                vp, vp, vp, vp, vp, vp]
         lib.amx_beam_ctc_emissions.restype = i32
+    if hasattr(lib, "amx_beam_ctc_lm_emissions"):  # (added to ABI 7 by name: absent from older builds)
+        lib.amx_beam_ctc_lm_workspace.argtypes = [i32, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_beam_ctc_lm_workspace.restype = i32
+        lib.amx_beam_ctc_lm_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, i32, i32, C.c_uint32, vp, i32, vp,
+                                                  C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        lib.amx_beam_ctc_lm_emissions.restype = i32
     if hasattr(lib, "amx_resample"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_resample_bank.argtypes = [i64, i64, C.c_int32, C.c_double, C.POINTER(AmxResampleGeometry), vp, vp]
         lib.amx_resample_bank.restype = i32
