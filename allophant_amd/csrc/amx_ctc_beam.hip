@@ -14,13 +14,24 @@
 //   blank    (P, blank, true) from the <= 2 states of P
 //   repeat   (P, k, false) from the state itself (k != blank, !b) plus the states of P[:-1] eligible for k
 // Every state adds the same e[t, n], so within one prefix the plain candidates are monotone in e[t, n].  The frame's top
-// beam_width + 2 tokens are taken by (emission, then lower index): ties at the cut go by index, not all tied tokens (tie
-// order is one of the open points of DESIGN 9).  A token outside them has beam_width + 2 tokens ahead of it; leaving out
-// blank and last(P) (whose candidates may lie below), at least beam_width candidates of the same prefix are at least as
-// high, so its plain candidate cannot survive except by a tie.  Plain candidates whose key is a repeat (P+n already a beam
-// state) are dropped; the repeat holds them.
+// beam_width + 2 tokens are taken by (emission as added, then lower index).  A token outside them has beam_width + 2
+// tokens ahead of it in that order; leaving out blank and last(P) (whose candidates may lie below), beam_width tokens m
+// remain whose extension P+m is at least as high.  Where P+m is not a beam state it is a plain candidate of the same
+// leader and, at an equal score, has the lower token.  Where it is a beam state the repeat candidate of that state holds
+// it, and repeat candidates come first in candidate order -- they must: such a repeat can equal the plain score exactly
+// (a state 37 or more below the extension vanishes in the log-add) and would otherwise lose that tie to the token off the
+// list.  So the unlisted token's plain candidate has beam_width candidates ahead of it and is not enumerated.  Plain
+// candidates whose key is a repeat (P+n already a beam state) are dropped; the repeat holds them.
 // That leaves at most B * (B + 4) candidates per frame, whose top B are found exactly by a radix select over their
-// order-preserving 64-bit keys and compacted in index order (deterministic; equal scores resolve by candidate index).
+// order-preserving 64-bit keys and compacted in index order.
+//
+// Tie order (the rule of DESIGN 9, which tests/ctc_beam_util.py restates without reference to this file).  Candidate
+// index is (kind, slot, token): one repeat candidate per state at its slot j, then the plain candidates of leader L (the
+// lowest slot of its prefix) at nS + L * KS + p with the list in class order, then one blank candidate per leader.  Equal
+// scores resolve by lower candidate index, and the survivors take the new slots in index order, not in score order.
+// Equal members of a merged candidate resolve in push order (fold keeps the first of equal ones): leader before partner,
+// and for a repeat the state itself, then the leader of P[:-1], then its partner.  The end step ranks equal merged scores
+// by lower leader slot.  Frames with no finite emission, and NaN, are outside the contract.
 //
 // A backpointer (parent slot << 16 | frame token) per (frame, slot) goes to a caller-supplied workspace; the end step
 // merges by prefix, ranks, and traces the n-best paths back into tokens and 1-based timesteps.
@@ -35,10 +46,12 @@ namespace {
 #include "amx_ctc_beam.inc"
 
 constexpr int BM_KMAX = BEAM_MAX + 2;                  // tokens considered for plain extensions per frame
-constexpr int BM_MMAX = BEAM_MAX * (BM_KMAX + 2);      // candidates per frame: plain, blank, repeat
+constexpr int BM_MMAX = BEAM_MAX * (BM_KMAX + 2);      // candidates per frame: repeat, plain, blank
+constexpr int BM_TILE = BM_MMAX - BM_KMAX;             // classes whose keys are staged at a time for the token list
 
 struct BeamSmem {
-    uint64_t key[BM_MMAX];  // candidate keys of the frame (0 = no candidate): the merged fp64 score, order-preserving
+    uint64_t key[BM_MMAX];  // candidate keys of the frame (0 = no candidate): the merged fp64 score, order-preserving;
+                            // before that, the staged token-list keys of step 1
     uint8_t par[BM_MMAX];   // slot of the candidate's highest member
     double sc[2][BEAM_MAX];
     uint64_t hs[2][BEAM_MAX];  // prefix hash
@@ -50,8 +63,9 @@ struct BeamSmem {
     int parent[BEAM_MAX];      // for a non-blank state: leader of P[:-1] in the beam, or -1
     int childp[BEAM_MAX];      // its last token's position in S, or -1
     double ek[BEAM_MAX];       // e[t, k] of a non-blank state
-    int S[BM_KMAX];            // the frame's top tokens, index order
-    double Se[BM_KMAX];
+    uint64_t Sk[BM_KMAX];      // the frame's top tokens, index order: their token-list keys,
+    int S[BM_KMAX];            //   the tokens
+    double Se[BM_KMAX];        //   and their emissions as added
     int win[BEAM_MAX];
     int hist[256];
     int wtmp[BM_WAVES];
@@ -65,8 +79,8 @@ __device__ __forceinline__ Members members(const BeamSmem& sm, int cur, int nS, 
     Members g;
     g.m = 0;
     const double cut = sm.cut;
-    if (i < nS * KS) {
-        const int L = i / KS, p = i - L * KS;
+    if (i >= nS && i < nS + nS * KS) {
+        const int L = (i - nS) / KS, p = (i - nS) - L * KS;
         const int n = sm.S[p];
         *token = n;
         if (sm.leader[L] != L || n == blank) return g;
@@ -80,8 +94,8 @@ __device__ __forceinline__ Members members(const BeamSmem& sm, int cur, int nS, 
             const double v = sm.sc[cur][q] + e;
             if (v >= cut) g.push(v, q);
         }
-    } else if (i < nS * KS + nS) {
-        const int L = i - nS * KS;
+    } else if (i >= nS) {
+        const int L = i - nS - nS * KS;
         *token = blank;
         if (sm.leader[L] != L) return g;
         const double e = sm.e0;
@@ -93,7 +107,7 @@ __device__ __forceinline__ Members members(const BeamSmem& sm, int cur, int nS, 
             if (v >= cut) g.push(v, q);
         }
     } else {
-        const int j = i - nS * KS - nS;
+        const int j = i;
         const int n = sm.tk[cur][j];
         *token = n;
         if (n == blank || sm.pb[cur][j]) return g;
@@ -135,17 +149,39 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
     const int KS = min(beam + 2, C);
     for (int t = 0; t < len; ++t) {
         const float* e = row + (int64_t)t * stride_t;
-        // 1. the frame's top KS tokens by (emission, -index)
-        if (KS == C) {
-            if (tid < C) sm.S[tid] = tid;
-        } else {
-            auto fkey = [&](int c) -> uint64_t { return ((uint64_t)key32(e[c]) << 16) | (uint64_t)(0xffffu - (unsigned)c); };
-            radix_select<uint64_t, 48>(C, KS, fkey, sm);
-            compact<uint64_t>(C, KS, fkey, [&](int pos, int c) { sm.S[pos] = c; }, sm);
+        // 1. the frame's top KS tokens by (emission as added, then lower index), in class order.  Under EXP the value as
+        // added is the fp32 exponential, one value for every raw emission below about -104 and for neighbours that round
+        // together: the raw value would rank tokens that the candidates cannot tell apart, and differently from the decoder
+        // with a language model.  Each class is converted once: its key (value image << 16 | 0xffff - class) is staged in
+        // sm.key, which is free until step 4, a tile of classes at a time behind the winners of the tiles before.  (+ 0.0f:
+        // -0.0f and 0.0f are one value and must be one key.  sm.ek and sm.e0 of step 2 keep the sign of a raw -0.0f, which
+        // no sum shows: the scores they are added to are never -0.0.)
+        int nb = 0;
+        for (int c0 = 0; c0 < C; c0 += BM_TILE) {
+            const int n = min(BM_TILE, C - c0);
+            uint64_t* dst = KS == C ? sm.Sk : sm.key + nb;  // KS == C: every class, nothing to select
+            if (tid < nb) sm.key[tid] = sm.Sk[tid];
+            for (int i = tid; i < n; i += BM_THREADS) {
+                const int c = c0 + i;
+                dst[i] = ((uint64_t)key32((float)emission(e[c], exp_mode) + 0.0f) << 16) | (uint64_t)(0xffffu - (unsigned)c);
+            }
+            if (KS == C) {
+                __syncthreads();
+                break;
+            }
+            const int tot = nb + n;  // > KS
+            auto fkey = [&](int i) -> uint64_t { return sm.key[i]; };
+            radix_select<uint64_t, 48>(tot, KS, fkey, sm);  // (begins with a barrier: the staged keys are visible)
+            compact<uint64_t>(tot, KS, fkey, [&](int pos, int i) { sm.Sk[pos] = sm.key[i]; }, sm);
+            __syncthreads();
+            nb = KS;
         }
-        __syncthreads();
-        // 2. emissions of S, blank, per-state structure
-        if (tid < KS) sm.Se[tid] = emission(e[sm.S[tid]], exp_mode);
+        // 2. tokens and emissions of S, the blank's emission, per-state structure
+        if (tid < KS) {
+            const uint64_t k = sm.Sk[tid];
+            sm.S[tid] = 0xffff - (int)(k & 0xffffu);
+            sm.Se[tid] = (double)unkey32((uint32_t)(k >> 16));
+        }
         if (tid == BM_THREADS - 1) sm.e0 = emission(e[blank], exp_mode);
         if (tid < nS) {
             const uint64_t h = sm.hs[cur][tid];
@@ -165,7 +201,7 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
                     if (sm.hs[cur][j] == ph) P = j;
                 if (P >= 0)
                     for (int p = 0; p < KS; ++p)
-                        if (sm.S[p] == k) cp = p;
+                        if (0xffff - (int)(sm.Sk[p] & 0xffffu) == k) cp = p;
                 sm.ek[tid] = emission(e[k], exp_mode);
             }
             sm.parent[tid] = P;
@@ -203,7 +239,7 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
         __syncthreads();
         // 5. a plain candidate onto a prefix already in the beam is that state's repeat candidate
         if (tid < nS && sm.parent[tid] >= 0 && sm.childp[tid] >= 0) {
-            const int i = sm.parent[tid] * KS + sm.childp[tid];
+            const int i = nS + sm.parent[tid] * KS + sm.childp[tid];
             if (sm.key[i]) {
                 sm.key[i] = 0;
                 atomicSub(&sm.nvalid, 1);
@@ -232,21 +268,21 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
             const int i = sm.win[tid];
             const double v = unkey64(sm.key[i]);
             const int par = sm.par[i];
-            const int tok = i < nS * KS ? sm.S[i % KS] : (i < nS * KS + nS ? blank : sm.tk[cur][i - nS * KS - nS]);
-            if (i < nS * KS) {
-                const int L = i / KS;
+            const int tok = i < nS ? sm.tk[cur][i] : (i < nS + nS * KS ? sm.S[(i - nS) % KS] : blank);
+            if (i >= nS && i < nS + nS * KS) {
+                const int L = (i - nS) / KS;
                 sm.hs[nxt][tid] = extend_hash(sm.hs[cur][L], tok);
                 sm.ph[nxt][tid] = sm.hs[cur][L];
                 sm.tk[nxt][tid] = tok;
                 sm.pb[nxt][tid] = 0;
-            } else if (i < nS * KS + nS) {
-                const int L = i - nS * KS;
+            } else if (i >= nS) {
+                const int L = i - nS - nS * KS;
                 sm.hs[nxt][tid] = sm.hs[cur][L];
                 sm.ph[nxt][tid] = sm.ph[cur][L];
                 sm.tk[nxt][tid] = blank;
                 sm.pb[nxt][tid] = 1;
             } else {
-                const int j = i - nS * KS - nS;
+                const int j = i;
                 sm.hs[nxt][tid] = sm.hs[cur][j];
                 sm.ph[nxt][tid] = sm.ph[cur][j];
                 sm.tk[nxt][tid] = tok;

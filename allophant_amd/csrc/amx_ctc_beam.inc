@@ -23,6 +23,7 @@ __device__ __forceinline__ uint32_t key32(float v) {
     const uint32_t u = __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+__device__ __forceinline__ float unkey32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 __device__ __forceinline__ uint64_t key64(double v) {
     const uint64_t u = (uint64_t)__double_as_longlong(v);
     const uint64_t k = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);

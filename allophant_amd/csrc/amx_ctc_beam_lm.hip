@@ -11,8 +11,13 @@
 //
 // Candidate reduction.  Without an LM every state adds the same e[t, n], and one list of the frame's top tokens serves all
 // prefixes.  Here a prefix P adds g_P(n) = e[t, n] + a_P(n), so each prefix leader keeps its OWN top min(beam + 2, C)
-// non-blank tokens by (g_P, then lower index).  A token outside that list has beam + 2 tokens of the same prefix ahead of
-// it; leaving out last(P) (whose candidate may lie below), at least beam candidates of that prefix are at least as high.
+// non-blank tokens by (g_P, then lower index), g_P being the fp64 sum of the emission as added and a.  A token outside
+// that list has beam + 2 tokens of the same prefix ahead of it; leaving out last(P) (whose candidate may lie below), at
+// least beam tokens m remain whose extension P+m is at least as high: a plain candidate of the same leader with the lower
+// token, or, where P+m is a beam state, that state's repeat candidate, which comes first in candidate order (see
+// amx_ctc_beam.hip for why it must).  So the token's plain candidate cannot survive and is not enumerated.  Tie order is
+// that of amx_ctc_beam.hip (the rule of DESIGN 9): candidate index is (kind, slot, token) -- repeat, plain, blank -- with
+// each list in class order, equal members in push order, the end ranking by lower leader slot.
 // Plain candidates whose key is already a beam state go to that state's repeat candidate whether or not the token is in
 // the list (the third branch of members()).  That leaves at most B * (B + 4) candidates per frame, as without an LM.
 //
@@ -33,7 +38,7 @@ namespace {
 #include "amx_ctc_beam.inc"
 
 constexpr int BL_KMAX = BEAM_MAX + 2;               // list length per prefix
-constexpr int BL_MMAX = BEAM_MAX * (BL_KMAX + 2);   // candidates per frame: plain, blank, repeat
+constexpr int BL_MMAX = BEAM_MAX * (BL_KMAX + 2);   // candidates per frame: repeat, plain, blank
 constexpr int BL_WCAP = 192;                        // per-wave selection buffer: three keys per lane
 
 struct BeamLmSmem {
@@ -192,13 +197,13 @@ __device__ __forceinline__ void prefix_list(BeamLmSmem& sm, const float* __restr
     wave_sync();  // the buffer is free for the wave's next prefix
 }
 
-// Members of candidate i: plain candidates i = L * KS + p (leader L, list position p), then one blank candidate per
-// leader, then one repeat candidate per state; their scores and state slots, after the threshold.
+// Members of candidate i: one repeat candidate per state, then plain candidates i = nS + L * KS + p (leader L, list
+// position p), then one blank candidate per leader; their scores and state slots, after the threshold.
 __device__ __forceinline__ Members members(const BeamLmSmem& sm, int cur, int nS, int KS, int blank, double cut, int i, int* token) {
     Members g;
     g.m = 0;
-    if (i < nS * KS) {
-        const int L = i / KS, p = i - L * KS;
+    if (i >= nS && i < nS + nS * KS) {
+        const int L = (i - nS) / KS, p = (i - nS) - L * KS;
         *token = blank;
         if (sm.leader[L] != L || p >= sm.nl[L]) return g;
         const int n = sm.ltok[L][p];
@@ -213,8 +218,8 @@ __device__ __forceinline__ Members members(const BeamLmSmem& sm, int cur, int nS
             const double v = (sm.sc[cur][q] + e) + a;
             if (v >= cut) g.push(v, q);
         }
-    } else if (i < nS * KS + nS) {
-        const int L = i - nS * KS;
+    } else if (i >= nS) {
+        const int L = i - nS - nS * KS;
         *token = blank;
         if (sm.leader[L] != L) return g;
         const double e = sm.e0;
@@ -226,7 +231,7 @@ __device__ __forceinline__ Members members(const BeamLmSmem& sm, int cur, int nS
             if (v >= cut) g.push(v, q);
         }
     } else {
-        const int j = i - nS * KS - nS;
+        const int j = i;
         const int n = sm.tk[cur][j];
         *token = n;
         if (n == blank || sm.pb[cur][j]) return g;
@@ -395,7 +400,7 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_lm_kernel(
         __syncthreads();
         // 5. a plain candidate onto a prefix already in the beam is that state's repeat candidate
         if (tid < nS && sm.parent[tid] >= 0 && sm.childp[tid] >= 0) {
-            const int i = sm.parent[tid] * KS + sm.childp[tid];
+            const int i = nS + sm.parent[tid] * KS + sm.childp[tid];
             if (sm.key[i]) {
                 sm.key[i] = 0;
                 atomicSub(&sm.nvalid, 1);
@@ -425,16 +430,16 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_lm_kernel(
             const double v = unkey64(sm.key[i]);
             const int par = sm.par[i];
             int tok;
-            if (i < nS * KS) {
-                const int L = i / KS;
-                tok = sm.ltok[L][i - L * KS];
+            if (i >= nS && i < nS + nS * KS) {
+                const int L = (i - nS) / KS;
+                tok = sm.ltok[L][(i - nS) - L * KS];
                 sm.hs[nxt][tid] = extend_hash(sm.hs[cur][L], tok);
                 sm.ph[nxt][tid] = sm.hs[cur][L];
                 sm.tk[nxt][tid] = tok;
                 sm.pb[nxt][tid] = 0;
                 sm.lt[nxt][tid] = tok;
-            } else if (i < nS * KS + nS) {
-                const int L = i - nS * KS;
+            } else if (i >= nS) {
+                const int L = i - nS - nS * KS;
                 tok = blank;
                 sm.hs[nxt][tid] = sm.hs[cur][L];
                 sm.ph[nxt][tid] = sm.ph[cur][L];
@@ -442,7 +447,7 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_lm_kernel(
                 sm.pb[nxt][tid] = 1;
                 sm.lt[nxt][tid] = sm.lt[cur][L];
             } else {
-                const int j = i - nS * KS - nS;
+                const int j = i;
                 tok = sm.tk[cur][j];
                 sm.hs[nxt][tid] = sm.hs[cur][j];
                 sm.ph[nxt][tid] = sm.ph[cur][j];

@@ -11,7 +11,10 @@ extern "C" {
  * lexicon-free, no LM, blank = silence, log_add = True, beam_threshold 50, every token considered per frame -- decoded on
  * the device.  Symbols added to ABI 6 without a struct change (detect them with dlsym).  The semantics are restated in
  * DESIGN 9; scores are fp64 sums of the emissions as given (or of their exponentials under AMX_BEAM_EXP_EMISSIONS, which is
- * what the reference passes: `log_emissions.exp()`).
+ * what the reference passes: `log_emissions.exp()`).  An emission of -inf is an ordinary value (under
+ * AMX_BEAM_EXP_EMISSIONS it adds exactly 0); a frame with no finite emission, and NaN, are outside the contract.  Equal
+ * scores resolve by one stated rule (candidates in (kind, beam slot, class) order, token lists by the value as
+ * added and then the lower class), so the result is a function of the inputs alone.
  *
  * Limits: 1 <= beam_width <= 64, 1 <= n_best <= beam_width, 2 <= C <= 65535, 0 <= blank < C; AMX_EINVAL otherwise.
  *

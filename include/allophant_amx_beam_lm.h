@@ -18,7 +18,8 @@ extern "C" {
  * and an -inf entry forbids the transition at every weight, 0 included.  Blank and repeat candidates add nothing.  The
  * frame threshold of 50 is taken against the best generated candidate with the language-model term included.  At the end
  * every state adds lm_weight * lm[last(P), C]; an -inf entry there drops the state, and a row with no state left has
- * hyp_counts 0.  `scores` are the fused totals.
+ * hyp_counts 0.  `scores` are the fused totals.  Equal scores resolve by the rule of amx_beam_ctc_emissions, each
+ * prefix's token list being cut by (emission as added + language-model term, then the lower class).
  *
  * `lm` is a DEVICE stack [n_lm, C + 1, C + 1], `lm_index` a DEVICE int32 [N]: the table of each row, or -1 for a row that
  * runs without one (no term, no end term: amx_beam_ctc_emissions bit for bit, as is every row at lm_weight 0 and

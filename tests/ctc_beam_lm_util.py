@@ -1,7 +1,8 @@
 """Executable form of the CTC beam-search contract with a token-level language model: flashlight's
-``LexiconFreeDecoder`` with a bigram instead of ZeroLM, restated in plain float64 NumPy over the helpers of
-``ctc_beam_util``.  It enumerates every (state, token) candidate of every frame.  The HIP kernel (amx_ctc_beam_lm.hip) is
-held to it in test_gpu_beam_lm.py, and it is held to brute force over all alignments in test_ctc_beam_lm_contract.py.
+``LexiconFreeDecoder`` with a bigram instead of ZeroLM, restated in plain float64 NumPy: the frame loop is
+``ctc_beam_util.search``, which both restatements share and which states the tie rule.  It enumerates every (state, token)
+candidate of every frame.  The HIP kernel (amx_ctc_beam_lm.hip) is held to it in test_gpu_beam_lm.py and, on tied inputs,
+in test_gpu_beam_ties.py; it is held to brute force over all alignments in test_ctc_beam_lm_contract.py.
 
 ``table`` is ``[C + 1, C + 1]``: row = previous token of the prefix (row C: begin), column = next token (column C: end).  A
 pair (state, token n) that emits a new token after the prefix P scores ``(s + e[t, n]) + (weight * table[last(P), n] +
@@ -12,93 +13,17 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from ctc_beam_util import THRESHOLD, Hypothesis, _fold, _Trie, brute_force, emissions_as_added
+from ctc_beam_util import THRESHOLD, Hypothesis, brute_force, search
 
 
 def beam_search_lm(em, length: int, beam_width: int, n_best: int, table, weight: float = 1.0, token_score: float = 0.0,
-                   blank: int = 0, exp: bool = True, threshold: float = THRESHOLD) -> List[Hypothesis]:
-    """Decodes one utterance: ``em`` fp32 [T, C]; frames at or beyond min(length, T) are ignored."""
-    em = np.asarray(em)
-    T, C = em.shape
-    L = max(0, min(int(length), T))
-    e = emissions_as_added(em[:L], exp)
-    lm = None if table is None else np.asarray(table, dtype=np.float32).astype(np.float64)
-    if lm is not None:
-        assert lm.shape == (C + 1, C + 1)
-    weight, token_score = float(weight), float(token_score)
-    trie = _Trie()
-    pid = np.array([0], dtype=np.int64)
-    k = np.array([blank], dtype=np.int64)
-    b = np.array([False])
-    s = np.array([0.0])
-    back: List[Tuple[np.ndarray, np.ndarray]] = []
-    n_all = np.arange(C, dtype=np.int64)
-
-    def last_of(ids):
-        last = np.array(trie.last)[ids]
-        return np.where(last < 0, C, last)
-
-    for t in range(L):
-        S = len(s)
-        x = (s[:, None] + e[t][None, :]).ravel()
-        slot = np.repeat(np.arange(S), C)
-        n = np.tile(n_all, S)
-        ks, bs, ps = k[slot], b[slot], pid[slot]
-        parent = np.array(trie.parent)[ps]
-        last = np.array(trie.last)[ps]
-        emit = (n != blank) & ((n != ks) | bs)
-        is_blank = n == blank
-        generated = np.ones(len(x), dtype=bool)
-        if lm is not None:
-            entry = lm[last_of(ps), n]
-            allowed = np.isfinite(entry)
-            a = weight * np.where(allowed, entry, 0.0) + token_score
-            x = np.where(emit, x + a, x)
-            generated = ~emit | allowed
-        key = np.empty((len(x), 4), dtype=np.int64)
-        key[:, 0] = np.where(emit, ps, parent)
-        key[:, 1] = np.where(emit, n, last)
-        key[:, 2] = np.where(is_blank, blank, n)
-        key[:, 3] = np.where(is_blank, 1, 0)
-        best = np.max(x[generated])
-        keep = generated & ~(x < best - threshold)
-        key, x, slot, n = key[keep], x[keep], slot[keep], n[keep]
-        gkeys, acc, head = _fold(key, x)
-        top = np.argsort(-acc, kind="stable")[:beam_width]
-        gkeys, acc, head = gkeys[top], acc[top], head[top]
-        pid = np.array([0 if pk[1] < 0 else trie.get(int(pk[0]), int(pk[1])) for pk in gkeys], dtype=np.int64)
-        k = gkeys[:, 2].copy()
-        b = gkeys[:, 3].astype(bool)
-        s = acc
-        back.append((slot[head], n[head]))
-    # end: every state becomes (P, blank, false, s + weight * table[last(P), end]), merged by prefix
-    alive = np.ones(len(s), dtype=bool)
-    if lm is not None:
-        entry = lm[last_of(pid), C]
-        alive = np.isfinite(entry)
-        s = s + weight * np.where(alive, entry, 0.0)
-    if not alive.any():
-        return []
-    keep = alive & ~(s < np.max(s[alive]) - threshold)
-    gkeys, acc, head = _fold(pid[keep][:, None], s[keep])
-    slots = np.flatnonzero(keep)[head]
-    top = np.argsort(-acc, kind="stable")[:beam_width][:n_best]
-    hyps = []
-    for g in top:
-        slot = int(slots[g])
-        frames = [0] * L
-        for t in range(L - 1, -1, -1):
-            parents, tokens = back[t]
-            frames[t] = int(tokens[slot])
-            slot = int(parents[slot])
-        out, ts, prev = [], [], blank
-        for t, v in enumerate(frames):
-            if v != blank and v != prev:
-                out.append(v)
-                ts.append(t + 1)
-            prev = v
-        hyps.append(Hypothesis(out, float(acc[g]), ts))
-    return hyps
+                   blank: int = 0, exp: bool = True, threshold: float = THRESHOLD, reverse_ties: bool = False,
+                   report: Optional[dict] = None) -> List[Hypothesis]:
+    """Decodes one utterance: ``em`` fp32 [T, C]; frames at or beyond min(length, T) are ignored.  Ties resolve by the rule
+    stated at ``ctc_beam_util.search``, which holds the one frame loop of both restatements; ``reverse_ties`` and ``report``
+    are for tests and described there."""
+    return search(em, length, beam_width, n_best, table, weight, token_score, blank=blank, exp=exp, threshold=threshold,
+                  reverse_ties=reverse_ties, report=report)
 
 
 def lm_score(labelling, table, weight: float, token_score: float) -> float:
