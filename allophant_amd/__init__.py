@@ -12,7 +12,8 @@ __all__ = ["spec", "synthetic", "Estimator", "Batch", "Predictions", "GreedyCTCD
            "levensthein_operations_batch", "levensthein_substitutions", "to_substitutions", "PropertyWeighting",
            "levensthein_matrix", "levensthein_confusions_batch", "ConfusionCounts", "ConfusionTable", "Alignment", "Aligned", "ctc_forced_align", "label_targets", "segments", "Score", "Scored",
            "Rescored", "ctc_score", "Found", "Hit", "ctc_search", "pick_hits", "query_targets", "LongPlan", "plan_windows",
-           "gather_windows", "stitch_windows", "Variants", "Alternatives", "ctc_variants", "PhonotacticLM"]
+           "gather_windows", "stitch_windows", "Variants", "Alternatives", "ctc_variants", "PhonotacticLM",
+           "TargetGraph", "GraphAlignment", "GraphAligned", "ctc_graph_align", "slot_targets"]
 __version__ = "0.1.0"
 
 
@@ -50,6 +51,10 @@ def __getattr__(name):
         from . import variants
 
         return getattr(variants, name)
+    if name in ("TargetGraph", "GraphAlignment", "GraphAligned", "ctc_graph_align", "slot_targets"):
+        from . import graph_alignment
+
+        return getattr(graph_alignment, name)
     if name == "PhonotacticLM":
         from . import phonotactics
 

@@ -5,6 +5,7 @@
 #include "../../include/allophant_amx_beam.h"
 #include "../../include/allophant_amx_beam_lm.h"
 #include "../../include/allophant_amx_align.h"
+#include "../../include/allophant_amx_align_graph.h"
 #include "../../include/allophant_amx_score.h"
 #include "../../include/allophant_amx_search.h"
 #include "../../include/allophant_amx_variants.h"
@@ -2584,6 +2585,86 @@ extern "C" int amx_ctc_align_long(amx_handle h, const float* out, const int64_t*
                                   float* totals, int32_t* status, void* stream) {
     return align_handle(true, h, out, frame_lengths, N, L, target_offsets, target_ids, max_target, workspace, workspace_bytes, paths,
                         frame_scores, spans, span_scores, totals, status, stream);
+}
+
+// ---- alignment over label graphs (include/allophant_amx_align_graph.h): the same call frame, five graph arrays for the two
+// target arrays ----
+namespace {
+struct AlignGraph {
+    const int32_t *node_offsets, *node_classes, *node_flags, *arc_offsets, *arc_preds;
+    int64_t max_nodes;
+    // what a call dereferences on the device (arc_preds may be empty, but not when a row can hold an arc)
+    bool complete() const { return node_offsets && arc_offsets && (max_nodes == 0 || (node_classes && node_flags)) && (max_nodes < 2 || arc_preds); }
+};
+int align_graph_check(amx_handle h, int64_t rows, int64_t T, int64_t max_nodes) {
+    if (max_nodes < 0 || max_nodes > AMX_ALIGN_GRAPH_MAX_NODES)
+        return fail(h, AMX_EINVAL, "max_nodes must be 0 to " + std::to_string(AMX_ALIGN_GRAPH_MAX_NODES) + ", got " + std::to_string(max_nodes));
+    return align_check(h, rows, T, max_nodes);
+}
+int align_graph_rows(amx_handle h, int device, CtcRows c, const int64_t* host_lengths, const AlignGraph& g, void* workspace,
+                     size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores, float* totals,
+                     int32_t* status, hipStream_t s) {
+    size_t need = 0;
+    if (!ctc_align_graph_workspace_bytes(c.rows, c.T, g.max_nodes, &need))
+        return fail(h, AMX_EINVAL, "graph alignment workspace size not representable");
+    if (int rc = check_workspace(h, "graph alignment", need, workspace, workspace_bytes)) return rc;
+    if (int rc = ctc_rows_begin(h, device, host_lengths, &c, s)) return rc;
+    c.target_offsets = g.node_offsets, c.target_ids = g.node_classes, c.max_target = (int)g.max_nodes;
+    AlignGraphArgs a{};
+    static_cast<CtcRows&>(a) = c;
+    a.node_flags = g.node_flags, a.arc_offsets = g.arc_offsets, a.arc_preds = g.arc_preds;
+    a.workspace = (uint4*)workspace;
+    a.paths = paths, a.frame_scores = frame_scores, a.spans = spans, a.span_scores = span_scores, a.totals = totals, a.status = status;
+    launch_ctc_align_graph(a, s);
+    return ctc_launched(h, "graph alignment");
+}
+}  // namespace
+
+extern "C" int amx_ctc_align_graph_workspace(int64_t rows, int64_t T, int64_t max_nodes, size_t* bytes) {
+    if (!bytes) return fail(nullptr, AMX_EINVAL, "null size pointer");
+    if (int rc = align_graph_check(nullptr, rows, T, max_nodes)) return rc;
+    if (!ctc_align_graph_workspace_bytes(rows, T, max_nodes, bytes))
+        return fail(nullptr, AMX_EINVAL, "graph alignment workspace size not representable");
+    return AMX_OK;
+}
+
+extern "C" int amx_ctc_align_graph_emissions(int device, const float* emissions, int64_t stride_n, int64_t stride_t,
+                                             const int32_t* frame_lengths, int N, int64_t T, int C, int blank_index,
+                                             const int32_t* node_offsets, const int32_t* node_classes, const int32_t* node_flags,
+                                             const int32_t* arc_offsets, const int32_t* arc_preds, int64_t max_nodes, void* workspace,
+                                             size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans,
+                                             float* span_scores, float* totals, int32_t* status, void* stream) {
+    if (int rc = align_graph_check(nullptr, N, T, max_nodes)) return rc;
+    if (int rc = align_check_classes(nullptr, C, blank_index)) return rc;
+    if (N == 0) return AMX_OK;
+    const AlignGraph g{node_offsets, node_classes, node_flags, arc_offsets, arc_preds, max_nodes};
+    if (!frame_lengths || !g.complete() || !totals || !status || (T && (!emissions || !paths || !frame_scores)) ||
+        (max_nodes && (!spans || !span_scores)))
+        return fail(nullptr, AMX_EINVAL, "null buffer");
+    const CtcRows c = rows_of_tensor(emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    return align_graph_rows(nullptr, device, c, nullptr, g, workspace, workspace_bytes, paths, frame_scores, spans, span_scores, totals,
+                            status, (hipStream_t)stream);
+}
+
+extern "C" int amx_ctc_align_graph(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L,
+                                   const int32_t* node_offsets, const int32_t* node_classes, const int32_t* node_flags,
+                                   const int32_t* arc_offsets, const int32_t* arc_preds, int64_t max_nodes, void* workspace,
+                                   size_t workspace_bytes, int32_t* paths, float* frame_scores, int32_t* spans, float* span_scores,
+                                   float* totals, int32_t* status, void* stream) {
+    if (!h) return AMX_EINVAL;
+    const AlignGraph g{node_offsets, node_classes, node_flags, arc_offsets, arc_preds, max_nodes};
+    if (!out || !frame_lengths || !g.complete() || !paths || !frame_scores || !totals || !status || (max_nodes > 0 && (!spans || !span_scores)))
+        return fail(h, AMX_EINVAL, "null buffer");
+    HIPCHK(h, hipSetDevice(h->device));
+    CtcRows c;
+    int rc = rows_of_handle(h, out, N, L, &c);
+    if (rc) return rc;
+    if ((rc = align_graph_check(h, c.rows, c.T, max_nodes))) return rc;
+    if (c.rows == 0) return AMX_OK;
+    for (const OutDesc& d : h->out_all)
+        if ((rc = align_check_classes(h, d.C, 0))) return rc;
+    return align_graph_rows(h, 0, c, frame_lengths, g, workspace, workspace_bytes, paths, frame_scores, spans, span_scores, totals,
+                            status, (hipStream_t)stream);
 }
 
 // =================================================================================================================

@@ -614,6 +614,17 @@ struct AlignArgs : CtcRows {
 bool ctc_align_workspace_bytes(int64_t rows, int64_t T, int64_t max_target, size_t* bytes);
 void launch_ctc_align(AlignArgs a, hipStream_t s);
 
+// CTC forced alignment over label graphs (amx_ctc_align_graph.hip), the same rows and outputs: contract in
+// include/allophant_amx_align_graph.h.  The rows' targets are the graph's nodes (target_offsets = node_offsets, target_ids =
+// node_classes, max_target = max_nodes); the workspace holds per (strip, frame) one 32-byte record, two uint4.  A struct of
+// its own: the kernels of amx_ctc_align.hip see the AlignArgs they always saw.
+struct AlignGraphArgs : AlignArgs {
+    const int32_t *node_flags, *arc_offsets, *arc_preds;
+};
+// false when the size is not representable in size_t
+bool ctc_align_graph_workspace_bytes(int64_t rows, int64_t T, int64_t max_nodes, size_t* bytes);
+void launch_ctc_align_graph(AlignGraphArgs a, hipStream_t s);
+
 // The same contract for rows of up to AMX_ALIGN_LONG_MAX_TARGET targets (amx_ctc_align_long.hip): one launch per block of
 // ALIGN_LONG_FRAMES frames over a grid of (state tiles, rows); a tile owns ALIGN_LONG_OWNED states and recomputes a left halo
 // of ALIGN_LONG_HALO.  Besides the moves the workspace holds two state rows per row (strips * 64 floats each, ping-ponged by

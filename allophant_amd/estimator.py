@@ -28,6 +28,7 @@ from torch import Tensor
 
 from . import alignment as _alignment
 from . import ctc as _ctc
+from . import graph_alignment as _graph_alignment
 from . import lib as _lib
 from . import phonotactics as _phonotactics
 from . import scoring as _scoring
@@ -35,6 +36,8 @@ from . import search as _search
 from . import spec as _spec
 from . import variants as _variants
 from .alignment import Aligned, Alignment, ctc_forced_align, label_targets, segments  # noqa: F401  (the façade's names)
+from .graph_alignment import (GraphAligned, GraphAlignment, TargetGraph, ctc_graph_align,  # noqa: F401  (the façade's graph names)
+                              slot_targets)
 from .scoring import Rescored, Score, Scored, ctc_score  # noqa: F401  (the façade's scoring names)
 from .search import Found, Hit, ctc_search, pick_hits, query_targets  # noqa: F401  (the façade's search names)
 from .phonotactics import PhonotacticLM  # noqa: F401  (the façade's language-model name)
@@ -915,6 +918,35 @@ class Estimator:
         """``align_device`` fetched to the host: per output with targets and utterance an ``Alignment`` (``None`` where no
         alignment exists)."""
         return self.align_device(predictions, targets, long).alignments()
+
+    def align_graph_device(self, predictions: Predictions, graphs: Dict[str, Sequence["_graph_alignment.TargetGraph"]]
+                           ) -> "_graph_alignment.GraphAligned":
+        """On-device CTC forced alignment over pronunciation graphs (``amx_ctc_align_graph``) of every output of
+        ``predictions``: ``graphs`` maps an output name to one ``TargetGraph`` per utterance (``TargetGraph.from_slots`` over
+        ``graph_alignment.slot_targets`` builds them from symbols).  An output without an entry is aligned against the graph
+        of no nodes and left out of ``GraphAligned.present``.  The result stays in HBM."""
+        names, N, L, T, O, frame_lengths, lengths_pointer, stream = self._predictions_call(predictions)
+        rows = self._target_rows(predictions, graphs, names, N, "align")
+        rows = [row if isinstance(row, _graph_alignment.TargetGraph) else _graph_alignment.TargetGraph.chain(row) for row in rows]
+        packed, starts, counts = _graph_alignment.pack_graphs(rows)
+        max_nodes = max(counts)
+        with torch.cuda.device(self._device):
+            meta = packed.to(self._device)
+            b = _graph_alignment.allocate(self._lib, O * N, T, max_nodes, self._device)
+            code = self._lib.amx_ctc_align_graph(
+                self._handle, C.c_void_p(predictions._flat.data_ptr()), lengths_pointer, N, L,
+                *_graph_alignment.graph_pointers(meta, starts), max_nodes, *b.pointers(), C.c_void_p(stream))
+            _lib.check(self._lib, self._handle, code)
+        return _graph_alignment.GraphAligned(
+            names, [name for name in names if name in graphs], b.paths.view(O, N, T), b.frame_scores.view(O, N, T),
+            b.spans.view(O, N, max_nodes, 2), b.span_scores.view(O, N, max_nodes), b.totals.view(O, N), b.status.view(O, N),
+            frame_lengths.tolist(), [rows[o * N:(o + 1) * N] for o in range(O)])
+
+    def align_graph(self, predictions: Predictions, graphs: Dict[str, Sequence["_graph_alignment.TargetGraph"]]
+                    ) -> Dict[str, List[Optional["_graph_alignment.GraphAlignment"]]]:
+        """``align_graph_device`` fetched to the host: per output with graphs and utterance a ``GraphAlignment`` (``None``
+        where no path exists)."""
+        return self.align_graph_device(predictions, graphs).alignments()
 
     def _score_call(self, call, predictions: Predictions, candidates: int, meta: Tensor, max_target: int, posteriors: bool):
         """``amx_ctc_score`` over every output of ``predictions`` (``call`` is their ``_predictions_call``): ``meta`` holds the

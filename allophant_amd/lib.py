@@ -71,6 +71,10 @@ ALIGN_LONG_EXPORTS = ["amx_ctc_align_long_workspace", "amx_ctc_align_long_emissi
 ALIGN_LONG_MAX_TARGET = 262143  # AMX_ALIGN_LONG_MAX_TARGET
 ALIGN_LONG_FRAME_BLOCK = 64  # AMX_ALIGN_LONG_FRAME_BLOCK
 ALIGN_LONG_TILE_STATES = 832  # AMX_ALIGN_LONG_TILE_STATES
+# the alignment over pronunciation graphs (include/allophant_amx_align_graph.h; added to ABI 7, detected by name)
+ALIGN_GRAPH_EXPORTS = ["amx_ctc_align_graph_workspace", "amx_ctc_align_graph_emissions", "amx_ctc_align_graph"]
+ALIGN_GRAPH_MAX_NODES = 4095  # AMX_ALIGN_GRAPH_MAX_NODES
+ALIGN_GRAPH_MAX_IN = 6  # AMX_ALIGN_GRAPH_MAX_IN
 # the CTC forward-backward scoring entry points (include/allophant_amx_score.h; added to ABI 6, detected by name)
 SCORE_EXPORTS = ["amx_ctc_score_workspace", "amx_ctc_score_emissions", "amx_ctc_score"]
 SCORE_MAX_TARGET = 4095  # AMX_SCORE_MAX_TARGET
@@ -250,6 +254,15 @@ def load() -> C.CDLL:
         lib.amx_ctc_align_long_emissions.restype = i32
         lib.amx_ctc_align_long.argtypes = lib.amx_ctc_align.argtypes
         lib.amx_ctc_align_long.restype = i32
+    if hasattr(lib, "amx_ctc_align_graph"):  # (added to ABI 7 by name: absent from older builds)
+        lib.amx_ctc_align_graph_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
+        lib.amx_ctc_align_graph_workspace.restype = i32
+        lib.amx_ctc_align_graph_emissions.argtypes = [i32, vp, i64, i64, vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp,
+                                                      C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+        lib.amx_ctc_align_graph_emissions.restype = i32
+        lib.amx_ctc_align_graph.argtypes = [vp, vp, C.POINTER(i64), i32, i64, vp, vp, vp, vp, vp, i64, vp, C.c_size_t, vp, vp, vp,
+                                            vp, vp, vp, vp]
+        lib.amx_ctc_align_graph.restype = i32
     if hasattr(lib, "amx_ctc_score"):  # (absent from older builds under AMX_ABI_OVERRIDE)
         lib.amx_ctc_score_workspace.argtypes = [i64, i64, i64, C.POINTER(C.c_size_t)]
         lib.amx_ctc_score_workspace.restype = i32
