@@ -254,9 +254,8 @@ class Prefetcher:
             self._turn[shape] = (turn + 1) % self._ring
             ring_key = (shape, turn)
             if ring_key in self._events:
+                # (a ring of one comes through here too: the event of the batch just handed out was stored above)
                 self._stream.wait_event(self._events.pop(ring_key))
-            elif ring_key in self._history[-1:]:
-                self._stream.wait_stream(current)  # (ring of one: the batch just handed out still owns the slot)
         with torch.cuda.stream(self._stream):
             if ring_key is not None:
                 dev = self._slots[ring_key[0]][ring_key[1]]

@@ -602,8 +602,12 @@ class Estimator:
         right-aligned, not short).  The windows of all recordings run through ``predict`` in slices of at most ``batch_windows``
         rows, and each window's frames between its contexts -- at the ends of a recording, up to the end -- are copied into the
         recording's output.  A slice is gathered (``amx_long_gather``), predicted and stitched (``amx_long_stitch``) on the
-        current stream without a host synchronisation, in one fixed pair of device buffers: equal slices replay one recorded
-        graph.
+        current stream, in one fixed pair of device buffers: equal slices replay one recorded graph.  The call itself adds no
+        host synchronisation (the window table and the lengths go up from pinned memory: two small blocks per call from
+        torch's caching host allocator); each slice is a forward pass and takes one of the handle's four pinned length slots
+        (``amx_forward``), so from the fifth slice on the launch of a slice waits for the slice four before it.  Measured
+        under a stalled stream (tests/test_gpu_run_ahead.py): a call of four slices on a handle whose earlier passes have
+        completed returns before the device starts; a call of ten slices does not.
 
         The result is an ordinary ``Predictions`` of the whole batch (layout of ``amx_output_layout(R, Lmax)``, ``lengths`` the
         recordings' frames, zeros beyond them; a recording below the receptive field has length 0): ``greedy_decode``,
@@ -649,8 +653,9 @@ class Estimator:
             flat = torch.zeros(total, dtype=torch.float32, device=self._device)
             window_audio = torch.empty(rows * longest, dtype=torch.float32, device=self._device)
             window_out = torch.empty(self._output_layout(rows, longest)[2], dtype=torch.float32, device=self._device)
-            windows = torch.from_numpy(plan.windows).to(self._device)
-            device_lengths = lengths.to(self._device)
+            # (pinned and asynchronous: a copy out of pageable memory would wait for everything the stream holds)
+            windows = torch.from_numpy(plan.windows).pin_memory().to(self._device, non_blocking=True)
+            device_lengths = lengths.pin_memory().to(self._device, non_blocking=True)
             status = torch.empty(2, W, dtype=torch.int32, device=self._device)
             where = {d.name: d.offset for d in descs}
             for lo in range(0, W, rows):
