@@ -2379,6 +2379,37 @@ extern "C" int amx_beam_ctc_workspace(int beam_width, int64_t rows, int64_t T, s
     return AMX_OK;
 }
 
+namespace {
+// The checks that the two decoders of an emission tensor make alike, in three steps between which each entry point makes
+// its own: the blank; the geometry (after it, N == 0 means there is nothing to decode); and, once the buffers are known to
+// be there, the workspace and the device.
+int beam_check_blank(int C, int blank_index) {
+    return blank_index < 0 || blank_index >= C ? fail(nullptr, AMX_EINVAL, "blank_index out of range") : AMX_OK;
+}
+int beam_check_geometry(int N, int64_t T) {
+    if (N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative emission geometry");
+    return T > INT32_MAX ? fail(nullptr, AMX_EINVAL, "too many frames") : AMX_OK;
+}
+int beam_tensor_begin(int device, int beam_width, int N, int64_t T, void* workspace, size_t workspace_bytes) {
+    size_t need = 0;
+    amx_beam_ctc_workspace(beam_width, N, T, &need);
+    if (int rc = check_workspace(nullptr, "beam-search", need, workspace, workspace_bytes)) return rc;
+    return hipSetDevice(device) == hipSuccess ? AMX_OK : fail(nullptr, AMX_EHIP, "hipSetDevice failed");
+}
+// the two halves of a BeamArgs: an emission tensor whose geometry has been checked, and the search with its results
+void beam_tensor(BeamArgs* a, const float* emissions, int64_t stride_n, int64_t stride_t, const int32_t* frame_lengths, int N, int64_t T,
+                 int C, int blank_index) {
+    a->emissions = emissions, a->stride_n = stride_n, a->stride_t = stride_t, a->frame_lengths = frame_lengths;
+    a->N = N, a->T = (int)T, a->C = C, a->blank = blank_index;
+}
+void beam_search(BeamArgs* a, int beam_width, int n_best, uint32_t flags, void* workspace, int64_t* tokens, int64_t* timesteps,
+                 int32_t* counts, double* scores, int32_t* hyp_counts) {
+    a->beam = beam_width, a->n_best = n_best, a->exp_mode = (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0;
+    a->workspace = (uint32_t*)workspace, a->tokens = tokens, a->timesteps = timesteps, a->counts = counts, a->scores = scores;
+    a->hyp_counts = hyp_counts;
+}
+}  // namespace
+
 extern "C" int amx_beam_ctc(amx_handle h, const float* out, const int64_t* frame_lengths, int N, int64_t L, int beam_width, int n_best,
                             uint32_t flags, void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* timesteps,
                             int32_t* counts, double* scores, int32_t* hyp_counts, void* stream) {
@@ -2392,14 +2423,14 @@ extern "C" int amx_beam_ctc(amx_handle h, const float* out, const int64_t* frame
     const int T = (int)h->layout_T;
     for (const OutDesc& d : h->out_all)
         if ((rc = beam_check_classes(h, d.C))) return rc;
-    const int64_t rows = (int64_t)h->out_all.size() * N;
+    BeamArgs a{};
+    a.emissions = out, a.descs = cur_inv(h).out_all_dev, a.n_out = (int)h->out_all.size(), a.N = N, a.T = T;
     size_t need = 0;
-    amx_beam_ctc_workspace(beam_width, rows, T, &need);
+    amx_beam_ctc_workspace(beam_width, (int64_t)a.n_out * N, T, &need);
     if ((rc = check_workspace(h, "beam-search", need, workspace, workspace_bytes))) return rc;
-    const int* d_fl;
-    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &d_fl))) return rc;
-    launch_beam_ctc(cur_inv(h).out_all_dev, (int)h->out_all.size(), out, d_fl, N, T, beam_width, n_best,
-                    (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores, hyp_counts, s);
+    if ((rc = upload_frame_lengths(h, frame_lengths, N, T, s, &a.frame_lengths))) return rc;
+    beam_search(&a, beam_width, n_best, flags, workspace, tokens, timesteps, counts, scores, hyp_counts);
+    launch_beam_ctc(a, s);
     return ctc_launched(h, "beam-search");
 }
 
@@ -2409,19 +2440,16 @@ extern "C" int amx_beam_ctc_emissions(int device, const float* emissions, int64_
                                       int64_t* timesteps, int32_t* counts, double* scores, int32_t* hyp_counts, void* stream) {
     if (int rc = beam_check(nullptr, beam_width, n_best, flags)) return rc;
     if (int rc = beam_check_classes(nullptr, C)) return rc;
-    if (blank_index < 0 || blank_index >= C) return fail(nullptr, AMX_EINVAL, "blank_index out of range");
-    if (N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative emission geometry");
-    if (T > INT32_MAX) return fail(nullptr, AMX_EINVAL, "too many frames");
+    if (int rc = beam_check_blank(C, blank_index)) return rc;
+    if (int rc = beam_check_geometry(N, T)) return rc;
     if (N == 0) return AMX_OK;
     if (!emissions || !frame_lengths || !tokens || !timesteps || !counts || !scores || !hyp_counts)
         return fail(nullptr, AMX_EINVAL, "null buffer");
-    size_t need = 0;
-    amx_beam_ctc_workspace(beam_width, N, T, &need);
-    if (int rc = check_workspace(nullptr, "beam-search", need, workspace, workspace_bytes)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
-    launch_beam_ctc_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, beam_width, n_best,
-                              (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, (uint32_t*)workspace, tokens, timesteps, counts, scores,
-                              hyp_counts, (hipStream_t)stream);
+    if (int rc = beam_tensor_begin(device, beam_width, N, T, workspace, workspace_bytes)) return rc;
+    BeamArgs a{};
+    beam_tensor(&a, emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    beam_search(&a, beam_width, n_best, flags, workspace, tokens, timesteps, counts, scores, hyp_counts);
+    launch_beam_ctc_emissions(a, (hipStream_t)stream);
     return ctc_launched(nullptr, "beam-search");
 }
 
@@ -2439,21 +2467,19 @@ extern "C" int amx_beam_ctc_lm_emissions(int device, const float* emissions, int
     if (C < 2 || C > AMX_BEAM_LM_MAX_CLASSES)
         return fail(nullptr, AMX_EINVAL, "beam search with a language model needs 2 to " + std::to_string(AMX_BEAM_LM_MAX_CLASSES) +
                                              " classes, got " + std::to_string(C));
-    if (blank_index < 0 || blank_index >= C) return fail(nullptr, AMX_EINVAL, "blank_index out of range");
+    if (int rc = beam_check_blank(C, blank_index)) return rc;
     if (n_lm < 1) return fail(nullptr, AMX_EINVAL, "n_lm must be at least 1, got " + std::to_string(n_lm));
     if (!std::isfinite(lm_weight) || !std::isfinite(token_score)) return fail(nullptr, AMX_EINVAL, "lm_weight and token_score must be finite");
-    if (N < 0 || T < 0) return fail(nullptr, AMX_EINVAL, "negative emission geometry");
-    if (T > INT32_MAX) return fail(nullptr, AMX_EINVAL, "too many frames");
+    if (int rc = beam_check_geometry(N, T)) return rc;
     if (N == 0) return AMX_OK;
     if (!emissions || !frame_lengths || !lm || !lm_index || !tokens || !timesteps || !counts || !scores || !hyp_counts)
         return fail(nullptr, AMX_EINVAL, "null buffer");
-    size_t need = 0;
-    amx_beam_ctc_workspace(beam_width, N, T, &need);
-    if (int rc = check_workspace(nullptr, "beam-search", need, workspace, workspace_bytes)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, AMX_EHIP, "hipSetDevice failed");
-    launch_beam_ctc_lm_emissions(emissions, stride_n, stride_t, frame_lengths, N, (int)T, C, blank_index, beam_width, n_best,
-                                 (flags & AMX_BEAM_EXP_EMISSIONS) ? 1 : 0, lm, n_lm, lm_index, lm_weight, token_score,
-                                 (uint32_t*)workspace, tokens, timesteps, counts, scores, hyp_counts, (hipStream_t)stream);
+    if (int rc = beam_tensor_begin(device, beam_width, N, T, workspace, workspace_bytes)) return rc;
+    BeamLmArgs a{};
+    beam_tensor(&a, emissions, stride_n, stride_t, frame_lengths, N, T, C, blank_index);
+    beam_search(&a, beam_width, n_best, flags, workspace, tokens, timesteps, counts, scores, hyp_counts);
+    a.lm = lm, a.n_lm = n_lm, a.lm_index = lm_index, a.lm_weight = lm_weight, a.token_score = token_score;
+    launch_beam_ctc_lm_emissions(a, (hipStream_t)stream);
     return ctc_launched(nullptr, "beam-search");
 }
 

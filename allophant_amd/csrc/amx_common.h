@@ -561,24 +561,39 @@ void launch_greedy_ctc_emissions(const float* emissions, int64_t stride_n, int64
 
 // CTC prefix beam search (amx_ctc_beam.hip), one workgroup per row: the reference's BeamCTCDecoder (lexicon-free, no LM).
 // Per row: tokens / timesteps int64 [n_best, T], counts int32 [n_best], scores fp64 [n_best], hyp_counts int32; the workspace
-// holds a uint32 backpointer per (row, frame, slot), rows x T x beam.  launch_beam_ctc decodes every output block of `out`
-// (rows o * N + n, blank 0), launch_beam_ctc_emissions one [N, T, C] tensor read with element strides (stride_n, stride_t, 1).
+// holds a uint32 backpointer per (row, frame, slot), rows x T x beam.  The emission source is that of a CtcRows, below, in
+// one of two forms.  launch_beam_ctc: `emissions` is the output buffer, of which the n_out output blocks of `descs` are
+// decoded (rows o * N + n; each block has its own class count and blank 0, so C, blank and the strides are not read).
+// launch_beam_ctc_emissions: the N utterances of one [N, T, C] tensor read with element strides (stride_n, stride_t, 1);
+// descs and n_out are not read.
 // Limits (checked by the callers): 1 <= n_best <= beam <= BEAM_MAX, 2 <= C <= 65535.
 constexpr int BEAM_MAX = 64;
 constexpr int BEAM_MAX_CLASSES = 65535;
-void launch_beam_ctc(const OutDesc* descs_dev, int n_out, const float* out, const int* frame_len, int N, int T, int beam, int n_best,
-                     int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps, int* counts, double* scores, int* hyp_counts,
-                     hipStream_t s);
-void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
-                               int blank, int beam, int n_best, int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps,
-                               int* counts, double* scores, int* hyp_counts, hipStream_t s);
+struct BeamArgs {
+    const float* emissions;
+    int64_t stride_n, stride_t;
+    const OutDesc* descs;
+    const int32_t* frame_lengths;
+    int n_out, N, T, C, blank;
+    int beam, n_best, exp_mode;
+    uint32_t* workspace;
+    int64_t *tokens, *timesteps;
+    int32_t* counts;
+    double* scores;
+    int32_t* hyp_counts;
+};
+void launch_beam_ctc(const BeamArgs& a, hipStream_t s);
+void launch_beam_ctc_emissions(const BeamArgs& a, hipStream_t s);
 // The same search with shallow fusion of a bigram table (amx_ctc_beam_lm.hip): lm fp32 [n_lm, C + 1, C + 1], lm_index int32
 // [N] on the device (-1: the row runs without a table).  Limits as above, and C <= BEAM_LM_MAX_CLASSES.
 constexpr int BEAM_LM_MAX_CLASSES = 4095;
-void launch_beam_ctc_lm_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
-                                  int blank, int beam, int n_best, int exp_mode, const float* lm, int n_lm, const int* lm_index,
-                                  double lm_weight, double token_score, uint32_t* ws, int64_t* tokens, int64_t* timesteps, int* counts,
-                                  double* scores, int* hyp_counts, hipStream_t s);
+struct BeamLmArgs : BeamArgs {
+    const float* lm;
+    int n_lm;
+    const int32_t* lm_index;
+    double lm_weight, token_score;
+};
+void launch_beam_ctc_lm_emissions(const BeamLmArgs& a, hipStream_t s);
 
 // The call frame that CTC forced alignment and forward-backward scoring share (device half in amx_ctc_row.inc): where the
 // emissions lie and which target rows are run over them.  With `descs` the emissions are every output block of the output

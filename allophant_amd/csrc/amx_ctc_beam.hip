@@ -3,40 +3,19 @@
 // every token considered per frame.  The contract restated from flashlight's LexiconFreeDecoder is in DESIGN 9 and, as
 // executable code, in tests/ctc_beam_util.py; this kernel must match that restatement.
 //
-// One workgroup decodes one (output, utterance) row.  A state is (prefix P, last frame token k, prevBlank b) with an fp64
-// score.  Per frame every (state, token) pair yields one candidate; candidates below best - 50 are dropped, equal keys merge
-// by log-add (members folded in descending order, the merged state keeps the path of its highest member), and the
-// beam_width best merged candidates survive.  Prefixes are identified by a 64-bit hash h' = mix(h, n): a collision between
-// two prefixes of one beam is treated as impossible (2^-64 per pair and frame).
+// One workgroup decodes one (output, utterance) row.  States, candidates, merging, the tie order, backpointers and the end
+// step are described in amx_ctc_beam.inc, which holds what this decoder shares with the one that fuses a language model
+// (amx_ctc_beam_lm.hip).
 //
-// Candidate reduction.  Only two states share a prefix, (P, last(P), false) and (P, blank, true), so merge groups are small:
-//   plain    (P+n, n, false) from the <= 2 states of P eligible for n (n != blank, n != k or b)
-//   blank    (P, blank, true) from the <= 2 states of P
-//   repeat   (P, k, false) from the state itself (k != blank, !b) plus the states of P[:-1] eligible for k
-// Every state adds the same e[t, n], so within one prefix the plain candidates are monotone in e[t, n].  The frame's top
-// beam_width + 2 tokens are taken by (emission as added, then lower index).  A token outside them has beam_width + 2
-// tokens ahead of it in that order; leaving out blank and last(P) (whose candidates may lie below), beam_width tokens m
-// remain whose extension P+m is at least as high.  Where P+m is not a beam state it is a plain candidate of the same
-// leader and, at an equal score, has the lower token.  Where it is a beam state the repeat candidate of that state holds
-// it, and repeat candidates come first in candidate order -- they must: such a repeat can equal the plain score exactly
-// (a state 37 or more below the extension vanishes in the log-add) and would otherwise lose that tie to the token off the
-// list.  So the unlisted token's plain candidate has beam_width candidates ahead of it and is not enumerated.  Plain
-// candidates whose key is a repeat (P+n already a beam state) are dropped; the repeat holds them.
-// That leaves at most B * (B + 4) candidates per frame, whose top B are found exactly by a radix select over their
-// order-preserving 64-bit keys and compacted in index order.
+// Candidate reduction.  Every state adds the same e[t, n], so within one prefix the plain candidates are monotone in
+// e[t, n], and one list serves all prefixes: the frame's top beam_width + 2 tokens by (emission as added, then lower
+// index).  A token outside them has beam_width + 2 tokens ahead of it in that order; leaving out blank and last(P) (whose
+// candidates may lie below), beam_width tokens m remain whose extension P+m is at least as high.  Where P+m is not a beam
+// state it is a plain candidate of the same leader and, at an equal score, has the lower token.  Where it is a beam state
+// the repeat candidate of that state holds it, and repeat candidates come first in candidate order.  So the unlisted
+// token's plain candidate has beam_width candidates ahead of it and is not enumerated.
 //
-// Tie order (the rule of DESIGN 9, which tests/ctc_beam_util.py restates without reference to this file).  Candidate
-// index is (kind, slot, token): one repeat candidate per state at its slot j, then the plain candidates of leader L (the
-// lowest slot of its prefix) at nS + L * KS + p with the list in class order, then one blank candidate per leader.  Equal
-// scores resolve by lower candidate index, and the survivors take the new slots in index order, not in score order.
-// Equal members of a merged candidate resolve in push order (fold keeps the first of equal ones): leader before partner,
-// and for a repeat the state itself, then the leader of P[:-1], then its partner.  The end step ranks equal merged scores
-// by lower leader slot.  Frames with no finite emission, and NaN, are outside the contract.
-//
-// A backpointer (parent slot << 16 | frame token) per (frame, slot) goes to a caller-supplied workspace; the end step
-// merges by prefix, ranks, and traces the n-best paths back into tokens and 1-based timesteps.
-//
-// What this decoder shares with the one that fuses a language model (amx_ctc_beam_lm.hip) is in amx_ctc_beam.inc.
+// The frame's best, for the threshold of 50, is the maximum over all (state, token) of s + e = max s + max e.
 #include "amx_common.h"
 
 namespace amx {
@@ -45,9 +24,7 @@ namespace {
 
 #include "amx_ctc_beam.inc"
 
-constexpr int BM_KMAX = BEAM_MAX + 2;                  // tokens considered for plain extensions per frame
-constexpr int BM_MMAX = BEAM_MAX * (BM_KMAX + 2);      // candidates per frame: repeat, plain, blank
-constexpr int BM_TILE = BM_MMAX - BM_KMAX;             // classes whose keys are staged at a time for the token list
+constexpr int BM_TILE = BM_MMAX - BM_KMAX;  // classes whose keys are staged at a time for the token list
 
 struct BeamSmem {
     uint64_t key[BM_MMAX];  // candidate keys of the frame (0 = no candidate): the merged fp64 score, order-preserving;
@@ -74,61 +51,24 @@ struct BeamSmem {
     double e0, cut;
 };
 
-// Members of candidate i (see the header comment for the layout): their scores x and state slots, after the threshold.
-__device__ __forceinline__ Members members(const BeamSmem& sm, int cur, int nS, int KS, int blank, int i, int* token) {
-    Members g;
-    g.m = 0;
-    const double cut = sm.cut;
-    if (i >= nS && i < nS + nS * KS) {
-        const int L = (i - nS) / KS, p = (i - nS) - L * KS;
-        const int n = sm.S[p];
-        *token = n;
-        if (sm.leader[L] != L || n == blank) return g;
-        const double e = sm.Se[p];
-        const int q = sm.partner[L];
-        if (n != sm.tk[cur][L] || sm.pb[cur][L]) {
-            const double v = sm.sc[cur][L] + e;
-            if (v >= cut) g.push(v, L);
-        }
-        if (q >= 0 && (n != sm.tk[cur][q] || sm.pb[cur][q])) {
-            const double v = sm.sc[cur][q] + e;
-            if (v >= cut) g.push(v, q);
-        }
-    } else if (i >= nS) {
-        const int L = i - nS - nS * KS;
-        *token = blank;
-        if (sm.leader[L] != L) return g;
-        const double e = sm.e0;
-        const int q = sm.partner[L];
-        double v = sm.sc[cur][L] + e;
-        if (v >= cut) g.push(v, L);
-        if (q >= 0) {
-            v = sm.sc[cur][q] + e;
-            if (v >= cut) g.push(v, q);
-        }
-    } else {
-        const int j = i;
-        const int n = sm.tk[cur][j];
-        *token = n;
-        if (n == blank || sm.pb[cur][j]) return g;
-        const double e = sm.ek[j];
-        double v = sm.sc[cur][j] + e;
-        if (v >= cut) g.push(v, j);
-        const int P = sm.parent[j];
-        if (P >= 0) {
-            if (n != sm.tk[cur][P] || sm.pb[cur][P]) {
-                v = sm.sc[cur][P] + e;
-                if (v >= cut) g.push(v, P);
-            }
-            const int q = sm.partner[P];
-            if (q >= 0 && (n != sm.tk[cur][q] || sm.pb[cur][q])) {
-                v = sm.sc[cur][q] + e;
-                if (v >= cut) g.push(v, q);
-            }
-        }
+// The decoder policy (amx_ctc_beam.inc).  What a new token adds: its emission, from the frame's one list (which may hold
+// the blank).
+struct PlainDecoder {
+    struct Term {
+        double e;
+    };
+    static __device__ __forceinline__ bool plain(const BeamSmem& sm, int L, int p, int blank, int* n, Term* x) {
+        *n = sm.S[p];
+        if (sm.leader[L] != L || *n == blank) return false;
+        x->e = sm.Se[p];
+        return true;
     }
-    return g;
-}
+    static __device__ __forceinline__ Term repeat(const BeamSmem&, int, double e) { return {e}; }
+    static __device__ __forceinline__ double add(double s, Term x) { return s + x.e; }
+    // the end step: a state's end total is its score, and every state takes part
+    static __device__ __forceinline__ double total(const BeamSmem& sm, int cur, int slot) { return sm.sc[cur][slot]; }
+    static __device__ __forceinline__ bool ends(double) { return true; }
+};
 
 // One row: frame t's C emissions at row + t * stride_t.  Outputs: tokens / timesteps [n_best, T], counts / scores [n_best],
 // *hyp_count; bp [T, beam] of the workspace.
@@ -225,8 +165,8 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
         const int M = nS * (KS + 2);
         int valid = 0;
         for (int i = tid; i < M; i += BM_THREADS) {
-            int tok, best;
-            const Members g = members(sm, cur, nS, KS, blank, i, &tok);
+            int best;
+            const Members g = members<PlainDecoder>(sm, cur, nS, KS, blank, sm.cut, i);
             uint64_t k = 0;
             if (g.m) {
                 k = key64(fold(g, &best));
@@ -237,31 +177,7 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
         }
         if (valid) atomicAdd(&sm.nvalid, valid);
         __syncthreads();
-        // 5. a plain candidate onto a prefix already in the beam is that state's repeat candidate
-        if (tid < nS && sm.parent[tid] >= 0 && sm.childp[tid] >= 0) {
-            const int i = nS + sm.parent[tid] * KS + sm.childp[tid];
-            if (sm.key[i]) {
-                sm.key[i] = 0;
-                atomicSub(&sm.nvalid, 1);
-            }
-        }
-        __syncthreads();
-        // 6. the top `beam` candidates, index order
-        const int nvalid = sm.nvalid;
-        const int nW = min(beam, nvalid);
-        auto ckey = [&](int i) -> uint64_t { return sm.key[i]; };
-        if (nvalid > beam) {
-            radix_select<uint64_t, 64>(M, beam, ckey, sm);
-        } else {
-            if (tid == 0) {
-                sm.sel_prefix = 0;
-                sm.sel_mask = ~0ull;
-                sm.sel_take = 0;
-            }
-            __syncthreads();
-        }
-        compact<uint64_t>(M, beam, ckey, [&](int pos, int i) { sm.win[pos] = i; }, sm);
-        __syncthreads();
+        const int nW = select_candidates(sm, nS, KS, beam);  // steps 5 and 6
         // 7. the new states and their backpointers
         const int nxt = cur ^ 1;
         if (tid < nW) {
@@ -297,69 +213,14 @@ __device__ __forceinline__ void beam_row(const float* __restrict__ row, int64_t 
     }
 
     // End: every state becomes (P, blank, false, s); threshold against the best state; merge by prefix; rank.
-    if (tid < nS) {
-        const uint64_t h = sm.hs[cur][tid];
-        int ld = tid, pt = -1;
-        for (int j = 0; j < nS; ++j)
-            if (sm.hs[cur][j] == h) {
-                if (j < ld) ld = j;
-                if (j != tid) pt = j;
-            }
-        sm.leader[tid] = ld;
-        sm.partner[tid] = pt;
-    }
+    group_prefixes(sm, cur, nS);
     if (tid < 64) {
         double s = tid < nS ? sm.sc[cur][tid] : -INFINITY;
         s = wave_max_f64(s);
         if (tid == 0) sm.cut = s - BM_THRESHOLD;
     }
     __syncthreads();
-    // merged value of each leader in sm.ek, its best member in sm.childp
-    if (tid < nS) {
-        double v = -INFINITY;
-        int bs = tid, valid = 0;
-        if (sm.leader[tid] == tid) {
-            Members g;
-            g.m = 0;
-            int best;
-            if (sm.sc[cur][tid] >= sm.cut) g.push(sm.sc[cur][tid], tid);
-            const int q = sm.partner[tid];
-            if (q >= 0 && sm.sc[cur][q] >= sm.cut) g.push(sm.sc[cur][q], q);
-            if (g.m) {
-                v = fold(g, &best);
-                bs = best;
-                valid = 1;
-            }
-        }
-        sm.ek[tid] = v;
-        sm.childp[tid] = bs;
-        sm.parent[tid] = valid;
-    }
-    __syncthreads();
-    if (tid < nS && sm.parent[tid]) {
-        const double v = sm.ek[tid];
-        int rank = 0;
-        for (int j = 0; j < nS; ++j)
-            if (sm.parent[j] && (sm.ek[j] > v || (sm.ek[j] == v && j < tid))) ++rank;
-        if (rank < n_best) {
-            sm.win[rank] = sm.childp[tid];
-            scores[rank] = v;
-        }
-    }
-    if (tid < 64) {
-        int g = tid < nS ? sm.parent[tid] : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o, 64);
-        if (tid == 0) sm.nvalid = min(g, n_best);
-    }
-    __syncthreads();
-    const int nh = sm.nvalid;
-    if (tid == 0) *hyp_count = nh;
-    if (tid >= nh && tid < n_best) {
-        counts[tid] = 0;
-        scores[tid] = -INFINITY;
-    }
-    trace_and_collapse(nh, len, T, beam, blank, bp, tokens, timesteps, counts, sm);
+    end_merge<PlainDecoder>(sm, cur, nS, sm.cut, n_best, len, T, beam, blank, bp, tokens, timesteps, counts, scores, hyp_count);
 }
 
 __global__ __launch_bounds__(BM_THREADS) void beam_ctc_kernel(const OutDesc* __restrict__ descs, const float* __restrict__ out,
@@ -390,18 +251,15 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_emissions_kernel(
 
 }  // namespace
 
-void launch_beam_ctc(const OutDesc* descs_dev, int n_out, const float* out, const int* frame_len, int N, int T, int beam, int n_best,
-                     int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps, int* counts, double* scores, int* hyp_counts,
-                     hipStream_t s) {
-    hipLaunchKernelGGL(beam_ctc_kernel, dim3(N, n_out), dim3(BM_THREADS), 0, s, descs_dev, out, frame_len, N, T, beam, n_best,
-                       exp_mode, ws, tokens, timesteps, counts, scores, hyp_counts);
+void launch_beam_ctc(const BeamArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(beam_ctc_kernel, dim3(a.N, a.n_out), dim3(BM_THREADS), 0, s, a.descs, a.emissions, a.frame_lengths, a.N, a.T,
+                       a.beam, a.n_best, a.exp_mode, a.workspace, a.tokens, a.timesteps, a.counts, a.scores, a.hyp_counts);
 }
 
-void launch_beam_ctc_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
-                               int blank, int beam, int n_best, int exp_mode, uint32_t* ws, int64_t* tokens, int64_t* timesteps,
-                               int* counts, double* scores, int* hyp_counts, hipStream_t s) {
-    hipLaunchKernelGGL(beam_ctc_emissions_kernel, dim3(N), dim3(BM_THREADS), 0, s, emissions, stride_n, stride_t, frame_len, T, C,
-                       blank, beam, n_best, exp_mode, ws, tokens, timesteps, counts, scores, hyp_counts);
+void launch_beam_ctc_emissions(const BeamArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(beam_ctc_emissions_kernel, dim3(a.N), dim3(BM_THREADS), 0, s, a.emissions, a.stride_n, a.stride_t,
+                       a.frame_lengths, a.T, a.C, a.blank, a.beam, a.n_best, a.exp_mode, a.workspace, a.tokens, a.timesteps,
+                       a.counts, a.scores, a.hyp_counts);
 }
 
 }  // namespace amx

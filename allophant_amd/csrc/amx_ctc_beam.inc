@@ -1,14 +1,50 @@
 // What the two CTC beam-search kernels share (amx_ctc_beam.hip, the decoder without a language model, and
-// amx_ctc_beam_lm.hip, the one with a phonotactic bigram): prefix hashes, the order-preserving key images, the merge of a
-// group's members, the workgroup scan, the exact radix select with its compaction, and the end step's trace and collapse.
-// Included inside namespace amx { namespace { ... } } by each of them.  The templates take the including file's
-// shared-memory struct `Smem`, of which they use: int hist[256], int wtmp[BM_WAVES], uint64_t sel_prefix, sel_mask,
-// int sel_take, sel_done, int win[], int carry[2].
+// amx_ctc_beam_lm.hip, the one with a phonotactic bigram): prefix hashes, the order-preserving key images, the grouping
+// of states by prefix, the members of a candidate and their merge, the workgroup scan, the exact radix select with its
+// compaction, steps 5 and 6 of a frame, and the end step behind its threshold with the trace and collapse.  Included
+// inside namespace amx { namespace { ... } } by each of them.  The templates take the including file's shared-memory
+// struct `Smem`, of which they use the per-state fields (sc hs ph tk pb partner leader parent childp ek) and the frame's
+// candidates and scratch (key par win hist wtmp sel_* nvalid carry e0); the two structs hold these fields in different
+// orders, each the one its kernel's register allocation was found with.  What differs between the decoders the templates
+// take as a decoder policy `D`, all static and inlined, so that the decoder without a language model carries none of the
+// other's terms (see members and end_merge).  Each kernel keeps its own LDS struct, token lists, threshold, step 4's
+// loop and step 7: written as shared functions these change the kernels' frame loops, and the loops as they are
+// compile to the instructions they had before anything was shared.
+//
+// A state is (prefix P, last frame token k, prevBlank b) with an fp64 score.  Per frame every (state, token) pair yields
+// one candidate; candidates below best - 50 are dropped, equal keys merge by log-add (members folded in descending order,
+// the merged state keeps the path of its highest member), and the beam_width best merged candidates survive.  Prefixes are
+// identified by a 64-bit hash h' = mix(h, n): a collision between two prefixes of one beam is treated as impossible
+// (2^-64 per pair and frame).
+//
+// Candidates.  Only two states share a prefix, (P, last(P), false) and (P, blank, true), so merge groups are small:
+//   repeat   (P, k, false) from the state itself (k != blank, !b) plus the states of P[:-1] eligible for k
+//   plain    (P+n, n, false) from the <= 2 states of P eligible for n (n != blank, n != k or b)
+//   blank    (P, blank, true) from the <= 2 states of P
+// Plain candidates are enumerated for the tokens of a list of KS = min(beam_width + 2, C) only; why no other token can
+// survive is each decoder's own argument, at the head of its file.  Plain candidates whose key is a repeat (P+n already a
+// beam state) are dropped; the repeat holds them.  That leaves at most B * (B + 4) candidates per frame, whose top B are
+// found exactly by a radix select over their order-preserving 64-bit keys and compacted in index order.
+//
+// Tie order (the rule of DESIGN 9, which tests/ctc_beam_util.py restates without reference to the kernels).  Candidate
+// index is (kind, slot, token): one repeat candidate per state at its slot j, then the plain candidates of leader L (the
+// lowest slot of its prefix) at nS + L * KS + p with the list in class order, then one blank candidate per leader.  Repeat
+// candidates come first because they must: such a repeat can equal the plain score of a token off the list exactly (a
+// state 37 or more below the extension vanishes in the log-add) and would otherwise lose that tie to it.  Equal scores
+// resolve by lower candidate index, and the survivors take the new slots in index order, not in score order.  Equal
+// members of a merged candidate resolve in push order (fold keeps the first of equal ones): leader before partner, and
+// for a repeat the state itself, then the leader of P[:-1], then its partner.  The end step ranks equal merged scores by
+// lower leader slot.  Frames with no finite emission, and NaN, are outside the contract.
+//
+// A backpointer (parent slot << 16 | frame token) per (frame, slot) goes to a caller-supplied workspace; the end step
+// merges by prefix, ranks, and traces the n-best paths back into tokens and 1-based timesteps.
 
 constexpr int BM_THREADS = 256;
 constexpr int BM_WAVES = BM_THREADS / 64;
 constexpr double BM_THRESHOLD = 50.0;                   // torchaudio's beam_threshold default
 constexpr uint64_t BM_ROOT = 0x6a09e667f3bcc908ull;     // hash of the empty prefix
+constexpr int BM_KMAX = BEAM_MAX + 2;                   // list length: tokens considered for plain extensions
+constexpr int BM_MMAX = BEAM_MAX * (BM_KMAX + 2);       // candidates per frame: repeat, plain, blank
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     z += 0x9e3779b97f4a7c15ull;
@@ -69,6 +105,80 @@ __device__ __forceinline__ double fold(Members g, int* best) {
     for (int r = 1; r < g.m; ++r) acc = logadd(acc, r == 1 ? b : c);
     *best = sa;
     return acc;
+}
+
+// leader (lowest slot) and partner (the other state) of every state's prefix
+template <typename Smem>
+__device__ __forceinline__ void group_prefixes(Smem& sm, int cur, int nS) {
+    const int tid = threadIdx.x;
+    if (tid < nS) {
+        const uint64_t h = sm.hs[cur][tid];
+        int ld = tid, pt = -1;
+        for (int j = 0; j < nS; ++j)
+            if (sm.hs[cur][j] == h) {
+                if (j < ld) ld = j;
+                if (j != tid) pt = j;
+            }
+        sm.leader[tid] = ld;
+        sm.partner[tid] = pt;
+    }
+}
+
+// Members of candidate i, in (repeat, plain, blank) order: their scores and state slots, after the threshold.  What a
+// new token adds is the decoder's: D::Term, D::plain(sm, L, p, blank, &n, &x) (false: leader L has no plain candidate at
+// list position p; else its token n and term x), D::repeat(sm, j) (the term of P[:-1] emitting k, for the repeat
+// candidate of state j) and D::add(s, x), the score s after x.
+template <typename D, typename Smem>
+__device__ __forceinline__ Members members(const Smem& sm, int cur, int nS, int KS, int blank, double cut, int i) {
+    Members g;
+    g.m = 0;
+    if (i >= nS && i < nS + nS * KS) {
+        const int L = (i - nS) / KS, p = (i - nS) - L * KS;
+        int n;
+        typename D::Term x;
+        if (!D::plain(sm, L, p, blank, &n, &x)) return g;
+        const int q = sm.partner[L];
+        if (n != sm.tk[cur][L] || sm.pb[cur][L]) {
+            const double v = D::add(sm.sc[cur][L], x);
+            if (v >= cut) g.push(v, L);
+        }
+        if (q >= 0 && (n != sm.tk[cur][q] || sm.pb[cur][q])) {
+            const double v = D::add(sm.sc[cur][q], x);
+            if (v >= cut) g.push(v, q);
+        }
+    } else if (i >= nS) {
+        const int L = i - nS - nS * KS;
+        if (sm.leader[L] != L) return g;
+        const double e = sm.e0;
+        const int q = sm.partner[L];
+        double v = sm.sc[cur][L] + e;
+        if (v >= cut) g.push(v, L);
+        if (q >= 0) {
+            v = sm.sc[cur][q] + e;
+            if (v >= cut) g.push(v, q);
+        }
+    } else {
+        const int j = i;
+        const int n = sm.tk[cur][j];
+        if (n == blank || sm.pb[cur][j]) return g;
+        const double e = sm.ek[j];
+        double v = sm.sc[cur][j] + e;
+        if (v >= cut) g.push(v, j);
+        const int P = sm.parent[j];
+        if (P >= 0) {
+            const typename D::Term x = D::repeat(sm, j, e);
+            if (n != sm.tk[cur][P] || sm.pb[cur][P]) {
+                v = D::add(sm.sc[cur][P], x);
+                if (v >= cut) g.push(v, P);
+            }
+            const int q = sm.partner[P];
+            if (q >= 0 && (n != sm.tk[cur][q] || sm.pb[cur][q])) {
+                v = D::add(sm.sc[cur][q], x);
+                if (v >= cut) g.push(v, q);
+            }
+        }
+    }
+    return g;
 }
 
 // exclusive prefix sum over the workgroup in thread order
@@ -240,4 +350,96 @@ __device__ __forceinline__ void trace_and_collapse(int nh, int len, int T, int b
         if (tid == 0) counts[r] = pos_base;
         __syncthreads();
     }
+}
+
+// Steps 5 and 6 of a frame, behind the barrier that follows the candidate keys (sm.key, sm.nvalid of them valid): the
+// move of a plain candidate onto a beam state to that state's repeat candidate, and the `beam` best, whose candidate
+// indices go to sm.win in index order.  Returns the number of survivors; ends with a barrier.
+template <typename Smem>
+__device__ __forceinline__ int select_candidates(Smem& sm, int nS, int KS, int beam) {
+    const int tid = threadIdx.x;
+    const int M = nS * (KS + 2);
+    // 5. a plain candidate onto a prefix already in the beam is that state's repeat candidate
+    if (tid < nS && sm.parent[tid] >= 0 && sm.childp[tid] >= 0) {
+        const int i = nS + sm.parent[tid] * KS + sm.childp[tid];
+        if (sm.key[i]) {
+            sm.key[i] = 0;
+            atomicSub(&sm.nvalid, 1);
+        }
+    }
+    __syncthreads();
+    // 6. the top `beam` candidates, index order
+    const int nvalid = sm.nvalid;
+    const int nW = min(beam, nvalid);
+    auto ckey = [&](int i) -> uint64_t { return sm.key[i]; };
+    if (nvalid > beam) {
+        radix_select<uint64_t, 64>(M, beam, ckey, sm);
+    } else {
+        if (tid == 0) {
+            sm.sel_prefix = 0;
+            sm.sel_mask = ~0ull;
+            sm.sel_take = 0;
+        }
+        __syncthreads();
+    }
+    compact<uint64_t>(M, beam, ckey, [&](int pos, int i) { sm.win[pos] = i; }, sm);
+    __syncthreads();
+    return nW;
+}
+
+// The end step behind its threshold `cut`: merges the states by prefix (leader and partner as group_prefixes left them,
+// D::total(sm, cur, slot) a state's end total, D::ends(total) whether it takes part), ranks the merged totals, counts the
+// hypotheses, fills the unused counts and scores, and traces the n_best first.
+template <typename D, typename Smem>
+__device__ __forceinline__ void end_merge(Smem& sm, int cur, int nS, const double& cut, int n_best, int len, int T, int beam, int blank,
+                                          const uint32_t* __restrict__ bp, int64_t* __restrict__ tokens,
+                                          int64_t* __restrict__ timesteps, int* __restrict__ counts, double* __restrict__ scores,
+                                          int* __restrict__ hyp_count) {
+    const int tid = threadIdx.x;
+    // merged value of each leader in sm.ek, its best member in sm.childp
+    if (tid < nS) {
+        double v = -INFINITY;
+        int bs = tid, valid = 0;
+        if (sm.leader[tid] == tid) {
+            Members g;
+            g.m = 0;
+            int best;
+            if (D::ends(D::total(sm, cur, tid)) && D::total(sm, cur, tid) >= cut) g.push(D::total(sm, cur, tid), tid);
+            const int q = sm.partner[tid];
+            if (q >= 0 && D::ends(D::total(sm, cur, q)) && D::total(sm, cur, q) >= cut) g.push(D::total(sm, cur, q), q);
+            if (g.m) {
+                v = fold(g, &best);
+                bs = best;
+                valid = 1;
+            }
+        }
+        sm.ek[tid] = v;
+        sm.childp[tid] = bs;
+        sm.parent[tid] = valid;
+    }
+    __syncthreads();
+    if (tid < nS && sm.parent[tid]) {
+        const double v = sm.ek[tid];
+        int rank = 0;
+        for (int j = 0; j < nS; ++j)
+            if (sm.parent[j] && (sm.ek[j] > v || (sm.ek[j] == v && j < tid))) ++rank;
+        if (rank < n_best) {
+            sm.win[rank] = sm.childp[tid];
+            scores[rank] = v;
+        }
+    }
+    if (tid < 64) {
+        int g = tid < nS ? sm.parent[tid] : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o, 64);
+        if (tid == 0) sm.nvalid = min(g, n_best);
+    }
+    __syncthreads();
+    const int nh = sm.nvalid;
+    if (tid == 0) *hyp_count = nh;
+    if (tid >= nh && tid < n_best) {
+        counts[tid] = 0;
+        scores[tid] = -INFINITY;
+    }
+    trace_and_collapse(nh, len, T, beam, blank, bp, tokens, timesteps, counts, sm);
 }

@@ -2,7 +2,7 @@
 // an LM instead of ZeroLM): the decoder of amx_ctc_beam.hip, whose every new token n after a prefix P additionally costs
 // a = w * lm[last(P), n] + beta, and whose end step adds w * lm[last(P), end].  The contract is in DESIGN 9 and, as
 // executable code, in tests/ctc_beam_lm_util.py; this kernel must match that restatement.  States, merging, thresholds, the
-// end step, backpointers and outputs are those of amx_ctc_beam.hip (the shared pieces are in amx_ctc_beam.inc).
+// end step, backpointers and outputs are those of amx_ctc_beam.hip (described, with the shared pieces, in amx_ctc_beam.inc).
 //
 // One workgroup decodes one row under the table lm[lm_index[row]] ([C + 1, C + 1] fp32: row = previous token, C = begin;
 // column = next token, C = end; the blank's row and column are never read).  An index of -1 runs the row with a = 0 and no
@@ -15,11 +15,10 @@
 // that list has beam + 2 tokens of the same prefix ahead of it; leaving out last(P) (whose candidate may lie below), at
 // least beam tokens m remain whose extension P+m is at least as high: a plain candidate of the same leader with the lower
 // token, or, where P+m is a beam state, that state's repeat candidate, which comes first in candidate order (see
-// amx_ctc_beam.hip for why it must).  So the token's plain candidate cannot survive and is not enumerated.  Tie order is
-// that of amx_ctc_beam.hip (the rule of DESIGN 9): candidate index is (kind, slot, token) -- repeat, plain, blank -- with
-// each list in class order, equal members in push order, the end ranking by lower leader slot.
-// Plain candidates whose key is already a beam state go to that state's repeat candidate whether or not the token is in
-// the list (the third branch of members()).  That leaves at most B * (B + 4) candidates per frame, as without an LM.
+// amx_ctc_beam.inc for why it must, and for the tie order).  So the token's plain candidate cannot survive and is not
+// enumerated.  Plain candidates whose key is already a beam state go to that state's repeat candidate whether or not the
+// token is in the list (the repeat branch of members()).  That leaves at most B * (B + 4) candidates per frame, as
+// without an LM.
 //
 // The per-prefix selection is the hot loop: one wave per prefix, classes across lanes (the table row is read as contiguous
 // 4-byte values), in ONE pass over the classes.  A lane whose key beats the running threshold appends it to a per-wave
@@ -37,19 +36,17 @@ namespace {
 
 #include "amx_ctc_beam.inc"
 
-constexpr int BL_KMAX = BEAM_MAX + 2;               // list length per prefix
-constexpr int BL_MMAX = BEAM_MAX * (BL_KMAX + 2);   // candidates per frame: repeat, plain, blank
 constexpr int BL_WCAP = 192;                        // per-wave selection buffer: three keys per lane
 
 struct BeamLmSmem {
-    uint64_t key[BL_MMAX];            // candidate keys of the frame (0 = no candidate)
-    double la[BEAM_MAX][BL_KMAX];     // per prefix leader and list position: a = w * lm + beta
-    float le[BEAM_MAX][BL_KMAX];      //   the emission as added (an fp32 value in both modes)
-    uint16_t ltok[BEAM_MAX][BL_KMAX]; //   the token, class order
+    uint64_t key[BM_MMAX];            // candidate keys of the frame (0 = no candidate)
+    double la[BEAM_MAX][BM_KMAX];     // per prefix leader and list position: a = w * lm + beta
+    float le[BEAM_MAX][BM_KMAX];      //   the emission as added (an fp32 value in both modes)
+    uint16_t ltok[BEAM_MAX][BM_KMAX]; //   the token, class order
     uint64_t wk[BM_WAVES][BL_WCAP];   // per-wave selection buffer: keys of g_P, class order
     uint16_t wt[BM_WAVES][BL_WCAP];
     float ef[BEAM_LM_MAX_CLASSES + 1];  // the frame's emissions as added
-    uint8_t par[BL_MMAX];             // slot of the candidate's highest member
+    uint8_t par[BM_MMAX];             // slot of the candidate's highest member
     double sc[2][BEAM_MAX];
     uint64_t hs[2][BEAM_MAX];  // prefix hash
     uint64_t ph[2][BEAM_MAX];  // hash of the prefix without its last token (read for non-blank states only)
@@ -197,79 +194,24 @@ __device__ __forceinline__ void prefix_list(BeamLmSmem& sm, const float* __restr
     wave_sync();  // the buffer is free for the wave's next prefix
 }
 
-// Members of candidate i: one repeat candidate per state, then plain candidates i = nS + L * KS + p (leader L, list
-// position p), then one blank candidate per leader; their scores and state slots, after the threshold.
-__device__ __forceinline__ Members members(const BeamLmSmem& sm, int cur, int nS, int KS, int blank, double cut, int i, int* token) {
-    Members g;
-    g.m = 0;
-    if (i >= nS && i < nS + nS * KS) {
-        const int L = (i - nS) / KS, p = (i - nS) - L * KS;
-        *token = blank;
-        if (sm.leader[L] != L || p >= sm.nl[L]) return g;
-        const int n = sm.ltok[L][p];
-        *token = n;
-        const double e = (double)sm.le[L][p], a = sm.la[L][p];
-        const int q = sm.partner[L];
-        if (n != sm.tk[cur][L] || sm.pb[cur][L]) {
-            const double v = (sm.sc[cur][L] + e) + a;
-            if (v >= cut) g.push(v, L);
-        }
-        if (q >= 0 && (n != sm.tk[cur][q] || sm.pb[cur][q])) {
-            const double v = (sm.sc[cur][q] + e) + a;
-            if (v >= cut) g.push(v, q);
-        }
-    } else if (i >= nS) {
-        const int L = i - nS - nS * KS;
-        *token = blank;
-        if (sm.leader[L] != L) return g;
-        const double e = sm.e0;
-        const int q = sm.partner[L];
-        double v = sm.sc[cur][L] + e;
-        if (v >= cut) g.push(v, L);
-        if (q >= 0) {
-            v = sm.sc[cur][q] + e;
-            if (v >= cut) g.push(v, q);
-        }
-    } else {
-        const int j = i;
-        const int n = sm.tk[cur][j];
-        *token = n;
-        if (n == blank || sm.pb[cur][j]) return g;
-        const double e = sm.ek[j];
-        double v = sm.sc[cur][j] + e;
-        if (v >= cut) g.push(v, j);
-        const int P = sm.parent[j];
-        if (P >= 0) {
-            const double a = sm.ak[j];
-            if (n != sm.tk[cur][P] || sm.pb[cur][P]) {
-                v = (sm.sc[cur][P] + e) + a;
-                if (v >= cut) g.push(v, P);
-            }
-            const int q = sm.partner[P];
-            if (q >= 0 && (n != sm.tk[cur][q] || sm.pb[cur][q])) {
-                v = (sm.sc[cur][q] + e) + a;
-                if (v >= cut) g.push(v, q);
-            }
-        }
+// The decoder policy (amx_ctc_beam.inc).  What a new token adds: its emission and a, from the list of its prefix leader.
+struct LmDecoder {
+    struct Term {
+        double e, a;
+    };
+    static __device__ __forceinline__ bool plain(const BeamLmSmem& sm, int L, int p, int, int* n, Term* x) {
+        if (sm.leader[L] != L || p >= sm.nl[L]) return false;
+        *n = sm.ltok[L][p];
+        x->e = (double)sm.le[L][p];
+        x->a = sm.la[L][p];
+        return true;
     }
-    return g;
-}
-
-// leader (lowest slot) and partner (the other state) of every state's prefix
-__device__ __forceinline__ void group_prefixes(BeamLmSmem& sm, int cur, int nS) {
-    const int tid = threadIdx.x;
-    if (tid < nS) {
-        const uint64_t h = sm.hs[cur][tid];
-        int ld = tid, pt = -1;
-        for (int j = 0; j < nS; ++j)
-            if (sm.hs[cur][j] == h) {
-                if (j < ld) ld = j;
-                if (j != tid) pt = j;
-            }
-        sm.leader[tid] = ld;
-        sm.partner[tid] = pt;
-    }
-}
+    static __device__ __forceinline__ Term repeat(const BeamLmSmem& sm, int j, double e) { return {e, sm.ak[j]}; }
+    static __device__ __forceinline__ double add(double s, Term x) { return (s + x.e) + x.a; }
+    // the end step: the end totals are in sm.ak, -inf for a state that is dropped
+    static __device__ __forceinline__ double total(const BeamLmSmem& sm, int, int slot) { return sm.ak[slot]; }
+    static __device__ __forceinline__ bool ends(double x) { return x > -INFINITY; }
+};
 
 // workgroup maximum of v; every thread gets it
 __device__ __forceinline__ double block_max(double v, BeamLmSmem& sm) {
@@ -386,8 +328,8 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_lm_kernel(
         const int M = nS * (KS + 2);
         int valid = 0;
         for (int i = tid; i < M; i += BM_THREADS) {
-            int tok, bs;
-            const Members g = members(sm, cur, nS, KS, blank, cut, i, &tok);
+            int bs;
+            const Members g = members<LmDecoder>(sm, cur, nS, KS, blank, cut, i);
             uint64_t k = 0;
             if (g.m) {
                 k = key64(fold(g, &bs));
@@ -398,31 +340,7 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_lm_kernel(
         }
         if (valid) atomicAdd(&sm.nvalid, valid);
         __syncthreads();
-        // 5. a plain candidate onto a prefix already in the beam is that state's repeat candidate
-        if (tid < nS && sm.parent[tid] >= 0 && sm.childp[tid] >= 0) {
-            const int i = nS + sm.parent[tid] * KS + sm.childp[tid];
-            if (sm.key[i]) {
-                sm.key[i] = 0;
-                atomicSub(&sm.nvalid, 1);
-            }
-        }
-        __syncthreads();
-        // 6. the top `beam` candidates, index order
-        const int nvalid = sm.nvalid;
-        const int nW = min(beam, nvalid);
-        auto ckey = [&](int i) -> uint64_t { return sm.key[i]; };
-        if (nvalid > beam) {
-            radix_select<uint64_t, 64>(M, beam, ckey, sm);
-        } else {
-            if (tid == 0) {
-                sm.sel_prefix = 0;
-                sm.sel_mask = ~0ull;
-                sm.sel_take = 0;
-            }
-            __syncthreads();
-        }
-        compact<uint64_t>(M, beam, ckey, [&](int pos, int i) { sm.win[pos] = i; }, sm);
-        __syncthreads();
+        const int nW = select_candidates(sm, nS, KS, beam);  // steps 5 and 6
         // 7. the new states and their backpointers
         const int nxt = cur ^ 1;
         if (tid < nW) {
@@ -476,63 +394,15 @@ __global__ __launch_bounds__(BM_THREADS) void beam_ctc_lm_kernel(
         sm.ak[tid] = fin;
     }
     const double cut = block_max(fin, sm) - BM_THRESHOLD;
-    // merged value of each leader in sm.ek, its best member in sm.childp
-    if (tid < nS) {
-        double v = -INFINITY;
-        int bs = tid, valid = 0;
-        if (sm.leader[tid] == tid) {
-            Members g;
-            g.m = 0;
-            int best;
-            if (sm.ak[tid] > -INFINITY && sm.ak[tid] >= cut) g.push(sm.ak[tid], tid);
-            const int q = sm.partner[tid];
-            if (q >= 0 && sm.ak[q] > -INFINITY && sm.ak[q] >= cut) g.push(sm.ak[q], q);
-            if (g.m) {
-                v = fold(g, &best);
-                bs = best;
-                valid = 1;
-            }
-        }
-        sm.ek[tid] = v;
-        sm.childp[tid] = bs;
-        sm.parent[tid] = valid;
-    }
-    __syncthreads();
-    if (tid < nS && sm.parent[tid]) {
-        const double v = sm.ek[tid];
-        int rank = 0;
-        for (int j = 0; j < nS; ++j)
-            if (sm.parent[j] && (sm.ek[j] > v || (sm.ek[j] == v && j < tid))) ++rank;
-        if (rank < n_best) {
-            sm.win[rank] = sm.childp[tid];
-            scores[rank] = v;
-        }
-    }
-    if (tid < 64) {
-        int g = tid < nS ? sm.parent[tid] : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o, 64);
-        if (tid == 0) sm.nvalid = min(g, n_best);
-    }
-    __syncthreads();
-    const int nh = sm.nvalid;
-    if (tid == 0) hyp_counts[row_n] = nh;
-    if (tid >= nh && tid < n_best) {
-        counts[tid] = 0;
-        scores[tid] = -INFINITY;
-    }
-    trace_and_collapse(nh, len, T, beam, blank, bp, tokens, timesteps, counts, sm);
+    end_merge<LmDecoder>(sm, cur, nS, cut, n_best, len, T, beam, blank, bp, tokens, timesteps, counts, scores, hyp_counts + row_n);
 }
 
 }  // namespace
 
-void launch_beam_ctc_lm_emissions(const float* emissions, int64_t stride_n, int64_t stride_t, const int* frame_len, int N, int T, int C,
-                                  int blank, int beam, int n_best, int exp_mode, const float* lm, int n_lm, const int* lm_index,
-                                  double lm_weight, double token_score, uint32_t* ws, int64_t* tokens, int64_t* timesteps, int* counts,
-                                  double* scores, int* hyp_counts, hipStream_t s) {
-    hipLaunchKernelGGL(beam_ctc_lm_kernel, dim3(N), dim3(BM_THREADS), 0, s, emissions, stride_n, stride_t, frame_len, T, C, blank,
-                       beam, n_best, exp_mode, lm, n_lm, lm_index, lm_weight, token_score, ws, tokens, timesteps, counts, scores,
-                       hyp_counts);
+void launch_beam_ctc_lm_emissions(const BeamLmArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(beam_ctc_lm_kernel, dim3(a.N), dim3(BM_THREADS), 0, s, a.emissions, a.stride_n, a.stride_t, a.frame_lengths,
+                       a.T, a.C, a.blank, a.beam, a.n_best, a.exp_mode, a.lm, a.n_lm, a.lm_index, a.lm_weight, a.token_score,
+                       a.workspace, a.tokens, a.timesteps, a.counts, a.scores, a.hyp_counts);
 }
 
 }  // namespace amx
