@@ -344,6 +344,114 @@ def heads_case_spec(dependency_blanks: bool) -> Dict[str, Any]:
     return spec
 
 
+# ----------------------------------------------------------------------------------------------------------------------------
+# heads models: the geometry switches of the row kernels of the heads, of ``create_heads`` and of the composition product that
+# ``heads_case_spec`` and the encoder cases do not cross (tests/test_gpu_stage_heads.py; CPU proof: tests/test_stage_util.py).
+# Each returns (spec, state dict, inventories); an uncomposed model has the one inventory ``None``.
+# ----------------------------------------------------------------------------------------------------------------------------
+def heads_audio(seed: int) -> Tuple[Tensor, Tensor]:
+    """The batch of every heads model: three ragged utterances of at most 3 s and a fourth of 400 samples -- 149 frames (more than
+    128 keys, not a multiple of 4) down to exactly one frame, i.e. a time-layer row of one valid key"""
+    audio, lengths = synthetic.make_audio(3, 48000, seed=seed, ragged=True)
+    one_frame = synthetic.make_audio(1, 400, seed=seed + 1)[0]
+    audio = torch.cat([audio, F.pad(one_frame, (0, audio.shape[1] - 400))])
+    return audio, torch.cat([lengths, torch.tensor([400])])
+
+
+def _sized(spec: Dict[str, Any], sizes: Dict[str, int]) -> None:
+    for c in spec["classes"]:
+        if c["name"] in sizes:
+            c["size"] = sizes[c["name"]]
+
+
+def narrow_wide_model():
+    """Log-softmax outputs of 2, 7, 8 | 9, 10 classes (lane-local up to 8, whole-wave beyond), phoneme outputs of 4 (lane-local), 64
+    and 65 classes (one wave stride, and one past it) from three inventories, a composition with K = 40 inside a 32-element group
+    of its 64-wide planes and N = 4 / 64 / 65, five direct heads in one stack."""
+    sizes = {"a1": 1, "a6": 6, "a7": 7, "a8": 8, "a9": 9}
+    spec = S.multitask_spec(S.tiny_encoder(1), list(sizes), embedding_size=40, train_phonemes=12, n_features=6, allophone_layer=True)
+    _sized(spec, sizes)
+    S.validate(spec)
+    return spec, synthetic.make_state_dict(spec, seed=31), [synthetic.make_inventory(spec, p, seed=31) for p in (3, 63, 64)]
+
+
+def large_inventory_model():
+    """The released head shape: a 640-wide composition with 37 features into 201 and 1026 classes (N odd and four-digit, the
+    log-softmax over hundreds and over more than 1024 columns), next to two 4-class heads."""
+    spec = S.multitask_spec(S.tiny_encoder(1), ["syllabic", "long"], embedding_size=640, train_phonemes=64, n_features=37)
+    S.validate(spec)
+    return spec, synthetic.make_state_dict(spec, seed=32), [synthetic.make_inventory(spec, p, seed=32) for p in (200, 1025)]
+
+
+def many_outputs_model():
+    """71 outputs: 70 attribute heads of 2 .. 10 classes (the second round of the lane-local log-softmax, which walks 64 outputs at
+    a time) and a plain phoneme head of 41, all direct: one stack whose N is the sum of the widths (454)."""
+    names = [f"attribute{i:02d}" for i in range(70)]
+    spec = S.baseline_spec(S.tiny_encoder(1), 40)
+    spec["classes"] = [{"name": n, "size": 1 + i % 9, "dependencies": [S.OUTPUT]} for i, n in enumerate(names)] + spec["classes"]
+    S.validate(spec)
+    return spec, synthetic.make_state_dict(spec, seed=33), [None]
+
+
+def wide_dependency_model(dependency_blanks: bool, encoder: Optional[Dict[str, Any]] = None):
+    """``concat_kernel``: a softmax part of 71 (70 without the blanks) columns, hidden-state parts that are not first
+    (``[wide, OUTPUT_0, other]``, ``[OUTPUT, wide, second, OUTPUT_1]``), concatenated widths of 224 (no zero fill) and 353 (one past
+    a multiple of 32 and of 8) with the blanks, 222 and 351 without; ``create_heads``: direct heads before (``wide``, ``other``)
+    and after (``late``) a dependent one, so two stacks.  Classifiers on ``OUTPUT_0`` / ``OUTPUT_1``: a pass without the keep
+    flag hands out every hidden state.  ``encoder``: two layers (default: the tiny one)."""
+    enc = dict(encoder or S.tiny_encoder(2))
+    assert enc["layers"] == 2
+    spec = S.hierarchical_spec(enc, ["wide", "other", "second", "late"], embedding_size=32, train_phonemes=12, n_features=6,
+                               dependency_blanks=dependency_blanks)
+    _sized(spec, {"wide": 70, "other": 24, "second": 25, "late": 4})
+    by_name = {c["name"]: c for c in spec["classes"]}
+    by_name["second"]["dependencies"] = ["wide", "OUTPUT_0", "other"]
+    by_name[S.PHONEME]["dependencies"] = [S.OUTPUT, "wide", "second", "OUTPUT_1"]
+    S.validate(spec)
+    return spec, synthetic.make_state_dict(spec, seed=34), [synthetic.make_inventory(spec, 9, seed=34)]
+
+
+def narrow_layout_model(dependency_blanks: bool = True):
+    """``wide_dependency_model`` on an encoder whose conv and FFN widths (24, 72) are no multiples of 32: separate planes, rows
+    padded to 8 instead of 32 (``kalign``)"""
+    enc = S.tiny_encoder(2)
+    enc.update(conv_dim=24, ffn=72)
+    return wide_dependency_model(dependency_blanks, enc)
+
+
+TIME_LAYER_COMPOSITIONS = ((64, 1), (192, 2), (160, 1))  # embedding size, heads of the phoneme head: head dimensions 64, 96, 160
+
+
+def time_layer_model(embedding_size: int, heads: int):
+    """``time_attention_kernel`` / ``time_ln_pe_kernel``: time-layer heads of (width, heads) (6, 6), (6, 2), (10, 2), (40, 1) --
+    head dimensions 1 (64 key groups), 3 and 5 (idle lanes), 40 -- with positions except on ``t62``, which reads the softmax of
+    ``t66`` in front of ``OUTPUT``; widths below 64 in rows padded to 32 / 64.  The composed phoneme head behind a time layer of
+    head dimension 64, 96 (a partial second round of 64 columns) or 160 (three rounds): ``TIME_LAYER_COMPOSITIONS``."""
+    sizes = {"t66": 5, "t62": 5, "t102": 9, "t401": 39}
+    spec = S.hierarchical_spec(S.tiny_encoder(1), list(sizes), embedding_size=embedding_size, train_phonemes=12, n_features=6)
+    _sized(spec, sizes)
+    by_name = {c["name"]: c for c in spec["classes"]}
+    by_name["t66"]["time_layer"] = {"num_heads": 6, "positional_embeddings": True}
+    by_name["t62"].update(dependencies=["t66", S.OUTPUT], time_layer={"num_heads": 2, "positional_embeddings": False})
+    by_name["t102"]["time_layer"] = {"num_heads": 2, "positional_embeddings": True}
+    by_name["t401"]["time_layer"] = {"num_heads": 1, "positional_embeddings": True}
+    by_name[S.PHONEME].update(dependencies=[S.OUTPUT, "t102"], time_layer={"num_heads": heads, "positional_embeddings": True})
+    S.validate(spec)
+    return spec, synthetic.make_state_dict(spec, seed=35 + heads), [synthetic.make_inventory(spec, 9, seed=35)]
+
+
+# name -> factory: the cases of tests/test_stage_util.py (CPU proof) and of tests/test_gpu_stage_heads.py
+HEADS_MODELS = {
+    "narrow_wide": narrow_wide_model,
+    "large_inventory": large_inventory_model,
+    "many_outputs": many_outputs_model,
+    "wide_dependency": lambda: wide_dependency_model(True),
+    "wide_dependency/no_blanks": lambda: wide_dependency_model(False),
+    "narrow_layout": narrow_layout_model,
+    **{f"time_layers/dh{e // h}": (lambda e=e, h=h: time_layer_model(e, h)) for e, h in TIME_LAYER_COMPOSITIONS},
+}
+
+
 def tapped_spec(encoder: Dict[str, Any], **heads: int) -> Dict[str, Any]:
     """The two-layer hierarchical model of the production cases: ``syllabic`` reads ``OUTPUT_0`` and the phoneme head reads
     ``cat(OUTPUT, softmax(syllabic), softmax(long), OUTPUT_1)``, so a pass keeps every hidden state a classifier reads and
@@ -409,13 +517,18 @@ def shortest_longest_and(lengths: Tensor, more: int) -> List[int]:
     return sorted({order[0], order[-1], *inner})
 
 
-def judged(run, device_out, frame_lengths: Sequence[int], precision: str) -> Tuple[float, float]:
+def judged(run, device_out, frame_lengths: Sequence[int], precision: str,
+           each: Optional[Dict[str, Tuple[float, float]]] = None) -> Tuple[float, float]:
     """One stage of a GPU case: ``run(ev)`` evaluates it from the device's input; returns (the device's error, e_emu of
-    ``precision``), both against the float64 truth over the valid frames."""
+    ``precision``), both against the float64 truth over the valid frames.  ``each`` (the heads, name -> tensor): filled with the
+    same pair per output."""
     with torch.inference_mode():
         truth = run(Evaluation("truth"))
-        e_emu = against(run(Evaluation(precision)), truth, frame_lengths)
-        return against(device_out, truth, frame_lengths), e_emu
+        emulated = run(Evaluation(precision))
+        if each is not None:
+            for k in truth:
+                each[k] = (max_abs_valid(device_out[k], truth[k], frame_lengths), max_abs_valid(emulated[k], truth[k], frame_lengths))
+        return against(device_out, truth, frame_lengths), against(emulated, truth, frame_lengths)
 
 
 def report(name: str, precision: str, found: Dict[str, Tuple[float, float]]) -> None:

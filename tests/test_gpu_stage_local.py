@@ -23,7 +23,9 @@ flag takes instead -- packed rows, the conv extractor's per-utterance tiles, the
 recorded graph -- is held to the same gate by tests/test_gpu_stage_production.py (packed and padded rows are the same bits only on
 the tiny model, so the budget does not carry over by itself).  The XLS-R 1B / 2B widths and head dimensions other than 64, whose
 attention, row-kernel, fold and positional-convolution instances no case here reaches, are held to it by
-tests/test_gpu_stage_widths.py.
+tests/test_gpu_stage_widths.py.  The heads stage at the geometries no case here reaches -- both paths and every stride of the
+log-softmax, wide and late parts of the concatenation, a second stack of direct heads, compositions of 4 .. 1026 classes,
+time-layer head dimensions 1 .. 160 -- is held to it by tests/test_gpu_stage_heads.py, with the helpers of this file.
 
 Not covered: the single-plane modes (``f16``, ``bf16``): no cross terms to lose; they keep their own bounds.
 """
@@ -47,10 +49,13 @@ def amd():
     return estimator
 
 
-def device_pass(amd, spec, state, tfi, audio, lengths, precision, expect, log_probabilities=True):
-    """one ``predict(..., _keep_hidden=True)``: the conv output, every hidden state and the outputs, on the host, batch-major"""
+def device_pass(amd, spec, state, tfi, audio, lengths, precision, expect, log_probabilities=True, est=None):
+    """one ``predict(..., _keep_hidden=True)``: the conv output, every hidden state and the outputs, on the host, batch-major.
+    ``est``: an estimator of the caller's that has run other passes (and stays open) instead of a fresh one"""
     n = audio.shape[0]
-    est = amd.Estimator(spec, state, "cuda:0", precision)
+    own = est is None
+    if own:
+        est = amd.Estimator(spec, state, "cuda:0", precision)
     try:
         pred = est.predict(amd.Batch(audio.cuda(), lengths, torch.zeros(n, dtype=torch.long)), tfi, log_probabilities, _keep_hidden=True)
         info = est.pass_info()
@@ -62,16 +67,19 @@ def device_pass(amd, spec, state, tfi, audio, lengths, precision, expect, log_pr
                 "outputs": {k: v.cpu().transpose(0, 1) for k, v in pred.outputs.items()},
                 "frames": pred.lengths.cpu(), "ln_fold": info["ln_fold"] == 1}
     finally:
-        est.close()
+        if own:
+            est.close()
 
 
 _conv_truth, _conv_e_emu = {}, {}  # the conv stage's input is the audio: its truth and e_emu do not depend on the device
 
 
-def stage_ratios(name, got, spec, state, tfi, audio, lengths, precision, picks, log_probabilities=True, conv_key=None):
+def stage_ratios(name, got, spec, state, tfi, audio, lengths, precision, picks, log_probabilities=True, conv_key=None,
+                 per_output=False):
     """``got``: a ``device_pass``.  Per stage, from the device's input to it and over utterances ``picks``: the truth, e_emu of
     ``precision`` and the device's error; prints and returns {stage: (device error, e_emu)}.  ``conv_key``: runs that differ in
-    nothing the conv stage sees (precision apart) share its truth and e_emu under this key."""
+    nothing the conv stage sees (precision apart) share its truth and e_emu under this key.  ``per_output``: also prints the
+    pair of every output of the heads (``heads/<output>``), for information: the gate is on the joint one."""
     picks = list(picks)
     frames = got["frames"][picks]
     offsets = synthetic.category_offsets(spec) if spec.get("embedding_size") else None
@@ -99,10 +107,11 @@ def stage_ratios(name, got, spec, state, tfi, audio, lengths, precision, picks, 
         judge(f"layer{i}", lambda ev, i=i: SU.layer_stage(got["hidden"][i][picks], frames, state, spec, ev, i, fold=got["ln_fold"]),
               got["hidden"][i + 1][picks])
     heads_in = {i: got["hidden"][i][picks] for i in SU.hidden_inputs(spec)}
-    judge("heads" if log_probabilities else "heads (logits)",
-          lambda ev: SU.heads_stage(heads_in, frames, state, spec, tfi, offsets, ev)[1 if log_probabilities else 0],
-          {k: v[picks] for k, v in got["outputs"].items()})
+    heads, each = "heads" if log_probabilities else "heads (logits)", {}
+    found[heads] = SU.judged(lambda ev: SU.heads_stage(heads_in, frames, state, spec, tfi, offsets, ev)[1 if log_probabilities else 0],
+                             {k: v[picks] for k, v in got["outputs"].items()}, frames, precision, each if per_output else None)
     SU.report(name, precision, found)
+    SU.report(name, precision, {f"{heads}/{k}": v for k, v in each.items()})
     return found
 
 

@@ -57,14 +57,17 @@ def device_pass(amd, spec, state, tfi, audio, lengths, precision, expect, log_pr
 _entry_truth, _entry_e_emu = {}, {}  # the entry stage's input is the audio: its truth and e_emu do not depend on the device
 
 
-def stage_ratios(name, got, spec, state, tfi, audio, lengths, precision, picks, log_probabilities=True, entry_key=None):
+def stage_ratios(name, got, spec, state, tfi, audio, lengths, precision, picks, log_probabilities=True, entry_key=None,
+                 per_output=False):
     """``got``: a ``device_pass``.  Per stage (``entry``, every ``layer<i>`` and ``heads``; post-LN: the last layer and the heads
     as ``tail``), from the device's input to it and over utterances ``picks``: the truth, e_emu of ``precision`` and the device's
     error; prints and returns {stage: (device error, e_emu)}.  ``entry_key``: runs that differ in nothing the entry stage sees
-    (precision apart) share its truth and e_emu under this key."""
+    (precision apart) share its truth and e_emu under this key.  ``per_output``: also prints the pair of every output of the
+    heads (``heads/<output>``), for information."""
     picks = list(picks)
     frames = got["frames"][picks]
     offsets = synthetic.category_offsets(spec)
+    each = {}
     layers, hidden = spec["layers"], got["hidden"]
     assert torch.equal(got["frames"], torch.tensor(S.frame_lengths(lengths.tolist(), spec)))
     found = {}
@@ -91,11 +94,12 @@ def stage_ratios(name, got, spec, state, tfi, audio, lengths, precision, picks, 
     taps = {i: hidden[i][picks] for i in SU.hidden_inputs(spec) if i < len(hidden)}
     if len(hidden) == layers + 1:
         found["heads" + suffix] = SU.judged(lambda ev: SU.heads_stage(taps, frames, state, spec, tfi, offsets, ev)[which], outputs,
-                                            frames, precision)
+                                            frames, precision, each if per_output else None)
     else:
         found["tail" + suffix] = SU.judged(
             lambda ev: SU.tail_stage(hidden[layers - 1][picks], taps, frames, state, spec, tfi, offsets, ev)[which], outputs, frames, precision)
     SU.report(name, precision, found)
+    SU.report(name, precision, {f"heads{suffix}/{k}": v for k, v in each.items()})
     return found
 
 

@@ -14,7 +14,8 @@ hierarchical model with time-layer heads that the GPU heads case runs.  For test
 widths (``xlsr_1b``, ``xlsr_2b``: hidden 1280 / 1920, heads of 80 / 120 columns, built like the XLS-R case) and the tiny models with
 head dimensions 40, 8, 96 and 128 (``dh40`` ...: ``stage_util.HEAD_DIM_MODELS``, 5 ragged utterances of <= 1.5 s).  A (case, mode,
 stage) whose weakest lost term is below 5.0 x e_emu -- ``LISTED_FLOOR`` plus 10 % for the summation order of the BLAS -- is not
-claimed, here or on the GPU: ``stage_util.NOT_CLAIMED``.
+claimed, here or on the GPU: ``stage_util.NOT_CLAIMED``.  For tests/test_gpu_stage_heads.py: the heads models of ``stage_util``
+(``narrow_wide`` ... ``time_layers/dh160``), the heads stage alone, once per inventory, on the batch of ``stage_util.heads_audio``.
 
 The same three things for the two combined stages that tests/test_gpu_stage_production.py judges a pass without the keep flag by:
 ``entry`` (audio -> hidden[0]) on the XLS-R and the tiny post-LN case, ``tail`` (last layer + heads of a post-LN encoder) at
@@ -149,10 +150,11 @@ def head_dim_case(hidden, heads, groups):
 
 class Recipe:
     """a case: how it is built and which stages it gets beyond conv / front / layers / heads.  ``fold``: every layer also the way
-    a pass with the LayerNorm fold runs it; ``entry``: audio -> hidden[0] in one; ``tail_only``: that combined stage alone"""
+    a pass with the LayerNorm fold runs it; ``entry``: audio -> hidden[0] in one; ``tail_only``: that combined stage alone;
+    ``heads_only``: a heads model (``build`` gives (spec, state, inventories)): the heads stage alone, once per inventory"""
 
-    def __init__(self, build, fold=False, entry=False, tail_only=False):
-        self.build, self.fold, self.entry, self.tail_only = build, fold, entry, tail_only
+    def __init__(self, build, fold=False, entry=False, tail_only=False, heads_only=False):
+        self.build, self.fold, self.entry, self.tail_only, self.heads_only = build, fold, entry, tail_only, heads_only
 
 
 CASES = {"xlsr": Recipe(xlsr_case, fold=True, entry=True), "post_ln": Recipe(post_ln_case, entry=True), "heads": Recipe(heads_case),
@@ -160,6 +162,13 @@ CASES = {"xlsr": Recipe(xlsr_case, fold=True, entry=True), "post_ln": Recipe(pos
          "xlsr_1b": Recipe(lambda: width_case(S.xlsr_1b_encoder()), fold=True, entry=True),
          "xlsr_2b": Recipe(lambda: width_case(S.xlsr_2b_encoder()), fold=True, entry=True),
          **{f"dh{hidden // heads}": Recipe(head_dim_case(hidden, heads, groups)) for hidden, heads, groups in SU.HEAD_DIM_MODELS}}
+
+# The heads models of tests/test_gpu_stage_heads.py, the heads stage alone (once per inventory).  The heads are judged jointly, as
+# a maximum over outputs, so an output with a large e_emu could hide a lost term of a quiet one.  The candidate was
+# ``large_inventory`` (the 1026-class log-softmax over the 640-wide composition, e_emu 2.5e-5 / 2.5e-4, next to 4-class heads): its
+# weakest term, lo(W) of ``syllabic.linear`` on bf16 planes, still lands at 30 x e_emu, so no model had to be split.
+HEADS_AUDIO_SEED = 97
+CASES.update({name: Recipe(build, heads_only=True) for name, build in SU.HEADS_MODELS.items()})
 
 
 def _named(logits, logp, transpose=False):
@@ -220,9 +229,25 @@ class Case:
 
         self.name = name
         recipe = CASES[name]
+        self._measured = {}
+        if recipe.heads_only:
+            spec, state, inventories = recipe.build()
+            audio, lengths = SU.heads_audio(HEADS_AUDIO_SEED)
+            offsets = synthetic.category_offsets(spec) if spec.get("embedding_size") else None
+            with torch.inference_mode():
+                hidden, frames, _ = O.wav2vec2_hidden_states(audio, lengths, state, spec, False, False)
+            heads_in = {i: hidden[i] for i in SU.hidden_inputs(spec)}
+            self.stages = []
+            for tfi in inventories:
+                with torch.inference_mode():
+                    raw = O.projection_forward([h.transpose(0, 1) for h in hidden], state, spec, tfi, offsets, frames)
+                    ref = {k: torch.log_softmax(v, -1) for k, v in raw.items()}
+                stage = "heads" if tfi is None or len(inventories) == 1 else f"heads/{tfi.shape[0]}"
+                self.stages.append(Stage(stage, lambda ev, tfi=tfi: _named(*SU.heads_stage(heads_in, frames, state, spec, tfi, offsets, ev)),
+                                         _named(raw, ref, transpose=True), frames))
+            return
         spec, state, tfi, audio, lengths = recipe.build()
         offsets = synthetic.category_offsets(spec)
-        self._measured = {}
         if recipe.tail_only:
             with torch.inference_mode():
                 ref, frames, inter = O.predict(audio, lengths, state, spec, tfi, offsets, keep_intermediates=True)
