@@ -4,7 +4,7 @@
 // Pure host logic: nothing is launched and no GPU is needed (device_cus() falls back to 256, the MI355X's count; the last line
 // names the count used).  So that the recording stays a small file, a block is printed as a digest of its lines; in clear text come
 // the flagship's own products (xlsr, f16x3, with workspace) and, at the end, the first case that reached each distinct route.
-// `route_dump full` prints every line instead.
+// `route_dump full` prints every line instead; `route_dump rows ...` the products of one layer at a given row count (rows_mode).
 // Everything except describe() uses the public queries only and compiles unchanged against an older csrc (-I pointing there, with
 // -DROUTE_DUMP_PUBLIC_ONLY where that csrc has no gemm_route: compare the columns up to the second bar of `route_dump full`).
 #include "amx_gemm.hip"
@@ -180,11 +180,9 @@ struct Layer {
     }
 };
 
-static void layer_rows(const Ctx& c, const Encoder& e, const Geo& geo, bool packed) {
-    const int T = (int)frames((int64_t)geo.seconds * 16000, nullptr);
-    const Layer L{c, e, packed ? packed_rows(geo) : (int64_t)geo.N * T, packed, T};
-    char where[64];
-    snprintf(where, sizeof where, "%dx%ds%s", geo.N, geo.seconds, packed ? "-packed" : "");
+// the products of one layer on Mrows rows (padded: utterances of T frames each)
+static void layer_rows_at(const Ctx& c, const Encoder& e, int64_t Mrows, bool packed, int T, const char* where) {
+    const Layer L{c, e, Mrows, packed, T};
     row(c.prec, L.qkv(), "%s-qkv", where);
     row(c.prec, L.oproj(), "%s-oproj", where);
     row(c.prec, L.ffn1(), "%s-ffn1", where);
@@ -199,6 +197,13 @@ static void layer_rows(const Ctx& c, const Encoder& e, const Geo& geo, bool pack
     if (!packed) { g.row_len = fake<int>(0xD00000); g.rows_T = T; }
     g.out_f32 = fake<float>(0x700000); g.ldo = e.D;
     row(c.prec, c.with_ws(g), "%s-featproj", where);
+}
+
+static void layer_rows(const Ctx& c, const Encoder& e, const Geo& geo, bool packed) {
+    const int T = (int)frames((int64_t)geo.seconds * 16000, nullptr);
+    char where[64];
+    snprintf(where, sizeof where, "%dx%ds%s", geo.N, geo.seconds, packed ? "-packed" : "");
+    layer_rows_at(c, e, packed ? packed_rows(geo) : (int64_t)geo.N * T, packed, T, where);
 }
 
 // conv layers 1 .. 6: implicit GEMMs over channels-last rows, as the unfused product and with the fused LayerNorm + GELU
@@ -434,7 +439,39 @@ static void grouped_rows(const Ctx& c) {
         }
 }
 
+// `route_dump rows <encoder> <precision> <packed 0|1> <M> [T]`: the products of one layer at an arbitrary row count (with the
+// split-K workspace, as a pass has it; padded rows: utterances of T frames), in the clear-text row format
+static int rows_mode(int argc, char** argv) {
+    if (argc < 6) {
+        fputs("usage: route_dump rows <encoder> <precision> <packed 0|1> <M> [T]\n", stderr);
+        return 2;
+    }
+    const Encoder* e = nullptr;
+    for (const Encoder& k : ENCODERS)
+        if (k.name == std::string(argv[2])) e = &k;
+    int prec = -1;
+    for (int i = 0; i < 4; ++i)
+        if (PREC_NAME[i] == std::string(argv[3])) prec = i;
+    const bool packed = atoi(argv[4]) != 0;
+    const int64_t M = atoll(argv[5]);
+    const int T = argc > 6 ? atoi(argv[6]) : (int)M;
+    if (!e || prec < 0 || M < 1 || T < 1 || (!packed && M % T)) {
+        fputs("route_dump rows: unknown encoder or precision, or M is no multiple of T\n", stderr);
+        return 2;
+    }
+    g_full = true;
+    fputs(HEADER, stdout);
+    begin_block("rows", true);
+    char where[64];
+    snprintf(where, sizeof where, "%lldx%d%s", (long long)(packed ? 1 : M / T), packed ? (int)M : T, packed ? "-packed" : "");
+    layer_rows_at(Ctx{prec, prec_planes(prec) > 1, true}, *e, M, packed, T, where);
+    end_block();
+    printf("%ld cases, cus %d\n", g_cases, device_cus());
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "rows") return rows_mode(argc, argv);
     g_full = argc > 1 && std::string(argv[1]) == "full";
     const int precs[] = {PREC_BF16, PREC_F16, PREC_BF16X3, PREC_F16X3};
     fputs(HEADER, stdout);

@@ -25,7 +25,9 @@ the tiny model, so the budget does not carry over by itself).  The XLS-R 1B / 2B
 attention, row-kernel, fold and positional-convolution instances no case here reaches, are held to it by
 tests/test_gpu_stage_widths.py.  The heads stage at the geometries no case here reaches -- both paths and every stride of the
 log-softmax, wide and late parts of the concatenation, a second stack of direct heads, compositions of 4 .. 1026 classes,
-time-layer head dimensions 1 .. 160 -- is held to it by tests/test_gpu_stage_heads.py, with the helpers of this file.
+time-layer head dimensions 1 .. 160 -- is held to it by tests/test_gpu_stage_heads.py, with the helpers of this file.  Where a row
+count ends inside the last row tile of a product -- every residue at which the edge epilogues, the fix-ups and the short tiles take
+another path, and both sides of the routing thresholds -- is held to it by tests/test_gpu_stage_row_edges.py.
 
 Not covered: the single-plane modes (``f16``, ``bf16``): no cross terms to lose; they keep their own bounds.
 """

@@ -18,7 +18,8 @@ Every case pins its route through ``pass_info()``.  ``test_fetch_of_packed_rows_
 offsets) to the padded pass on the tiny model, where both layouts give the same bits: a wrong row offset cannot pass as kernel
 error here, nor kernel error as a fetch bug.
 
-Not held: the single-plane modes (``f16``, ``bf16``: no cross terms to lose; they keep their own bounds).
+Not held: the single-plane modes (``f16``, ``bf16``: no cross terms to lose; they keep their own bounds).  The row counts here end
+each product's last row tile wherever they happen to; tests/test_gpu_stage_row_edges.py holds the chosen residues, with these helpers.
 """
 import pytest
 import torch
